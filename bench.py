@@ -16,12 +16,16 @@ Modes
 After each step the per-world records are all-gathered over RCCL and rank 0 takes the argmin over
 feasible worlds (the only collective on this path).
 
-Rank 0 at N = 1 also reports: the roofline of the reach kernel (its timed-region launches'
+A plain run does what the headline figure needs: set-up, warmup, the timed steps, the outputs if
+--dump-outputs is given, and the result line (`roofline`, `cpu_baseline`: null).
+
+With --full, rank 0 at N = 1 also reports: the roofline of the reach kernel (its timed-region launches'
 device-clock spans; HIP events under load and the kernel alone beside them) and SURVEY §8(d)'s per-plan byte count B_plan = B_setup + E * B_eval; the measured copy peak;
 single-plan latency (the drop-in's use: one world per call) at T = 100 and 128 and the wall time of
 the armour_main process; the CPU baseline (the oracle on config 1, 1 thread and the box's share).
 
 Usage: python bench.py [--gpus N --steps K --warmup W --batch B --planners P --total-worlds N]
+                       [--dump-outputs DIR] [--full [--cpu-seconds S] [--no-extras]]
        (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 Prints ONE JSON line on rank 0.
 """
@@ -70,8 +74,17 @@ def parse():
     ap.add_argument("--robot", default="kinova", choices=["kinova", "fetch"],
                     help="kinova: built-in Gen3 tables (configs 1-4); fetch: tests/golden/robot_fetch.json, the "
                          "Fetch arm from its URDF (config 5, at fp64)")
-    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="per CPU-baseline leg (0: skip)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the N=1 extras (latency, copy peak, roofline)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure, at N = 1, the extras (roofline of the reach kernel, "
+                         "per-plan bytes, iteration-limit study, copy peak, single-plan latency) and the CPU baseline; "
+                         "off by default: a plain run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="with --full: per CPU-baseline leg (0: skip)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the N=1 extras (latency, copy peak, roofline)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step returned to its caller as DIR/<name>.npy (float64, world "
+                         "order): every world's k_opt, cost, feasible, status, iterations, evaluations and kkt from "
+                         "Planner.plan, the gathered records and the index of the best feasible world")
     ap.add_argument("--dump-records", default="",
                     help="rank 0 saves the last step's gathered per-world records (armour_amd.dist.RECORD layout, "
                          "world order) to this .npy file (tests/test_gpu_dist.py compares them with the oracle)")
@@ -200,7 +213,8 @@ def latency(A, O, robot, geo):
     exe = os.path.join(ROOT, "armour-dev_amd", "armour_amd", "armour_main")
     if robot is None and os.path.exists(exe):
         q0, qd0, qdd0, qdes, obs = A.make_world(50_000, O, geo, profile="survey")
-        with tempfile.TemporaryDirectory() as d:
+        # right under /tmp: <d>/armour.sock of the served leg has to fit sockaddr_un's 108 bytes
+        with tempfile.TemporaryDirectory(dir="/tmp") as d:
             with open(os.path.join(d, "armour.in"), "w") as f:
                 for v in (q0, qd0, qdd0, qdes):
                     f.write(" ".join(f"{x:.10f}" for x in v) + "\n")
@@ -261,8 +275,22 @@ def per_plan_bytes(P, res, T, O, NJ, reach_bytes, nsample=8):
     return dict(B_setup=B_setup, B_eval=B_eval, E=E, B_plan=B_setup + E * B_eval, M_links=M_links, M_tau=M_tau)
 
 
+def dump_outputs(d, res, allrec, best):
+    """the last timed step's outputs as float64 .npy files: rank 0's Planner.plan results (at N = 1
+    every world of the step, in world order), the gathered records (armour_amd.dist.RECORD layout)
+    and the argmin over feasible worlds"""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "k_opt.npy"), np.array([r["k_opt"] for r in res], dtype=np.float64).reshape(len(res), -1))
+    for k in ("cost", "feasible", "status", "iterations", "evaluations", "kkt"):
+        np.save(os.path.join(d, k + ".npy"), np.array([float(r[k]) for r in res], dtype=np.float64))
+    np.save(os.path.join(d, "records.npy"), np.asarray(allrec, dtype=np.float64))
+    np.save(os.path.join(d, "best.npy"), np.array([best], dtype=np.float64))
+
+
 def main():
     a = parse()
+    if a.steps < 1:
+        raise SystemExit("bench: --steps must be at least 1")
     rank = int(os.environ.get("RANK", "0"))
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -435,6 +463,8 @@ def main():
         return
     if a.dump_records:
         np.save(a.dump_records, allrec)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, res, allrec, best)
     total_plans = a.steps * total_job
     value = total_plans / elapsed
     n_feas = int(allrec[:, 8].sum())
@@ -476,7 +506,7 @@ def main():
         "roofline": None,
         "cpu_baseline": None,
     }
-    if world_size == 1 and not a.no_extras:
+    if a.full and world_size == 1 and not a.no_extras:
         # Roofline of the dominant kernel (the bundle reach kernel) over the timed region's own
         # launches: its algorithmic bytes per launch over the mean execution span of those launches
         # on the device clock (first workgroup start to last workgroup end, armour_get_reach_span:
@@ -561,7 +591,7 @@ def main():
         for p in planners[1:]:
             p.close()
         line["latency"] = latency(A, a.O, robot, geo)
-    if a.cpu_seconds > 0 and world_size == 1:   # the CPU baseline is an N = 1 figure (rank 0 only)
+    if a.full and a.cpu_seconds > 0 and world_size == 1:   # the CPU baseline is an N = 1 figure (rank 0 only)
         rs = None
         if robot is not None:
             from armour_amd import robot_tables as RT

@@ -1,6 +1,7 @@
 """ARMTD comparison planner (ACMP/, oracle/src/armtd.cpp): the oracle against the committed
 fixtures (tests/golden/armtd_T100_O10.npz, tests/golden/make_armtd.py) and against the reference's
-own definitions; the fixtures' JRS tables against the reference's offline JRS files when present."""
+own definitions; the fixtures' JRS tables against the reference's offline JRS files (the ones the
+test needs are stored under tests/golden/offline_jrs/)."""
 import os
 
 import numpy as np
@@ -61,13 +62,12 @@ def test_layout_and_extrema():
 
 def test_tables_are_the_reference_offline_jrs():
     """the fixture's tables are the slices of ACMP/offline_jrs/orig_parameterization/JRS_<c_kvi>.mat
-    the MATLAB caller makes (KSI/uarmtd_planner.m:260-318)"""
+    the MATLAB caller makes (KSI/uarmtd_planner.m:260-318); tests/golden/offline_jrs/ holds the
+    reference's files of the c_kvi that worlds 0 and 3 select, unchanged"""
     import offline_jrs as J
 
-    if not os.path.isdir(J.JRS_DIR):
-        pytest.skip("reference not present")
     fx = load()
     for w in (0, 3):
-        tab, kr = J.armtd_input(fx["qd0"][w])
+        tab, kr = J.armtd_input(fx["qd0"][w], jrs_dir=os.path.join(GOLD, "offline_jrs"))
         np.testing.assert_array_equal(tab, fx["tables"][w])
         np.testing.assert_array_equal(kr, fx["k_range"][w])

@@ -1,7 +1,10 @@
 """The drop-in executable armour_main speaks the reference's file protocol
 (kinova_planner_realtime/armour_main.cu:5-10, 37-77, 319-398)."""
 import os
+import pathlib
+import shutil
 import subprocess
+import tempfile
 
 import numpy as np
 import pytest
@@ -98,7 +101,16 @@ def _outputs(path):
     return {n: open(os.path.join(path, n)).read() for n in names}
 
 
-def test_served_mode_matches_in_process(tmp_path):
+@pytest.fixture
+def short_tmp():
+    """a directory right under /tmp for the served tests: <buffer>/armour.sock has to fit
+    sockaddr_un's 108 bytes, which pytest's tmp_path under a deep base directory does not"""
+    d = pathlib.Path(tempfile.mkdtemp(prefix="armour_", dir="/tmp"))
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
+
+
+def test_served_mode_matches_in_process(short_tmp):
     """`armour_main --serve` keeps one planner warm; a plain armour_main run then forwards its
     buffer directory over <buffer>/armour.sock and exits with the server's status. The five output
     files must be byte-identical to an in-process run, failures included, and a served replan
@@ -106,7 +118,7 @@ def test_served_mode_matches_in_process(tmp_path):
     import time
 
     T = 20
-    srv, loc = tmp_path / "srv", tmp_path / "loc"
+    srv, loc = short_tmp / "srv", short_tmp / "loc"
     srv.mkdir()
     loc.mkdir()
     env = dict(os.environ, ARMOUR_NUM_TIME_STEPS=str(T))
@@ -147,7 +159,7 @@ def test_served_mode_matches_in_process(tmp_path):
     assert not (srv / "armour.sock").exists()
 
 
-def test_served_late_plan_is_discarded(tmp_path):
+def test_served_late_plan_is_discarded(short_tmp):
     """A client that times out (ARMOUR_SERVE_TIMEOUT_MS) writes -1 and exits non-zero; the server's
     plan for it finishes later (ARMOUR_SERVE_DELAY_MS holds it back here) and must not land in the
     buffer directory: the server commits its .part files only while the client still waits, under
@@ -155,7 +167,7 @@ def test_served_late_plan_is_discarded(tmp_path):
     import time
 
     T = 20
-    srv = tmp_path / "srv"
+    srv = short_tmp / "srv"
     srv.mkdir()
     env = dict(os.environ, ARMOUR_NUM_TIME_STEPS=str(T))
     server = subprocess.Popen([EXE, "--serve", str(srv)], env=dict(env, ARMOUR_SERVE_DELAY_MS="1500"),

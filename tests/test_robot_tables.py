@@ -11,13 +11,11 @@ Pins (reference data, copied as values):
 import os
 
 import numpy as np
-import pytest
 
 import armour_amd as A
 from armour_amd import robot_tables as RT
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-REF = "/root/reference"
 
 # ACMP/FetchInfo.h:17-58, first 8 of its 9 joints (the 9th is a fixed payload link)
 FETCH_INFO = dict(
@@ -75,13 +73,15 @@ def test_fetch_urdf_tables_equal_fetch_info():
     assert not np.any(np.all(np.isclose(gen["link_generators"], 0.05), axis=1))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
 def test_fixtures_regenerate_from_the_reference():
+    """from the reference's two URDFs and their links' meshes as stored under tests/golden/urdfs/
+    (tests/golden/make_robot_meshes.py: the URDFs as they are, the meshes thinned with their bounds
+    kept to the bit, which is all the tables take from a mesh)"""
     import importlib.util
     spec = importlib.util.spec_from_file_location("make_robots", os.path.join(GOLD, "make_robots.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    for name, tables in mod.generate(REF).items():
+    for name, tables in mod.generate(GOLD).items():
         saved = RT.load_json(os.path.join(GOLD, name))
         fresh = RT._shaped(RT.from_struct(RT.to_struct(tables)))
         for k, v in saved.items():

@@ -7,8 +7,11 @@ client plans in-process. A server that never answers ends the client within
 ARMOUR_SERVE_TIMEOUT_MS with -1 in armour.out and a non-zero status; armour.out never keeps a
 previous replan's k_opt (KSI/uarmtd_planner.m:202-204 reads it whenever the exit status is 0)."""
 import os
+import pathlib
+import shutil
 import socket
 import subprocess
+import tempfile
 import threading
 import time
 
@@ -52,12 +55,16 @@ def _env(**kw):
 
 
 @pytest.fixture
-def bufdir(tmp_path):
+def bufdir():
+    """a buffer directory right under /tmp: <dir>/armour.sock has to fit sockaddr_un's 108 bytes,
+    which pytest's tmp_path under a deep base directory does not"""
     if not os.path.exists(EXE):
         subprocess.run(["make", "-C", os.path.join(ROOT, "armour-dev_amd", "csrc")], check=True, capture_output=True)
-    (tmp_path / "armour.in").write_text("0 " * 28 + "0\n")
-    (tmp_path / "armour.out").write_text("0.1\n0.2\n0.3\n0.4\n0.5\n0.6\n0.7\n5")  # a previous replan's plan
-    return tmp_path
+    d = pathlib.Path(tempfile.mkdtemp(prefix="armour_", dir="/tmp"))
+    (d / "armour.in").write_text("0 " * 28 + "0\n")
+    (d / "armour.out").write_text("0.1\n0.2\n0.3\n0.4\n0.5\n0.6\n0.7\n5")  # a previous replan's plan
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
 
 
 def test_request_names_absolute_dir_horizon_and_settings(bufdir):

@@ -8,6 +8,9 @@
 #   pytest ARGS         python -m pytest -m gpu -x -v --timeout 300 --timeout-method thread ARGS
 #   smoke               __graft_entry__.smoke()
 #   bench ARGS          python bench.py ARGS (the JSON line -> gpurun_out/<n>_bench.json)
+#                       (a plain run times the steps only; --full adds the roofline, latency, copy-peak
+#                       and CPU-baseline legs, as does a `stats bench.py --full ...` summary that
+#                       bench.py's rocprof_under_load record is to match)
 #   py SCRIPT ARGS      python -u SCRIPT ARGS
 #   stats SCRIPT ARGS   rocprofv3 --kernel-trace --stats of python SCRIPT ARGS (csv under gpurun_out/<n>_stats/)
 #   pmc 'CTRS' SCRIPT ARGS  one rocprofv3 --pmc pass (counters within one pass's block limits);
