@@ -49,6 +49,9 @@ constexpr int RCH = 6;                    // reduction slots combined per round 
 #ifndef LANE_UC9
 #define LANE_UC9 2                        // concatenations of 3x3 blocks
 #endif
+#ifndef LANE_UXC
+#define LANE_UXC 8                        // monomials per wave round of the PZ x constant cross
+#endif
 
 #define DI __device__ inline __attribute__((always_inline))
 // Explicit address spaces for the simplify round loop: a pointer the
@@ -104,9 +107,6 @@ struct LCtx {
     int* gkp;
     int* ggp;
     int cap_glb;
-    double* gout;          // HBM [cap_out][9][LG]: kept group values between the two passes
-    uint64_t* gm;          // HBM [cap_out]: group keep masks
-    int cap_out;
     uint64_t* rmask;       // LDS [2][64]: keep masks of a simplify round (double-buffered)
     uint64_t* stage;       // LDS staged operand hashes
     int stage_cap;
@@ -1034,87 +1034,120 @@ DI void cross_const_finish(const LCtx& x, const LH& h, const LH& A, const CrossC
         abs_(x, h, e) = red[6 + e];
     }
 }
-// ends with a barrier
+// One compacting pass, as simplify()'s rounds (no sort: the operand's monomials map 1:1, in hash
+// order). Rounds of LW x UXC monomials: in the round that starts at r0 wave w takes k = r0 + w + u LW,
+// u = 0..UXC-1, which is k = w (mod LW) in ascending order, so each wave's pruned sums accumulate in
+// the order of a plain k += LW loop. All of a round's row loads are issued before the first use
+// (clamped index, no branch around a load; only the operand's own rows, global-typed), each wave
+// decides per lane and ballots the keep masks into LDS, and after one barrier every wave knows the
+// round's kept prefix and stores its kept monomials (rows, hash, mask) at their final place. The
+// output reserves N monomials up front and gives back the tail (no other allocation runs meanwhile),
+// as simplify() does: the arena's peak use counts the reservation, so a bundle within N - K monomials
+// of its arena's end overflows here (ERR_ARENA, cnt = 0) and takes the planner's capacity retry.
+// Ends with a barrier.
 DI void cross_const(LCtx& x, int o, int a, const CrossC& C) {
+    constexpr int UXC = LANE_UXC, RG = LW * UXC;
+    static_assert(RG <= 64, "round masks fit one wave ballot");
     const LH& A = x.H[a];
-    const int N = A.cnt;
-    const LSrc S = src_of(x, A);
-    double red[9], out[3], m[9];
+    const int N = ui(A.cnt);
+    double red[9];
 #pragma unroll
     for (int e = 0; e < 9; e++) red[e] = 0.0;
-    int* kp = N <= x.cap_lds ? x.kp : x.gkp;
     if (x.tid == 0) atomicMax(&x.occ[0], N);
-    if (N > x.cap_glb || N > x.cap_out) {
-        if (x.tid == 0) { err_or(x, ERR_SORTCAP); x.H[o].cnt = 0; }
-        combine_red<9>(x, red);
-        return;
+    // (no key buffers and no sort here, so no ERR_SORTCAP: the arena is the only capacity)
+    // the operand, read as LSrc::read does: element e of a full block is row e, of an element view
+    // row comp; a scaled view multiplies; elements beyond the block are zeros
+    const int n = ui(A.R * A.C), stride = ui(A.stride), comp = ui(A.comp), scaled = ui(A.scaled);
+    const double scale = ud(A.scale);
+    GAS const double* const src = gas(up(x.A->c)) + bcast0(A.coff) * LG;
+    GAS const uint64_t* const Sh = gas(up(x.A->h)) + bcast0(A.hoff);
+    GAS const uint64_t* const Sm = gas(up(x.A->m)) + bcast0(A.hoff);
+    long ro[3];
+#pragma unroll
+    for (int e = 0; e < 3; e++) ro[e] = (long)(comp >= 0 ? comp : (e < n ? e : 0)) * LG;
+    if (x.tid == 0) {
+        x.A->hmark = x.A->hused;
+        x.A->cmark = x.A->cused;
+        arena_alloc(x, x.H[o], N, 3);
     }
-    unsigned long long b = 0;
-    // two monomials per trip (k, k + LW: the wave's own order, so the pruned sums accumulate as
-    // before), both monomials' rows loaded before either is used
-    for (int k = x.wave; k < N; k += 2 * LW) {
-        const int k2 = k + LW;
-        const bool has2 = k2 < N;
-        double m2[9];
-        S.read(k, false, m, x.lane);
-        S.read(has2 ? k2 : k, false, m2, x.lane);
-#pragma unroll
-        for (int q = 0; q < 2; q++) {
-            if (q == 1 && !has2) break;
-            const int kk = q == 0 ? k : k2;
-#pragma unroll
-            for (int e = 0; e < 3; e++) out[e] = 0.0;
-            const bool keep = cross_const_mono(C, q == 0 ? m : m2, x.thr, out, red);
-            double* go = x.gout + (long)kk * 3 * LG + x.lane;
-#pragma unroll
-            for (int e = 0; e < 3; e++) go[(long)e * LG] = keep ? out[e] : 0.0;
-            const unsigned long long mk = ballot(keep);
-            if (x.lane == 0) {
-                x.gm[kk] = mk;
-                kp[kk] = mk != 0 ? 1 : 0;
-                b += (unsigned long long)__popcll(S.m[kk]) * 32ull + (unsigned long long)__popcll(mk) * 32ull;
-            }
-        }
-    }
-    if (b) atomicAdd(&x.A->bytes, b);
-    sync();
-    const int K = block_scan(x, kp, N);
-    if (x.tid == 0) arena_alloc(x, x.H[o], K, 3);
     sync();
     const LH& ho = x.H[o];
-    if (ho.cnt == K) {
-        double* dst = x.A->c + ho.coff * LG + x.lane;
-        // two monomials per trip, loads first (clamped), stores of the kept ones after
-        for (int k = x.wave; k < N; k += 2 * LW) {
-            int kk[2];
-            kk[0] = k;
-            kk[1] = k + LW < N ? k + LW : k;
-            bool kept[2];
-            long pos[2];
-            double v[2][3];
+    const bool ok = ui(ho.cnt) == N;
+    GAS double* const dst = gas(up(x.A->c)) + bcast0(ho.coff) * LG;  // wave-uniform; + lane at the store
+    const long hoff = bcast0(ho.hoff);
+    GAS uint64_t* const Ah = gas(up(x.A->h));
+    GAS uint64_t* const Am = gas(up(x.A->m));
+    int base = 0, par = 0;
+    unsigned long long b = 0;
+    for (int r0 = 0; r0 < N; r0 += RG, par ^= 1) {
+        double m[UXC][3];
+        uint64_t hk[UXC], sm[UXC];
 #pragma unroll
-            for (int q = 0; q < 2; q++) {
-                const int j = kk[q];
-                kept[q] = (q == 0 || k + LW < N) && ((j + 1 < N) ? kp[j + 1] != kp[j] : kp[j] != K);
-                pos[q] = kp[j];
-                const double* go = x.gout + (long)j * 3 * LG + x.lane;
+        for (int u = 0; u < UXC; u++) {
+            const int k = min(r0 + x.wave + u * LW, N - 1);
+            GAS const double* const row = src + (long)k * stride * LG + x.lane;
 #pragma unroll
-                for (int e = 0; e < 3; e++) v[q][e] = go[(long)e * LG];
+            for (int e = 0; e < 3; e++) m[u][e] = row[ro[e]];
+            hk[u] = Sh[k];
+            sm[u] = Sm[k];
+        }
+        double out[UXC][3];
+        unsigned long long mk[UXC];
+#pragma unroll
+        for (int u = 0; u < UXC; u++) {
+            const bool in = r0 + x.wave + u * LW < N;  // wave-uniform
+            double v[3];
+#pragma unroll
+            for (int e = 0; e < 3; e++) {
+                double t = m[u][e];
+                if (scaled) t = scale * t;
+                v[e] = e < n ? t : 0.0;
+                out[u][e] = 0.0;
             }
+            bool keep = false;
+            if (in) keep = cross_const_mono(C, v, x.thr, out[u], red);
+            mk[u] = ballot(keep);
+            if (x.lane == 0) x.rmask[par * 64 + u * LW + x.wave] = mk[u];
+            if (in) b += (unsigned long long)__popcll(sm[u]) * 32ull + (unsigned long long)__popcll(mk[u]) * 32ull;
+        }
+        // rmask is double-buffered by the round's parity: a wave that writes half `par` for round
+        // r + 2 has passed round r + 1's barrier, which every wave reaches only after its reads of
+        // that half in round r (they precede the barrier in program order); the other half is the
+        // one round r + 1 uses. So one barrier per round publishes the masks and also keeps a fast
+        // wave out of a half a slower wave still reads. `base` is each wave's own count of the
+        // monomials kept in earlier rounds, formed from the same masks in every wave, so it needs no
+        // publishing. The first round's writes follow the allocation's barrier, behind which no
+        // wave still reads rmask for the operator before.
+        sync();
+        // positions follow k: slot idx = u LW + wave of the round (not wave U + u as in simplify())
+        const unsigned long long km = ballot(x.lane < RG && x.rmask[par * 64 + x.lane] != 0);
 #pragma unroll
-            for (int q = 0; q < 2; q++) {
-                if (!kept[q]) continue;
+        for (int u = 0; u < UXC; u++) {
+            if (mk[u] == 0 || !ok) continue;
+            const int idx = u * LW + x.wave;
+            const long pos = base + __popcll(km & ((1ull << idx) - 1));
 #pragma unroll
-                for (int e = 0; e < 3; e++) dst[(pos[q] * 3 + e) * LG] = v[q][e];
-                if (x.lane == 0) {
-                    x.A->h[ho.hoff + pos[q]] = S.h[kk[q]];
-                    x.A->m[ho.hoff + pos[q]] = x.gm[kk[q]];
-                }
+            for (int e = 0; e < 3; e++) dst[(pos * 3 + e) * LG + x.lane] = out[u][e];
+            if (x.lane == 0) {
+                Ah[hoff + pos] = hk[u];
+                Am[hoff + pos] = mk[u];
             }
         }
+        base += __popcll(km);
+    }
+    if (b && x.lane == 0) atomicAdd(&x.A->bytes, b);
+    if (x.tid == 0 && ok) {
+        // give back the rows of the monomials no lane kept. No barrier before this, unlike
+        // simplify(): every wave read H[o] (ok, dst, hoff) once, right after the allocation's barrier,
+        // and the round loop never reads the handle again (a read added there needs a barrier
+        // here); with N = 0 a late reader sees cnt = 0 = N either way. combine_red's barriers
+        // publish the count before cross_const_finish or the next operator reads it.
+        x.H[o].cnt = base;
+        x.A->hused = x.A->hmark + base;
+        x.A->cused = x.A->cmark + (long)base * 3;
     }
     combine_red<9>(x, red);
-    if (x.wave == 0) cross_const_finish(x, ho, A, C, red);
+    if (x.wave == 0) cross_const_finish(x, x.H[o], A, C, red);
     sync();
 }
 
@@ -1614,6 +1647,7 @@ DI void run_program(LCtx& x, const RobotParams& rp, const Op* prog, int nops, co
                     hdr_zero(x, hv.off, 3);
                 }
                 sync();
+                nterms = x.H[op.a].cnt;
                 cross_const(x, op.o, op.a, C);
                 break;
             }

@@ -34,9 +34,6 @@ struct LaneArgs {
     int* gkp;              // [grid][gcap + 1]
     int* ggp;              // [grid][gcap + 1]
     int gcap;
-    double* gout;          // [grid][ocap][9][LG]
-    uint64_t* gm;          // [grid][ocap]
-    int ocap;
     unsigned long long* bytes;
     double* dump;          // optional [nops][DUMP_W][LG] of bundle 0 (null: off)
     unsigned long long* prof;  // optional [2 * nops + 16] per-op cycles/terms + phase cycles
@@ -91,9 +88,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(LT, LT), amdgpu_waves_per_
     x.gkp = a.gkp + wg * (a.gcap + 1);
     x.ggp = a.ggp + wg * (a.gcap + 1);
     x.cap_glb = a.gcap;
-    x.gout = a.gout + wg * (long)a.ocap * 9 * LG;
-    x.gm = a.gm + wg * (long)a.ocap;
-    x.cap_out = a.ocap;
     x.rmask = rmask;
     x.stage = stage;
     x.stage_cap = S::STAGE;

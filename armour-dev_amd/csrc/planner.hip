@@ -385,7 +385,6 @@ static int planner_init(armour_planner* p, const armour_config* cfg, const armou
         la.hcap = hc ? std::atol(hc) : (1L << 16);
         la.ccap = cc ? std::atol(cc) : (1L << 17);
         la.gcap = 1 << 15;
-        la.ocap = 4096;
         int pool = 0;
         {
             ProgramBuilder pb;
@@ -398,8 +397,7 @@ static int planner_init(armour_planner* p, const armour_config* cfg, const armou
         if ((rc = p->alloc(&la.pool, G * la.pool_rows * LGs)) || (rc = p->alloc(&la.arena_h, G * la.hcap)) ||
             (rc = p->alloc(&la.arena_m, G * la.hcap)) || (rc = p->alloc(&la.arena_c, G * la.ccap * LGs)) ||
             (rc = p->alloc(&la.gkh, G * la.gcap)) || (rc = p->alloc(&la.gki, G * la.gcap)) ||
-            (rc = p->alloc(&la.gkp, G * (la.gcap + 1))) || (rc = p->alloc(&la.ggp, G * (la.gcap + 1))) ||
-            (rc = p->alloc(&la.gout, G * la.ocap * 9 * LGs)) || (rc = p->alloc(&la.gm, G * la.ocap)))
+            (rc = p->alloc(&la.gkp, G * (la.gcap + 1))) || (rc = p->alloc(&la.ggp, G * (la.gcap + 1))))
             return rc;
         if ((rc = p->alloc(&p->d_wlist, (size_t)Wm))) return rc;
         la.occ = p->d_occ;
@@ -722,7 +720,6 @@ static int run_reach(armour_planner* p) {
         la.hcap *= RETRY_SCALE;
         la.ccap *= RETRY_SCALE;
         la.gcap *= RETRY_SCALE;
-        la.ocap *= RETRY_SCALE;
         la.pool_rows *= RETRY_SCALE;
         la.wlist = p->d_wlist;
         la.nlist = (int)retry.size();
