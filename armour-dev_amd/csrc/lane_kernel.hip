@@ -74,7 +74,9 @@ __global__ __attribute__((amdgpu_flat_work_group_size(LT, LT), amdgpu_waves_per_
     const long wg = blockIdx.x;
     LCtx x;
     x.tid = threadIdx.x;
-    x.wave = x.tid >> 6;
+    // scalar: what the round loops derive from it (group slots, prefix masks, rmask addresses) then
+    // lives in SGPRs and is not reloaded from scratch between a round's stores
+    x.wave = __builtin_amdgcn_readfirstlane(x.tid >> 6);
     x.lane = x.tid & 63;
     x.H = H;
     x.pool = a.pool + wg * a.pool_rows * LG;

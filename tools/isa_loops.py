@@ -9,11 +9,25 @@ then
     python tools/isa_loops.py /tmp/lane.s [SOURCE_FILE LAST_LINE]
 lists the loops (back edges) with the most scratch_load / scratch_store instructions, and with
 SOURCE_FILE and LAST_LINE (e.g. lane_engine.h and the line of `base += __popcll(km);`) the loops whose
-last source line of that file is LAST_LINE: the simplify round loops, with their spill sites."""
+last source line of that file is LAST_LINE: the simplify round loops, with their spill sites.
+
+    python tools/isa_loops.py --round-waits /tmp/lane.s [SOURCE_FILE]
+prints, for each loop that contains exactly one barrier and global stores after it (the compacting
+rounds of simplify() and cross_const()): the vmcnt waits between the first store after the barrier
+and the back edge (each also waits for the stores issued before it to be acknowledged), the vmcnt
+waits between the loop header and the first LDS read (they hold the next round's index reads behind
+the last round's stores; where no LDS read precedes the barrier, as in cross_const(), up to the
+round's first load from memory), and the scratch accesses in the loop. Loops are taken from the
+compiler's block comments (Loop Header / in Loop / Parent Loop), since the layout may put a loop's
+latch blocks ahead of its header. A loop is named by its kernel and by the lines of SOURCE_FILE
+(default lane_engine.h) its instructions come from. It counts waits and nothing else."""
 import collections
 import re
 import sys
 
+round_waits = sys.argv[1:2] == ["--round-waits"]
+if round_waits:
+    del sys.argv[1]
 lines = open(sys.argv[1]).read().split("\n")
 files, loc, cur, labels = {}, [None] * len(lines), None, {}
 for i, l in enumerate(lines):
@@ -38,7 +52,82 @@ def count(a, b, what):
     return sum(what in x for x in lines[a:b + 1])
 
 
-if len(sys.argv) > 3:
+def instr(j):
+    return lines[j].split(";")[0].strip()
+
+
+def vm_wait(j):
+    return instr(j).startswith("s_waitcnt") and "vmcnt" in instr(j)
+
+
+def loop_blocks():
+    """Loops by the compiler's own block comments: header label -> sorted (start, end) line ranges of
+    its blocks, nested loops' blocks included (blocks of one loop need not be contiguous)."""
+    starts = [i for i, l in enumerate(lines) if re.match(r"^\.LBB\d+_\d+:", l)]
+    funcs = [i for i, l in enumerate(lines) if ".cfi_endproc" in l or l.startswith(".Lfunc_end")]
+    own, parents = {}, {}
+    for k, i in enumerate(starts):
+        end = min([f for f in funcs if f > i][:1] + starts[k + 1:k + 2] + [len(lines)])
+        name = lines[i].split(":")[0][2:]
+        cm, j = [lines[i].split(";", 1)[1] if ";" in lines[i] else ""], i + 1
+        while j < len(lines) and lines[j].lstrip().startswith(";"):
+            cm.append(lines[j])
+            j += 1
+        cm = "\n".join(cm)
+        m = re.search(r"in Loop: Header=(BB\d+_\d+)", cm)
+        if m:
+            own.setdefault(m.group(1), []).append((i, end - 1))
+        elif "Loop Header" in cm:
+            own.setdefault(name, []).append((i, end - 1))
+            parents[name] = re.findall(r"Parent Loop (BB\d+_\d+)", cm)
+    full = {h: list(r) for h, r in own.items()}
+    for h, ps in parents.items():
+        for q in ps:
+            full.setdefault(q, []).extend(own.get(h, []))
+    return {h: sorted(r) for h, r in full.items()}, parents
+
+
+if round_waits:
+    src = sys.argv[2] if len(sys.argv) > 2 else "lane_engine.h"
+    blocks, parents = loop_blocks()
+    kernels = [(i, l.split(":")[0]) for i, l in enumerate(lines) if re.match(r"^[A-Za-z_]\w*:", l)]
+    n, tot, kern = 0, [0, 0], None
+    for h, rs in sorted(blocks.items(), key=lambda kv: kv[1][0]):
+        body = [j for a, b in rs for j in range(a, b + 1)]  # in layout order
+        bar = [k for k, j in enumerate(body) if instr(j).startswith("s_barrier")]
+        if len(bar) != 1:
+            continue
+        st = [k for k in range(bar[0], len(body)) if re.match(r"(global|flat)_store", instr(body[k]))]
+        if not st:
+            continue
+        # the round's first read: an LDS read ahead of the barrier, else the first load from memory
+        rd = [k for k in range(bar[0]) if re.match(r"ds_read", instr(body[k]))]
+        what = "LDS read"
+        if not rd:
+            rd = [k for k in range(bar[0]) if re.match(r"(global|flat)_load", instr(body[k]))]
+            what = "load (no LDS read ahead of the barrier)"
+        # the layout may put the latch blocks ahead of the header: walk the round from the header
+        hd = next(k for k, j in enumerate(body) if lines[j].startswith(".L" + h + ":"))
+        order = body[hd:] + body[:hd]
+        pos = {j: k for k, j in enumerate(order)}
+        first_st = min(pos[body[k]] for k in st)
+        after = sum(vm_wait(j) for j in order[first_st:])
+        before = sum(vm_wait(j) for j in order[:min(pos[body[k]] for k in rd)]) if rd else 0
+        ln = sorted({loc[j][1] for j in body if loc[j] and loc[j][0] == src and loc[j][1] > 0})
+        sl = sum("scratch_load" in instr(j) for j in body)
+        ss = sum("scratch_store" in instr(j) for j in body)
+        k = [nm for i, nm in kernels if i < rs[0][0]][-1:]
+        if k and k[0] != kern:
+            kern = k[0]
+            print(f"kernel {kern}")
+        n += 1
+        tot[0] += after
+        tot[1] += before
+        print(f"  loop {h} (depth {len(parents.get(h, [])) + 1}, {src}:{ln[0]}-{ln[-1]}, {len(body)} lines, {len(st)} stores to memory): "
+              f"vmcnt waits after the first store {after}, before the first {what} {before}; "
+              f"scratch loads {sl}, stores {ss}")
+    print(f"{n} round loops: vmcnt waits after the first store {tot[0]}, before the first read {tot[1]}")
+elif len(sys.argv) > 3:
     src, last = sys.argv[2], int(sys.argv[3])
     for a, b in sorted(set(loops)):
         own = [loc[j][1] for j in range(a, b + 1) if loc[j] and loc[j][0] == src]
