@@ -132,7 +132,7 @@ struct armour_planner {
     unsigned* h_pcnext = nullptr;  // pinned: the plane cache pool records the last build needed
     // state of the last batch
     int W = 0, O = 0;
-    bool reached = false, planned = false;
+    bool reached = false, planned = false, evaluated = false;  // evaluated: slot 0 holds armour_eval_constraints' point
     std::vector<void*> allocs;
 
     template <class T>
@@ -1401,7 +1401,7 @@ int armour_reach_batch(armour_planner* p, int W, const armour_world* worlds, arm
     DeviceScope device_scope(p);
     if (!p) return fail(ARMOUR_E_ARG, "null planner");
     if (p->armtd) return fail(ARMOUR_E_ARG, "an ARMTD planner takes armour_armtd_world (armour_reach_armtd_batch)");
-    p->reached = p->planned = false;
+    p->reached = p->planned = p->evaluated = false;
     auto t0 = std::chrono::steady_clock::now();
     const int rc = upload_worlds(p, W, worlds);
     return rc ? rc : reach_uploaded(p, timing, t0);
@@ -1410,7 +1410,7 @@ int armour_reach_batch(armour_planner* p, int W, const armour_world* worlds, arm
 int armour_reach_armtd_batch(armour_planner* p, int W, const armour_armtd_world* worlds, armour_timing* timing) {
     DeviceScope device_scope(p);
     if (!p) return fail(ARMOUR_E_ARG, "null planner");
-    p->reached = p->planned = false;
+    p->reached = p->planned = p->evaluated = false;
     auto t0 = std::chrono::steady_clock::now();
     const int rc = upload_armtd(p, W, worlds);
     return rc ? rc : reach_uploaded(p, timing, t0);
@@ -1420,7 +1420,7 @@ int armour_plan_armtd_batch(armour_planner* p, int W, const armour_armtd_world* 
                             armour_timing* timing) {
     DeviceScope device_scope(p);
     if (!p || !results) return fail(ARMOUR_E_ARG, "null planner / results");
-    p->reached = p->planned = false;
+    p->reached = p->planned = p->evaluated = false;
     auto t0 = std::chrono::steady_clock::now();
     const int rc = upload_armtd(p, W, worlds);
     return rc ? rc : plan_uploaded(p, results, timing, t0);
@@ -1448,7 +1448,7 @@ int armour_plan_batch(armour_planner* p, int W, const armour_world* worlds, armo
     DeviceScope device_scope(p);
     if (!p || !results) return fail(ARMOUR_E_ARG, "null planner / results");
     if (p->armtd) return fail(ARMOUR_E_ARG, "an ARMTD planner takes armour_armtd_world (armour_plan_armtd_batch)");
-    p->reached = p->planned = false;
+    p->reached = p->planned = p->evaluated = false;
     auto t0 = std::chrono::steady_clock::now();
     const int rc = upload_worlds(p, W, worlds);
     return rc ? rc : plan_uploaded(p, results, timing, t0);
@@ -1529,6 +1529,7 @@ int armour_eval_constraints(armour_planner* p, int w, const double* x, double* g
     if (jac) HIPCK(hipMemcpyAsync(jac, d.J + gidx(d, 0, w, 0) * NF, sizeof(double) * d.m * NF, hipMemcpyDeviceToHost, p->stream));
     HIPCK(hipStreamSynchronize(p->stream));
     p->planned = false;
+    p->evaluated = true;
     return 0;
 }
 
@@ -1545,9 +1546,12 @@ int armour_get_constraints(armour_planner* p, int w, double* g) {
 int armour_get_link_centers(armour_planner* p, int w, double* c) {
     DeviceScope device_scope(p);
     if (!p || !c) return fail(ARMOUR_E_ARG, "null argument");
-    if (!p->planned) return fail(ARMOUR_E_STATE, "no plan");
+    if (!p->planned && !p->evaluated) return fail(ARMOUR_E_STATE, "no plan and no evaluated point");
     if (w < 0 || w >= p->W) return fail(ARMOUR_E_ARG, "world index out of range");
-    HIPCK(hipMemcpy(c, p->d.link_c + 2 * p->d.lcs + (size_t)w * p->T * p->NJ * 3, sizeof(double) * p->T * p->NJ * 3, hipMemcpyDeviceToHost));
+    // after a plan: slot 2 (feasible_kernel's copy of the final iterate's centres); after
+    // armour_eval_constraints: slot 0, where eval_kernel_t in mode 0 wrote those of its point
+    const int slot = p->planned ? 2 : 0;
+    HIPCK(hipMemcpy(c, p->d.link_c + slot * p->d.lcs + (size_t)w * p->T * p->NJ * 3, sizeof(double) * p->T * p->NJ * 3, hipMemcpyDeviceToHost));
     return 0;
 }
 

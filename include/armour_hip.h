@@ -183,7 +183,10 @@ int armour_eval_constraints(armour_planner* p, int w, const double* x, double* g
 /* Outputs of world w of the last batch (the armour_*.out payloads, armour_main.cu:340-398) */
 int armour_get_constraints(armour_planner* p, int w, double* g);              /* m values at k_opt */
 int armour_get_link_centers(armour_planner* p, int w, double* centers);       /* [T][NJ][3] sliced at the
-                                                                               last evaluated point: k_opt after a plan */
+                                                                               last evaluated point: k_opt after a plan,
+                                                                               x after armour_eval_constraints (which
+                                                                               evaluates every world of the batch at x);
+                                                                               ARMOUR_E_STATE before either */
 int armour_get_link_generators(armour_planner* p, int w, double* gens);       /* [T][NJ][3][6] */
 int armour_get_torque_radius(armour_planner* p, int w, double* radius);       /* [T][7] */
 int armour_num_joints(const armour_planner* p);

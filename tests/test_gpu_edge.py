@@ -47,12 +47,18 @@ def test_outputs_at_solution():
     g, _, lc = R.eval(k, centers=True)
     np.testing.assert_allclose(P.link_centers(0), lc, rtol=0, atol=1e-9)
     np.testing.assert_allclose(P.constraints(0), g, rtol=0, atol=1e-9)
+    # armour_get_link_centers follows the last evaluated point: after eval_constraints(k_opt), the same centres
+    post_plan = P.link_centers(0)
+    P.eval_constraints(0, k)
+    assert np.array_equal(P.link_centers(0), post_plan)
 
 
 def test_argument_and_state_errors():
     P = A.Planner(T=10, max_obstacles=3, max_worlds=2)
     with pytest.raises(A.ArmourError, match="state|no reach|plan"):
         P.constraints(0)
+    with pytest.raises(A.ArmourError, match="no plan and no evaluated point"):
+        P.link_centers(0)                   # neither a plan nor an evaluated point yet
     worlds = [A.make_world(s, 3) for s in range(3)]
     with pytest.raises(A.ArmourError, match="num_worlds"):
         P.plan(worlds)                      # more worlds than max_worlds
@@ -63,6 +69,10 @@ def test_argument_and_state_errors():
     P.plan(worlds[:2])
     with pytest.raises(A.ArmourError, match="out of range"):
         P.torque_radius(2)
+    P.eval_constraints(0, np.zeros(7))      # the centres follow the evaluated point; the plan's outputs need a plan
+    assert P.link_centers(1).shape == (10, 7, 3)
+    with pytest.raises(A.ArmourError, match="no plan"):
+        P.constraints(0)
 
 
 def test_concurrent_planners_match_sequential():
