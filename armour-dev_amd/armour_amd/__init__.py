@@ -99,6 +99,13 @@ def lib():
         L.armour_plan_batch.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(World), ctypes.POINTER(Result),
                                         ctypes.POINTER(Timing)]
         L.armour_reach_batch.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(World), ctypes.POINTER(Timing)]
+        # (bound where present: an A/B against an older build through ARMOUR_LIB still loads; using a
+        # mixed entry on such a build raises)
+        for name, args in (("armour_plan_batch_mixed", L.armour_plan_batch.argtypes),
+                           ("armour_reach_batch_mixed", L.armour_reach_batch.argtypes),
+                           ("armour_world_num_obstacles", [ctypes.c_void_p, ctypes.c_int])):
+            if hasattr(L, name):
+                getattr(L, name).argtypes = args
         L.armour_plan.argtypes = [ctypes.c_void_p, ctypes.POINTER(World), ctypes.POINTER(PlanOutput)]
         L.armour_eval_constraints.argtypes = [ctypes.c_void_p, ctypes.c_int, _dp, _dp, _dp]
         L.armour_get_reach_program.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
@@ -125,7 +132,8 @@ ABI_SYMBOLS = ["armour_copy_bandwidth", "armour_create", "armour_create_robot", 
                "armour_num_joints", "armour_get_joint_bounds", "armour_get_reach_program", "armour_get_reach_profile",
                "armour_get_reach_dump", "armour_get_reach_occupancy", "armour_get_monomial_counts",
                "armour_create_armtd", "armour_plan_armtd_batch", "armour_reach_armtd_batch",
-               "armour_get_plane_cache_stats", "armour_plan", "armour_get_reach_span"]
+               "armour_get_plane_cache_stats", "armour_plan", "armour_get_reach_span",
+               "armour_plan_batch_mixed", "armour_reach_batch_mixed", "armour_world_num_obstacles"]
 
 
 def default_batch(T: int, device: int = 0, waves: int = 2) -> int:
@@ -155,7 +163,8 @@ def _ptr(a):
 
 
 class Planner:
-    """Batched MI355X planner. A world is (q0, qd0, qdd0, q_des, obstacles[O, 12])."""
+    """Batched MI355X planner. A world is (q0, qd0, qdd0, q_des, obstacles[O, 12]). plan / reach take
+    worlds that all carry the same O; plan_mixed / reach_mixed take any mix of counts."""
 
     def __init__(self, T=100, max_obstacles=20, max_worlds=1, device=0, max_iter=0, robot=None, _armtd=False):
         """robot: None (built-in Kinova Gen3 tables) or a robot-table dict (armour_amd.robot_tables)"""
@@ -231,6 +240,29 @@ class Planner:
     def _plan_call(self, *a):
         return lib().armour_plan_batch(*a)
 
+    def plan_mixed(self, worlds):
+        """armour_plan_batch_mixed: one reach launch and one solve for worlds that carry different
+        numbers of obstacles (zero included); results and timing as plan()"""
+        arr = self._worlds(worlds)
+        res = (Result * len(worlds))()
+        tm = Timing()
+        _check(lib().armour_plan_batch_mixed(self.h, len(worlds), arr, res, ctypes.byref(tm)))
+        return self._results(res), self._span(tm.as_dict())
+
+    def reach_mixed(self, worlds):
+        """armour_reach_batch_mixed: the reach-set half of plan_mixed (enables eval_constraints)"""
+        arr = self._worlds(worlds)
+        tm = Timing()
+        _check(lib().armour_reach_batch_mixed(self.h, len(worlds), arr, ctypes.byref(tm)))
+        return self._span(tm.as_dict())
+
+    def world_obstacles(self, w):
+        """obstacle count of world w of the last batch (armour_world_num_obstacles)"""
+        n = lib().armour_world_num_obstacles(self.h, w)
+        if n < 0:
+            _check(n)
+        return n
+
     @staticmethod
     def _results(res):
         out = []
@@ -256,8 +288,15 @@ class Planner:
     def _reach_call(self, *a):
         return lib().armour_reach_batch(*a)
 
+    def _m(self, w):
+        # world w's own constraint count (a mixed batch's worlds differ); an invalid w or a missing
+        # batch is left to the call that follows, which reports it
+        f = getattr(lib(), "armour_world_num_obstacles", None)
+        n = f(self.h, w) if f else -1
+        return self.num_constraints(n if n >= 0 else self.O)
+
     def eval_constraints(self, w, x, jac=True):
-        m = self.num_constraints(self.O)
+        m = self._m(w)
         x = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
         g = np.zeros(m)
         J = np.zeros((m, NF)) if jac else None
@@ -265,7 +304,7 @@ class Planner:
         return (g, J) if jac else g
 
     def constraints(self, w):
-        g = np.zeros(self.num_constraints(self.O))
+        g = np.zeros(self._m(w))
         _check(lib().armour_get_constraints(self.h, w, _ptr(g)))
         return g
 

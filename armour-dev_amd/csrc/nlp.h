@@ -171,6 +171,10 @@ struct NlpDev {
     unsigned char* pcok;
     unsigned long long* pcbase;  // [W][T] first pool record of each block
     unsigned* pcnext;            // pool records handed out by the current build (zeroed by jrs_kernel)
+    // Mixed batch (armour_plan_batch_mixed): the obstacle count of each world, [W]; null for a uniform
+    // batch. O, m, R and nblk above then hold the batch maximum and serve only as strides and grid
+    // sizes; a world's own extents come from shape_of<true>.
+    const int* Ow;
 };
 constexpr int EV_MAXK = 9;   // speculative trials per world (max_ls - 1)
 constexpr int PC_K = 12;               // initial pool: records per pair per block (ARMOUR_PC_K; the survey workload keeps 5.3)
@@ -181,5 +185,24 @@ constexpr double PC_MARGIN = 1e-9;     // >> the rounding of the bound and of A 
 AD int world_of(const NlpDev& d, int b) { return d.wl ? d.wl[b] : b; }
 
 AD long gidx(const NlpDev& d, int slot, int w, long r) { return ((long)slot * d.W + w) * d.m + r; }
+
+// In-world extents of world w: obstacles, constraints, solver rows (constraints + the box rows on x)
+// and row blocks. A uniform batch's are the batch's (the fields of NlpDev, no load); a mixed batch's
+// come from the world's own count, so its rows have the layout and the row-to-block partition of a
+// uniform batch of O_w obstacles (chunk is a constant), inside slabs strided by the batch maximum.
+struct Shape {
+    int O, m, R, nblk;
+};
+template <bool MX>
+AD Shape shape_of(const NlpDev& d, int w) {
+    if constexpr (MX) {
+        const int O = d.Ow[w];
+        const int m = d.nt + d.T * d.NJ * O + 4 * NF;
+        const int R = m + NF;
+        return Shape{O, m, R, (R + d.chunk - 1) / d.chunk};
+    } else {
+        return Shape{d.O, d.m, d.R, d.nblk};
+    }
+}
 
 }  // namespace armour

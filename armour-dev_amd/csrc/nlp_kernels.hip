@@ -59,8 +59,8 @@ __device__ inline void block_reduce_n(double (&v)[N], const int (&kinds)[N], dou
 }
 
 // row bounds: a collision row's are the constants bounds_kernel stores (-1e19, 0), not re-read
-__device__ inline void row_bounds(const NlpDev& d, long i, int r, double& L, double& U) {
-    const bool col = r >= d.nt && r < d.nt + d.T * d.NJ * d.O;
+__device__ inline void row_bounds(const NlpDev& d, const Shape& sh, long i, int r, double& L, double& U) {
+    const bool col = r >= d.nt && r < d.nt + d.T * d.NJ * sh.O;
     L = col ? -1e19 : d.L[i];
     U = col ? 0.0 : d.U[i];
 }
@@ -76,8 +76,8 @@ struct RowBounds {
     double Lm, Um;
     bool col;
     long lo;  // index of the row's lower-side slots
-    __device__ RowBounds(const NlpDev& d, long i, long wb, int r) {
-        col = r >= d.nt && r < d.nt + d.T * d.NJ * d.O;
+    __device__ RowBounds(const NlpDev& d, const Shape& sh, long i, long wb, int r) {
+        col = r >= d.nt && r < d.nt + d.T * d.NJ * sh.O;
         const long ib = col ? wb : i;
         Lm = d.L[ib];
         Um = d.U[ib];
@@ -90,31 +90,32 @@ __device__ inline bool has_lo(const NlpDev& d, double L) { return L > -d.opt.inf
 __device__ inline bool has_hi(const NlpDev& d, double U) { return U < d.opt.inf_bound; }
 
 // value and gradient of row r of world w from eval slot `slot` at point x; a collision row's
-// gradient is n . dc/dx from the compact form (bitwise the value eval_kernel forms densely)
-__device__ inline double row_va(const NlpDev& d, int slot, int w, int r, const double* x, double* a) {
-    const int nc = d.T * d.NJ * d.O;
+// gradient is n . dc/dx from the compact form (bitwise the value eval_kernel forms densely).
+// sh: the world's own extents (shape_of); the slabs of g, J and jn keep the batch's strides
+__device__ inline double row_va(const NlpDev& d, const Shape& sh, int slot, int w, int r, const double* x, double* a) {
+    const int nc = d.T * d.NJ * sh.O, ncs = d.T * d.NJ * d.O;
     // the value's load ahead of the branches (a box row's, from row 0, goes unused), so that it
     // travels with the row's other loads instead of after them
-    const long gi = gidx(d, slot, w, r < d.m ? r : 0);
+    const long gi = gidx(d, slot, w, r < sh.m ? r : 0);
     const double v = d.g[gi];
     if (r >= d.nt && r < d.nt + nc) {
-        const int q = r - d.nt, lt = q / d.O, l = lt / d.T, t = lt % d.T;
-        const double* n = d.jn + slot * d.njn + ((long)w * nc + q) * 3;
+        const int q = r - d.nt, lt = q / sh.O, l = lt / d.T, t = lt % d.T;
+        const double* n = d.jn + slot * d.njn + ((long)w * ncs + q) * 3;
         const double* D = d.jd + slot * d.njd + (((long)w * d.T + t) * d.NJ + l) * NF * 3;
         const double n0 = n[0], n1 = n[1], n2 = n[2];
 #pragma unroll
         for (int j = 0; j < NF; j++) a[j] = n0 * D[3 * j] + n1 * D[3 * j + 1] + n2 * D[3 * j + 2];
         return v;
     }
-    if (r < d.m) {
+    if (r < sh.m) {
         const double* J = d.J + gi * NF;
 #pragma unroll
         for (int j = 0; j < NF; j++) a[j] = J[j];
         return v;
     }
 #pragma unroll
-    for (int j = 0; j < NF; j++) a[j] = (j == r - d.m) ? 1.0 : 0.0;
-    return x[r - d.m];
+    for (int j = 0; j < NF; j++) a[j] = (j == r - sh.m) ? 1.0 : 0.0;
+    return x[r - sh.m];
 }
 
 // normalised cross product of a generator pair, zero for a parallel pair (CollisionChecking.cu:136-228)
@@ -269,10 +270,10 @@ __device__ inline __attribute__((always_inline)) R slice_term(R co, int h, int k
 // ------------------------------------------------------------------------------------------
 // constraint bounds (NLPclass.cu:87-165) of row r of world w; rows m..m+NF-1 are the box bounds on
 // x. Formed by ipm_rows_init on the solver stream (no kernel of its own on the reach stream).
-__device__ inline void bounds_of(const NlpDev& d, int w, int r, double& L, double& U) {
+__device__ inline void bounds_of(const NlpDev& d, const Shape& sh, int w, int r, double& L, double& U) {
     const RobotParams& rp = *d.rp;
     {
-        const int nt = d.nt, nc = d.T * d.NJ * d.O;
+        const int nt = d.nt, nc = d.T * d.NJ * sh.O;
         if (r < nt) {
             const int t = r / NF, j = r % NF;
             const double tr = d.ro.torque_radius[((long)w * d.T + t) * NF + j];
@@ -284,7 +285,7 @@ __device__ inline void bounds_of(const NlpDev& d, int w, int r, double& L, doubl
             const int j = (r - nt - nc) % NF;
             L = rp.state_lb[j] + rp.qe;
             U = rp.state_ub[j] - rp.qe;
-        } else if (r < d.m) {
+        } else if (r < sh.m) {
             const int j = (r - nt - nc - 2 * NF) % NF;
             L = -rp.speed_limits[j] + rp.qde;
             U = rp.speed_limits[j] - rp.qde;
@@ -456,10 +457,14 @@ __device__ inline double dkey(unsigned long long k) {
     return __builtin_bit_cast(double, (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k);
 }
 
-__global__ __launch_bounds__(EVAL_THREADS) void plane_cache_kernel(NlpDev d) {
+// MX (a mixed batch): the world's own obstacle count; its obstacles and its pcoff entries stay in
+// slabs strided by the batch's largest count (OS, NPS). A world without obstacles takes no records.
+template <bool MX>
+__device__ __attribute__((always_inline)) void plane_cache_body(const NlpDev& d) {
     const int t = blockIdx.x, w = blockIdx.y, tid = threadIdx.x;
     const long jt = (long)w * d.T + t;
-    const int NJ = d.NJ, O = d.O, NP = NJ * O;
+    const int NJ = d.NJ, O = shape_of<MX>(d, w).O, NP = NJ * O;
+    const int OS = d.O, NPS = NJ * OS;
     __shared__ double cen[MAX_J][3], rad[MAX_J][3];
     __shared__ double lgen[MAX_J][18];
     __shared__ double obs[MAX_OBS][12];
@@ -472,7 +477,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void plane_cache_kernel(NlpDev d) {
     __shared__ unsigned long long pbits[MAX_J * MAX_OBS];  // surviving planes of a pair, bit = scan position
     __shared__ unsigned total_s;
     for (int i = tid; i < NJ * 18; i += blockDim.x) lgen[i / 18][i % 18] = d.ro.link_gens[jt * NJ * 18 + i];
-    for (int i = tid; i < O * 12; i += blockDim.x) obs[i / 12][i % 12] = d.obs[(long)w * O * 12 + i];
+    for (int i = tid; i < O * 12; i += blockDim.x) obs[i / 12][i % 12] = d.obs[(long)w * OS * 12 + i];
     if (tid < NJ * 3) {
         const int l = tid / 3, e = tid % 3;
         const long b = jt * NJ + l;
@@ -603,7 +608,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void plane_cache_kernel(NlpDev d) {
             const unsigned c = cntp[q];
             cntp[q] = run;
             run += c;
-            d.pcoff[jt * NP + q] = (run - c) << 8 | c;
+            d.pcoff[jt * NPS + q] = (run - c) << 8 | c;
         }
         if (tid == 63) total_s = incl;
     }
@@ -652,6 +657,8 @@ __global__ __launch_bounds__(EVAL_THREADS) void plane_cache_kernel(NlpDev d) {
             }
     }
 }
+__global__ __launch_bounds__(EVAL_THREADS) void plane_cache_kernel(NlpDev d) { plane_cache_body<false>(d); }
+__global__ __launch_bounds__(EVAL_THREADS) void plane_cache_kernel_mx(NlpDev d) { plane_cache_body<true>(d); }
 
 // ------------------------------------------------------------------------------------------
 // g(x) and dense Jacobian, grid (T, W). mode 0: ws.x into slot 0 (start point,
@@ -673,9 +680,12 @@ constexpr int LM_S = 16, UM_S = 64;
 constexpr int UB_S = 1544;   // >= MAX_J * LM_S * 3 + NF * UM_S, and the pair tables of 280 pairs (5.5 NP + 1)
 static_assert(UB_S >= MAX_J * LM_S * 3 + NF * UM_S, "small staging buffer");
 __host__ __device__ constexpr int eval_pair_doubles(int np) { return np + (np + 1) / 2 + 4 * np; }
-template <typename R, bool ARMTD, bool CACHED, int LM, int UM, int UB>
+// MX (a mixed batch, fp64 ARMOUR only): the world's own obstacle count O decides its rows; the
+// obstacle, jn and pcoff slabs keep the batch's strides (OS)
+template <typename R, bool ARMTD, bool CACHED, int LM, int UM, int UB, bool MX = false>
 __device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mode) {
     static_assert(!CACHED || std::is_same<R, double>::value, "the plane cache is fp64");
+    static_assert(!MX || (std::is_same<R, double>::value && !ARMTD), "mixed batches: the fp64 ARMOUR planner");
     // mode 5: the trial point the speculative round chose (ipm_world_Cs: spec_k >= 0), in full,
     // into the world's trial slot (list entries, blockIdx.y -> wl)
     if ((mode == 1 || mode == 5) && d.lcount && blockIdx.y >= *d.lcount) return;
@@ -698,7 +708,7 @@ __device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mo
     const RobotParams& rp = *d.rp;
     const int tid = threadIdx.x;
     const long jt = (long)w * d.T + t;
-    const int NJ = d.NJ, O = d.O;
+    const int NJ = d.NJ, O = shape_of<MX>(d, w).O, OS = d.O;
     // everything this (world, t) reads is staged into LDS with coalesced loads first
     __shared__ double x[NF];   // the point itself stays fp64 (cost and extremum rows)
     __shared__ R lc[MAX_J][3];
@@ -733,7 +743,7 @@ __device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mo
     if (tid >= 32 && tid < 32 + NF) tcnt[tid - 32] = d.nt ? d.ro.tq_cnt[jt * NF + tid - 32] : 0;  // ARMTD: no torque PZs
     if constexpr (!CACHED) {
         for (int i = tid; i < NJ * 18; i += blockDim.x) lgen[i / 18][i % 18] = d.ro.link_gens[jt * NJ * 18 + i];
-        for (int i = tid; i < O * 12; i += blockDim.x) obs[i / 12][i % 12] = d.obs[(long)w * O * 12 + i];
+        for (int i = tid; i < O * 12; i += blockDim.x) obs[i / 12][i % 12] = d.obs[(long)w * OS * 12 + i];
     }
     __syncthreads();
     EVP_MARK
@@ -841,7 +851,7 @@ __device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mo
         const double D = rp.duration;
         const int v = tid - ((int)blockDim.x - 2 * NF - 1);
         if (v < 2 * NF) {
-            const long off2 = (long)NF * d.T + (long)d.T * d.NJ * d.O;
+            const long off2 = (long)NF * d.T + (long)d.T * d.NJ * O;
             const int kind = v / NF, i = v % NF;
             const double Tq = qd0[i] * D, TTq = qdd0[i] * D * D;
             const double ka = rp.k_range[i] * x[i];
@@ -892,6 +902,7 @@ __device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mo
     // completes them.
     const long nt = d.nt;
     bool coll = !(d.diag & 2);
+    if constexpr (MX) coll = coll && O > 0;  // a world without obstacles: no collision rows, no planes
     if constexpr (CACHED) {
         // the certified plane cache (plane_cache_kernel): the scan over the kept planes, same order,
         // same arithmetic. A point outside the cache's box cannot come from the solver (its box
@@ -914,7 +925,7 @@ __device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mo
             // strict-> first maximum, value, plane and sign exactly. The pair tables live in the
             // slicing buffer (free now).
             const int NP = NJ * O;
-            const unsigned last = d.pcoff[jt * NP + NP - 1];
+            const unsigned last = d.pcoff[jt * (NJ * OS) + NP - 1];
             const int total = (int)(last >> 8) + (int)(last & 255);
             const unsigned long long pb = d.pcbase[jt];
             const double* const rec = d.pc + 5 * pb;
@@ -1181,6 +1192,16 @@ template __global__ void eval_kernel_t<double, true, false>(NlpDev, int);
 template __global__ void eval_kernel_t<float, true, false>(NlpDev, int);
 template __global__ void eval_kernel_t<double, false, true>(NlpDev, int);
 template __global__ void eval_kernel_t<double, true, true>(NlpDev, int);
+// the mixed-batch instantiations (fp64 ARMOUR planner; full scan or plane cache, and the small form)
+template <bool CACHED>
+__global__ __launch_bounds__(EVAL_THREADS) void eval_kernel_mx(NlpDev d, int mode) {
+    eval_body<double, false, CACHED, CAP_LM, CAP_UM, UB_FULL, true>(d, mode);
+}
+__global__ __launch_bounds__(EVAL_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void eval_kernel_small_mx(NlpDev d, int mode) {
+    eval_body<double, false, true, LM_S, UM_S, UB_S, true>(d, mode);
+}
+template __global__ void eval_kernel_mx<false>(NlpDev, int);
+template __global__ void eval_kernel_mx<true>(NlpDev, int);
 
 // ------------------------------------------------------------------------------------------
 // Speculative line-search round, values only. Block (t, list entry i) evaluates the K = max_ls - 1
@@ -1193,8 +1214,10 @@ template __global__ void eval_kernel_t<double, true, true>(NlpDev, int);
 // LM, UM, UB as eval_body; the staging buffer then holds the (trial, pair) keys, K * NP <= UB
 constexpr int UB_TS = EV_MAXK * 280;   // small variant: 9 trials of up to 280 pairs (7 links x 40 obstacles)
 static_assert(UB_TS >= MAX_J * LM_S * 3 + NF * UM_S, "small trials staging buffer");
+template <bool MX>
 __device__ inline double pass_b_alpha(const NlpDev& d, int w);
-template <int LM, int UM, int UB, int KM = EV_MAXK>
+// MX (a mixed batch): the world's own O and NP; the trial slots gs and pcoff keep the batch's strides
+template <int LM, int UM, int UB, int KM = EV_MAXK, bool MX = false>
 __device__ __attribute__((always_inline)) void eval_trials_body(const NlpDev& d) {
     if (d.lcount && blockIdx.y >= *d.lcount) return;
     const int t = blockIdx.x, i = blockIdx.y, w = d.wl[i];
@@ -1205,7 +1228,7 @@ __device__ __attribute__((always_inline)) void eval_trials_body(const NlpDev& d)
     const RobotParams& rp = *d.rp;
     const int tid = threadIdx.x, K = d.K;
     const long jt = (long)w * d.T + t;
-    const int NJ = d.NJ, O = d.O, NP = NJ * O;
+    const int NJ = d.NJ, O = shape_of<MX>(d, w).O, NP = NJ * O;
     const long nt = d.nt;
     __shared__ double xk[KM][NF];
     __shared__ double ptab[KM][NF][4];  // x_j^g of trial k (the value slices' factors)
@@ -1219,7 +1242,7 @@ __device__ __attribute__((always_inline)) void eval_trials_body(const NlpDev& d)
     auto tco = reinterpret_cast<double (*)[UM]>(ubuf + MAX_J * LM * 3);
     if (tid < K * NF) {
         const int kk = tid / NF, j = tid % NF;
-        double a = d.b_in_cs ? pass_b_alpha(d, w) : S.alpha;
+        double a = d.b_in_cs ? pass_b_alpha<MX>(d, w) : S.alpha;
         for (int q = 0; q < kk; q++) a *= 0.5;
         const double xj = S.x[j] + a * S.dx[j];
         xk[kk][j] = xj;
@@ -1316,7 +1339,7 @@ __device__ __attribute__((always_inline)) void eval_trials_body(const NlpDev& d)
         const double* qdd0 = d.qdd0 + w * NF;
         const double D = rp.duration;
         if (v < 2 * NF) {
-            const long off2 = (long)NF * d.T + (long)d.T * d.NJ * d.O;
+            const long off2 = (long)NF * d.T + (long)d.T * d.NJ * O;
             const int kind = v / NF, j = v % NF;
             double mn, mx, e2, e3;
             int mnid, mxid;
@@ -1351,7 +1374,7 @@ __device__ __attribute__((always_inline)) void eval_trials_body(const NlpDev& d)
     // (Measured slower: one thread per pair scanning its records, 2x in the solver's tail: a pair's
     // records are a dependent chain of loads on one lane; and each thread reducing four consecutive
     // records before its atomics, strided loads.)
-    const unsigned last = NP > 0 ? d.pcoff[jt * NP + NP - 1] : 0u;
+    const unsigned last = NP > 0 ? d.pcoff[jt * (NJ * d.O) + NP - 1] : 0u;
     const int total = (int)(last >> 8) + (int)(last & 255);
     const unsigned long long pb = d.pcbase[jt];
     const double* const rec = d.pc + 5 * pb;
@@ -1384,12 +1407,21 @@ __device__ __attribute__((always_inline)) void eval_trials_body(const NlpDev& d)
     EVP_PRINT("TR")
 }
 __global__ __launch_bounds__(EVAL_THREADS) void eval_trials_kernel(NlpDev d) { eval_trials_body<CAP_LM, CAP_UM, UB_FULL>(d); }
+__global__ __launch_bounds__(EVAL_THREADS) void eval_trials_kernel_mx(NlpDev d) {
+    eval_trials_body<CAP_LM, CAP_UM, UB_FULL, EV_MAXK, true>(d);
+}
 // the sync-free tail's single line-search round: all max_ls trials (K = EV_MAXK + 1) of the few
 // running worlds, round 0's trial included (ipm_world_Cs_all); K * NJ * O <= UB_FULL (host check)
 __global__ __launch_bounds__(EVAL_THREADS) void eval_trials_all(NlpDev d) { eval_trials_body<CAP_LM, CAP_UM, UB_FULL, EV_MAXK + 1>(d); }
+__global__ __launch_bounds__(EVAL_THREADS) void eval_trials_all_mx(NlpDev d) {
+    eval_trials_body<CAP_LM, CAP_UM, UB_FULL, EV_MAXK + 1, true>(d);
+}
 // five waves per SIMD (91 VGPRs): six measured slower (5.5 -> 5.7 ms per solve)
 __global__ __launch_bounds__(EVAL_THREADS) __attribute__((amdgpu_waves_per_eu(5, 5))) void eval_trials_small(NlpDev d) {
     eval_trials_body<LM_S, UM_S, UB_TS>(d);
+}
+__global__ __launch_bounds__(EVAL_THREADS) __attribute__((amdgpu_waves_per_eu(5, 5))) void eval_trials_small_mx(NlpDev d) {
+    eval_trials_body<LM_S, UM_S, UB_TS, EV_MAXK, true>(d);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1428,16 +1460,19 @@ __global__ __launch_bounds__(64) void ipm_world_init(NlpDev d) {
     S.rphi = -1;
 }
 
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_init(NlpDev d) {
+template <bool MX>
+__device__ __attribute__((always_inline)) void ipm_rows_init_body(const NlpDev& d) {
     const int w = world_of(d, blockIdx.y);  // every world, or the list restarted by a restoration phase
+    const Shape sh = shape_of<MX>(d, w);
+    if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
     const WorldState& S = d.ws[w];
     const long r0 = (long)blockIdx.x * d.chunk;
-    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < d.R; r += blockDim.x) {
+    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.R; r += blockDim.x) {
         double a[NF];
-        const double v = row_va(d, S.cur, w, (int)r, S.x, a);
+        const double v = row_va(d, sh, S.cur, w, (int)r, S.x, a);
         const long i = (long)w * d.R + r;
         double L, U;
-        bounds_of(d, w, (int)r, L, U);
+        bounds_of(d, sh, w, (int)r, L, U);
         d.L[i] = L;
         d.U[i] = U;
         const bool hl = has_lo(d, L), hh = has_hi(d, U);
@@ -1456,6 +1491,8 @@ __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_init(NlpDev d) {
         }
     }
 }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_init(NlpDev d) { ipm_rows_init_body<false>(d); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_init_mx(NlpDev d) { ipm_rows_init_body<true>(d); }
 
 // pass A: residuals, errors, reduced Newton system sums
 // pass A's row accumulation (residuals, Newton system) at the current point: value v, gradient a
@@ -1572,8 +1609,11 @@ __device__ inline __attribute__((always_inline)) void row_D(const NlpDev& d, lon
     for (int j = 0; j < NF; j++) wn[j] += wv * a[j];
 }
 
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_A(NlpDev d) {
+template <bool MX>
+__device__ __attribute__((always_inline)) void ipm_rows_A_body(const NlpDev& d) {
     const int w = world_of(d, blockIdx.y);
+    const Shape sh = shape_of<MX>(d, w);
+    if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
     const WorldState& S = d.ws[w];
     if (S.status != 0) return;
     __shared__ double lds[(ROW_THREADS / 64) * NA];
@@ -1581,16 +1621,18 @@ __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_A(NlpDev d) {
     c.zero();
     const double mu = S.mu;
     const long r0 = (long)blockIdx.x * d.chunk;
-    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < d.R; r += blockDim.x) {
+    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.R; r += blockDim.x) {
         double a[NF];
-        const double v = row_va(d, S.cur, w, (int)r, S.x, a);
+        const double v = row_va(d, sh, S.cur, w, (int)r, S.x, a);
         const long i = (long)w * d.R + r;
         double L, U;
-        row_bounds(d, i, (int)r, L, U);
+        row_bounds(d, sh, i, (int)r, L, U);
         row_A(d, i, v, a, L, U, mu, c);
     }
     reduce_A(d, w, c, lds);
 }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_A(NlpDev d) { ipm_rows_A_body<false>(d); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_A_mx(NlpDev d) { ipm_rows_A_body<true>(d); }
 
 // passes D (of the previous iteration) and A (of this one) in one sweep over the rows: the trial
 // point D accepts is the point A works at, so each row's value and gradient are read once; the
@@ -1601,10 +1643,12 @@ __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_A(NlpDev d) {
 // launch 744 -> 651 us, but a small grid's latency 17.2 -> 19.9 us (the slots' LDS round trips), so
 // grids below four blocks per CU keep the register form (planner.hip ipm_loop)
 constexpr int DA_ML = 20;
-template <int ML>
+template <int ML, bool MX = false>
 __device__ __attribute__((always_inline)) void rows_DA_body(const NlpDev& d) {
     if (d.lcount && blockIdx.y >= *d.lcount) return;
     const int w = world_of(d, blockIdx.y);
+    const Shape sh = shape_of<MX>(d, w);
+    if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
     const WorldState& S = d.ws[w];
     if (S.status != 0) return;
     __shared__ double lds[(ROW_THREADS / 64) * NA];
@@ -1623,15 +1667,15 @@ __device__ __attribute__((always_inline)) void rows_DA_body(const NlpDev& d) {
     c.zero();
     const double ks = d.opt.kappa_sigma;
     const long r0 = (long)blockIdx.x * d.chunk, wb = (long)w * d.R;
-    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < d.R; r += blockDim.x) {
+    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.R; r += blockDim.x) {
         // the row's loads in one batch, then row_D's and row_A's arithmetic on registers (A reads
         // the slacks and multipliers D has just formed)
         const long i = wb + r;
-        const RowBounds B(d, i, wb, (int)r);
+        const RowBounds B(d, sh, i, wb, (int)r);
         const double slo = d.slo[B.lo], zlo = d.zlo[B.lo], dslo = d.dslo[B.lo];
         const double shi = d.shi[i], zhi = d.zhi[i], dshi = d.dshi[i];
         double a[NF];
-        const double v = row_va(d, 1 - S.cur, w, (int)r, S.xt, a);
+        const double v = row_va(d, sh, 1 - S.cur, w, (int)r, S.xt, a);
         const double L = B.L(), U = B.U();
         double wv = 0, sl = slo, zl = zlo, sh = shi, zh = zhi;
         if (has_lo(d, L)) {
@@ -1662,6 +1706,8 @@ __device__ __attribute__((always_inline)) void rows_DA_body(const NlpDev& d) {
 }
 __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_DA(NlpDev d) { rows_DA_body<0>(d); }
 __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_DA_lds(NlpDev d) { rows_DA_body<DA_ML>(d); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_DA_mx(NlpDev d) { rows_DA_body<0, true>(d); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_DA_lds_mx(NlpDev d) { rows_DA_body<DA_ML, true>(d); }
 
 __device__ bool chol_solve7(const double* M, double shift, const double* b, double* x) {
     double L[NF * NF];
@@ -1697,9 +1743,10 @@ __device__ bool chol_solve7(const double* M, double shift, const double* b, doub
 template <int N>
 __device__ inline void world_partials_at(const double* base, int nblk, int stride, const double (&init)[N],
                                          const int (&op)[N], double (&P)[N]);
+// (nblk: the world's own row blocks, Shape::nblk; its partials sit in a slab of d.nblk blocks)
 template <int N>
-__device__ inline void world_partials(const NlpDev& d, int w, const double (&init)[N], const int (&op)[N], double (&P)[N]) {
-    world_partials_at(d.partial + (long)w * d.nblk * KA, d.nblk, KA, init, op, P);
+__device__ inline void world_partials(const NlpDev& d, int w, int nblk, const double (&init)[N], const int (&op)[N], double (&P)[N]) {
+    world_partials_at(d.partial + (long)w * d.nblk * KA, nblk, KA, init, op, P);
 }
 template <int N>
 __device__ inline void world_partials_at(const double* base, int nblk, int stride, const double (&init)[N],
@@ -1731,6 +1778,7 @@ __device__ inline void world_partials_at(const double* base, int nblk, int strid
     }
 }
 
+template <bool MX>
 __device__ inline void world_A_body(const NlpDev& d, WorldState& S, int w, int nside);
 // The adaptive barrier parameter on a fixed logarithmic grid 2^(j/8) x 2^e (oracle/src/ipm.cpp
 // mu_grid, the same constants and comparisons): a rounding-level difference in the complementarity
@@ -1765,19 +1813,28 @@ __device__ inline void ws_copy(WorldState& dst, const WorldState& src) {
     uint64_t* t = reinterpret_cast<uint64_t*>(&dst);
     for (int k = threadIdx.x; k < (int)(sizeof(WorldState) / 8); k += blockDim.x) t[k] = s[k];
 }
-__global__ __launch_bounds__(64) void ipm_world_A(NlpDev d, int nside) {
+template <bool MX>
+__device__ __attribute__((always_inline)) void ipm_world_A_body(const NlpDev& d, int nside) {
     const int w = world_of(d, blockIdx.x);
     __shared__ WorldState S;
     ws_copy(S, d.ws[w]);
     __syncthreads();
     const bool act = S.status == 0;
-    world_A_body(d, S, w, nside);
+    world_A_body<MX>(d, S, w, nside);
     __syncthreads();
     if (act) ws_copy(d.ws[w], S);
 }
-// pass A's world step: convergence test, barrier update, Newton step; every lane of the wave calls it
+__global__ __launch_bounds__(64) void ipm_world_A(NlpDev d, int nside) { ipm_world_A_body<false>(d, nside); }
+__global__ __launch_bounds__(64) void ipm_world_A_mx(NlpDev d, int nside) { ipm_world_A_body<true>(d, nside); }
+// pass A's world step: convergence test, barrier update, Newton step; every lane of the wave calls it.
+// nside: the finite constraint sides of a world, a batch constant from the host (planner.hip
+// nside_count); a mixed batch's world counts its own: torque 2 per row, collision 1, extrema 2,
+// box 2 per variable
+template <bool MX>
 __device__ inline void world_A_body(const NlpDev& d, WorldState& S, int w, int nside) {
     if (S.status != 0) return;
+    const Shape sh = shape_of<MX>(d, w);
+    if constexpr (MX) nside = 2 * d.nt + d.T * d.NJ * sh.O + 2 * 4 * NF + 2 * NF;
     if (S.iter >= d.opt.max_iter) {  // oracle: loop ends without a final check
         if (threadIdx.x == 0) S.status = 2;
         return;
@@ -1786,7 +1843,7 @@ __device__ inline void world_A_body(const NlpDev& d, WorldState& S, int w, int n
     int op[NA];
 #pragma unroll
     for (int k = 0; k < NA; k++) { init[k] = k == 54 ? 1e300 : 0; op[k] = (k >= 7 && k <= 9) ? 1 : k == 54 ? 2 : 0; }
-    world_partials(d, w, init, op, P);
+    world_partials(d, w, sh.nblk, init, op, P);
     if (threadIdx.x != 0) return;
     const double* grad = d.grad + ((long)S.cur * d.W + w) * NF;
     double rd[NF], inf_d = 0;
@@ -1862,9 +1919,12 @@ __device__ inline void world_A_body(const NlpDev& d, WorldState& S, int w, int n
 // pass B: step components, fraction to boundary, line-search ingredients. Held to four waves per
 // SIMD (128 VGPRs, 2 spilled): 3.66 ms per 327-world solve against 3.95 at three. ipm_rows_DA held
 // to three spills 32 registers and slows from 6.5 to 7.9 ms, so it stays at two.
-__global__ __launch_bounds__(ROW_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void ipm_rows_B(NlpDev d) {
+template <bool MX>
+__device__ __attribute__((always_inline)) void ipm_rows_B_body(const NlpDev& d) {
     if (d.lcount && blockIdx.y >= *d.lcount) return;
     const int w = world_of(d, blockIdx.y);
+    const Shape sh = shape_of<MX>(d, w);
+    if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
     const WorldState& S = d.ws[w];
     if (S.status != 0) return;
     __shared__ double lds[(ROW_THREADS / 64) * NA];
@@ -1877,13 +1937,13 @@ __global__ __launch_bounds__(ROW_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
 #pragma unroll
     for (int j = 0; j < NF; j++) dx[j] = S.dx[j];
     const long r0 = (long)blockIdx.x * d.chunk, w0 = (long)w * d.R;
-    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < d.R; r += blockDim.x) {
+    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.R; r += blockDim.x) {
         const long i = w0 + r;  // the row's loads in one batch (RowBounds)
-        const RowBounds B(d, i, w0, (int)r);
+        const RowBounds B(d, sh, i, w0, (int)r);
         const double slo = d.slo[B.lo], zlo = d.zlo[B.lo];
         const double shi = d.shi[i], zhi = d.zhi[i];
         double a[NF];
-        const double v = row_va(d, S.cur, w, (int)r, S.x, a);
+        const double v = row_va(d, sh, S.cur, w, (int)r, S.x, a);
         double adx = 0;
 #pragma unroll
         for (int j = 0; j < NF; j++) adx += a[j] * dx[j];
@@ -1925,16 +1985,19 @@ __global__ __launch_bounds__(ROW_THREADS) __attribute__((amdgpu_waves_per_eu(4, 
     for (int k = 0; k < 19; k++) kinds[k] = k < 2 ? 2 : 0;
     block_reduce_n(v, kinds, lds, out);
 }
+__global__ __launch_bounds__(ROW_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void ipm_rows_B(NlpDev d) { ipm_rows_B_body<false>(d); }
+__global__ __launch_bounds__(ROW_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void ipm_rows_B_mx(NlpDev d) { ipm_rows_B_body<true>(d); }
 
 // pass B's world step: step sizes, line-search ingredients, the first trial point (every lane of
 // the wave calls it; ipm_world_B, or ipm_world_Cs_all in the sync-free tail)
+template <bool MX>
 __device__ inline void world_B_body(const NlpDev& d, WorldState& S, int w) {
     if (S.status != 0) return;
     double P[19], init[19];
     int op[19];
 #pragma unroll
     for (int k = 0; k < 19; k++) { init[k] = k < 2 ? 1.0 : 0.0; op[k] = k < 2 ? 2 : 0; }
-    world_partials(d, w, init, op, P);
+    world_partials(d, w, shape_of<MX>(d, w).nblk, init, op, P);
     if (threadIdx.x != 0) return;
     const double* grad = d.grad + ((long)S.cur * d.W + w) * NF;
     const double f = d.f[S.cur * d.W + w];
@@ -1957,50 +2020,58 @@ __device__ inline void world_B_body(const NlpDev& d, WorldState& S, int w) {
     S.ftype = 0;
     S.accepted_ok = 0;
 }
-__global__ __launch_bounds__(64) void ipm_world_B(NlpDev d) {
+template <bool MX>
+__device__ __attribute__((always_inline)) void ipm_world_B_body(const NlpDev& d) {
     if (d.lcount && blockIdx.x >= *d.lcount) return;
     const int w = world_of(d, blockIdx.x);
     __shared__ WorldState S;
     ws_copy(S, d.ws[w]);
     __syncthreads();
     const bool act = S.status == 0;
-    world_B_body(d, S, w);
+    world_B_body<MX>(d, S, w);
     __syncthreads();
     if (act) ws_copy(d.ws[w], S);
 }
+__global__ __launch_bounds__(64) void ipm_world_B(NlpDev d) { ipm_world_B_body<false>(d); }
+__global__ __launch_bounds__(64) void ipm_world_B_mx(NlpDev d) { ipm_world_B_body<true>(d); }
 // the first trial's step alpha = S.ap as world_B_body forms it: pass B's block partials of the
 // primal fraction to the boundary, min onto 1 in block order (world_partials' arithmetic), for the
 // tail's trial passes that run before the world step (NlpDev::b_in_cs)
+template <bool MX>
 __device__ inline double pass_b_alpha(const NlpDev& d, int w) {
     const double* in = d.partial + (long)w * d.nblk * KA;
+    const int nblk = shape_of<MX>(d, w).nblk;
     double a = 1.0;
-    for (int b0 = 0; b0 < d.nblk; b0 += 16) {
+    for (int b0 = 0; b0 < nblk; b0 += 16) {
         double x[16];
 #pragma unroll
-        for (int u = 0; u < 16; u++) x[u] = in[(long)min(b0 + u, d.nblk - 1) * KA];
+        for (int u = 0; u < 16; u++) x[u] = in[(long)min(b0 + u, nblk - 1) * KA];
 #pragma unroll
         for (int u = 0; u < 16; u++)
-            if (b0 + u < d.nblk) a = fmin(a, x[u]);
+            if (b0 + u < nblk) a = fmin(a, x[u]);
     }
     return a;
 }
 
 // pass C: barrier objective and constraint violation at the trial point
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_C(NlpDev d) {
+template <bool MX>
+__device__ __attribute__((always_inline)) void ipm_rows_C_body(const NlpDev& d) {
     if (d.lcount && blockIdx.y >= *d.lcount) return;
     const int w = world_of(d, blockIdx.y);
+    const Shape sh = shape_of<MX>(d, w);
+    if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
     const WorldState& S = d.ws[w];
     if (!(S.status == 0 && S.searching)) return;
     __shared__ double lds[(ROW_THREADS / 64) * NA];
     double logt = 0, rpt = 0;
     const double alpha = S.alpha;
     const long r0 = (long)blockIdx.x * d.chunk, wb = (long)w * d.R;
-    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < d.R; r += blockDim.x) {
+    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.R; r += blockDim.x) {
         const long i = wb + r;  // the row's loads in one batch (RowBounds)
-        const RowBounds B(d, i, wb, (int)r);
+        const RowBounds B(d, sh, i, wb, (int)r);
         const double slo = d.slo[B.lo], dslo = d.dslo[B.lo], shi = d.shi[i], dshi = d.dshi[i];
         double a[NF];
-        const double v = row_va(d, 1 - S.cur, w, (int)r, S.xt, a);
+        const double v = row_va(d, sh, 1 - S.cur, w, (int)r, S.xt, a);
         const double L = B.L(), U = B.U();
         if (has_lo(d, L)) { const double st = slo + alpha * dslo; logt += log(st); rpt += fabs((v - L) - st); }
         if (has_hi(d, U)) { const double st = shi + alpha * dshi; logt += log(st); rpt += fabs((U - v) - st); }
@@ -2010,6 +2081,8 @@ __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_C(NlpDev d) {
     const int kinds[2] = {0, 0};
     block_reduce_n(v, kinds, lds, out);
 }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_C(NlpDev d) { ipm_rows_C_body<false>(d); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_C_mx(NlpDev d) { ipm_rows_C_body<true>(d); }
 
 __device__ inline void accept_trial(const NlpDev& d, WorldState& S, double logt, double rpt, double ft, bool filt, int w);
 // the filter test of a trial (theta_t, phi_t) on a whole wave, one filter entry per lane
@@ -2019,12 +2092,13 @@ __device__ inline bool filter_pass(const WorldState& S, double thetat, double ph
     const bool fail = q < S.nfilt && !(thetat < S.filt_theta[q] || phit < S.filt_phi[q]);
     return __ballot(fail) == 0;
 }
+template <bool MX>
 __device__ inline void world_C_body(const NlpDev& d, WorldState& S, int w) {
     if (!(S.status == 0 && S.searching)) return;
     double P[2];
     const double init[2] = {0.0, 0.0};
     const int op[2] = {0, 0};
-    world_partials(d, w, init, op, P);
+    world_partials(d, w, shape_of<MX>(d, w).nblk, init, op, P);
     const double ft = d.f[(1 - S.cur) * d.W + w];
     const bool filt = filter_pass(S, P[1], ft - S.mu * P[0]);
     if (threadIdx.x != 0) return;
@@ -2083,7 +2157,8 @@ __device__ inline void accept_trial(const NlpDev& d, WorldState& S, double logt,
 // still running (round 0) and still searching are appended to the next lists (their order only
 // decides which block serves which world), and the last block to finish publishes both counts to
 // the mapped host flags and resets the counters for the next launch.
-__global__ __launch_bounds__(64) void ipm_world_C(NlpDev d) {
+template <bool MX>
+__device__ __attribute__((always_inline)) void ipm_world_C_body(const NlpDev& d) {
     const bool valid = !d.lcount || blockIdx.x < *d.lcount;
     const int w = valid ? world_of(d, blockIdx.x) : 0;
     __shared__ WorldState S;
@@ -2091,7 +2166,7 @@ __global__ __launch_bounds__(64) void ipm_world_C(NlpDev d) {
         ws_copy(S, d.ws[w]);
         __syncthreads();
         const bool act = S.status == 0;
-        world_C_body(d, S, w);
+        world_C_body<MX>(d, S, w);
         __syncthreads();
         if (act) ws_copy(d.ws[w], S);
     }
@@ -2116,27 +2191,32 @@ __global__ __launch_bounds__(64) void ipm_world_C(NlpDev d) {
         d.cnt[2] = 0;
     }
 }
+__global__ __launch_bounds__(64) void ipm_world_C(NlpDev d) { ipm_world_C_body<false>(d); }
+__global__ __launch_bounds__(64) void ipm_world_C_mx(NlpDev d) { ipm_world_C_body<true>(d); }
 
 // Speculative line-search round (the tail: few worlds still searching after round 0). Pass C of
 // every remaining trial k = 0 .. K-1 (alpha halved k times) of list entry i, blockIdx.y = i * K + k,
 // from the trial's own slot; the arithmetic of ipm_rows_C at that trial.
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_Cs(NlpDev d) {
+template <bool MX>
+__device__ __attribute__((always_inline)) void ipm_rows_Cs_body(const NlpDev& d) {
     const int i = blockIdx.y / d.K, k = blockIdx.y % d.K;
     if (d.lcount && (unsigned)i >= *d.lcount) return;
     const int w = d.wl[i];
+    const Shape sh = shape_of<MX>(d, w);
+    if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
     const WorldState& S = d.ws[w];
     if (!(S.status == 0 && (d.b_in_cs || S.searching))) return;
     __shared__ double lds[(ROW_THREADS / 64) * NA];
-    double alpha = d.b_in_cs ? pass_b_alpha(d, w) : S.alpha;
+    double alpha = d.b_in_cs ? pass_b_alpha<MX>(d, w) : S.alpha;
     for (int q = 0; q < k; q++) alpha *= 0.5;
     const double* G = d.gs + (long)blockIdx.y * d.m;
     double logt = 0, rpt = 0;
     const long r0 = (long)blockIdx.x * d.chunk, wb = (long)w * d.R;
-    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < d.R; r += blockDim.x) {
+    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.R; r += blockDim.x) {
         const long ii = wb + r;  // the row's loads in one batch (RowBounds)
-        const RowBounds B(d, ii, wb, (int)r);
+        const RowBounds B(d, sh, ii, wb, (int)r);
         const double slo = d.slo[B.lo], dslo = d.dslo[B.lo], shi = d.shi[ii], dshi = d.dshi[ii];
-        const double v = r < d.m ? G[r] : S.x[r - d.m] + alpha * S.dx[r - d.m];  // box row: the trial's x
+        const double v = r < sh.m ? G[r] : S.x[r - sh.m] + alpha * S.dx[r - sh.m];  // box row: the trial's x
         const double L = B.L(), U = B.U();
         if (has_lo(d, L)) { const double st = slo + alpha * dslo; logt += log(st); rpt += fabs((v - L) - st); }
         if (has_hi(d, U)) { const double st = shi + alpha * dshi; logt += log(st); rpt += fabs((U - v) - st); }
@@ -2146,23 +2226,29 @@ __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_Cs(NlpDev d) {
     const int kinds[2] = {0, 0};
     block_reduce_n(v, kinds, lds, out);
 }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_Cs(NlpDev d) { ipm_rows_Cs_body<false>(d); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_Cs_mx(NlpDev d) { ipm_rows_Cs_body<true>(d); }
 
 // the trials of a speculative round tested in order, exactly as the sequential rounds would
 // (ipm_world_C): the first acceptable one ends the search, or the last (forced) one
 // list entry blockIdx.x (one wave): every trial's two partial sums at once (lane 2 k + q, block
 // partials summed in order as world_partials_at), then the acceptance tests in trial order on lane 0
+template <bool MX>
 __device__ inline void world_Cs_body(const NlpDev& d, WorldState& S, int i);
-__global__ __launch_bounds__(64) void ipm_world_Cs(NlpDev d) {
+template <bool MX>
+__device__ __attribute__((always_inline)) void ipm_world_Cs_body(const NlpDev& d) {
     if (d.lcount && blockIdx.x >= *d.lcount) return;
     const int w = d.wl[blockIdx.x];
     __shared__ WorldState S;
     ws_copy(S, d.ws[w]);
     __syncthreads();
     const bool act = S.status == 0;
-    world_Cs_body(d, S, blockIdx.x);
+    world_Cs_body<MX>(d, S, blockIdx.x);
     __syncthreads();
     if (act) ws_copy(d.ws[w], S);
 }
+__global__ __launch_bounds__(64) void ipm_world_Cs(NlpDev d) { ipm_world_Cs_body<false>(d); }
+__global__ __launch_bounds__(64) void ipm_world_Cs_mx(NlpDev d) { ipm_world_Cs_body<true>(d); }
 // The tail's whole line search in one round (planner.hip run_solver, sync-free tail): every trial
 // k = 0 .. max_ls - 1 of every running world was evaluated values-only (eval_trials_kernel with
 // K = max_ls) and summed (ipm_rows_Cs), so this is round 0 and every later round of
@@ -2170,7 +2256,8 @@ __global__ __launch_bounds__(64) void ipm_world_Cs(NlpDev d) {
 // then round 0's bookkeeping — the worlds still running appended to the next iteration's list, the
 // last block publishing the count as ipm_world_C does for ls0. The chosen trial is then evaluated in
 // full (eval_kernel_t mode 5).
-__global__ __launch_bounds__(64) void ipm_world_Cs_all(NlpDev d) {
+template <bool MX>
+__device__ __attribute__((always_inline)) void ipm_world_Cs_all_body(const NlpDev& d) {
     const bool valid = !d.lcount || blockIdx.x < *d.lcount;
     const int w = valid ? d.wl[blockIdx.x] : 0;
     __shared__ WorldState S;
@@ -2178,9 +2265,9 @@ __global__ __launch_bounds__(64) void ipm_world_Cs_all(NlpDev d) {
         ws_copy(S, d.ws[w]);
         __syncthreads();
         const bool act = S.status == 0;
-        if (d.b_in_cs) world_B_body(d, S, w);
+        if (d.b_in_cs) world_B_body<MX>(d, S, w);
         __syncthreads();  // lane 0's WorldState stores before every lane's reads (filter_pass)
-        world_Cs_body(d, S, blockIdx.x);
+        world_Cs_body<MX>(d, S, blockIdx.x);
         __syncthreads();
         if (act) ws_copy(d.ws[w], S);
     }
@@ -2204,12 +2291,15 @@ __global__ __launch_bounds__(64) void ipm_world_Cs_all(NlpDev d) {
         d.cnt[2] = 0;
     }
 }
+__global__ __launch_bounds__(64) void ipm_world_Cs_all(NlpDev d) { ipm_world_Cs_all_body<false>(d); }
+__global__ __launch_bounds__(64) void ipm_world_Cs_all_mx(NlpDev d) { ipm_world_Cs_all_body<true>(d); }
+template <bool MX>
 __device__ inline void world_Cs_body(const NlpDev& d, WorldState& S, int i) {
     const int lane = threadIdx.x & 63;
     double s = 0.0;
     if (lane < 2 * d.K) {
         const double* in = d.partial_s + ((long)i * d.K + (lane >> 1)) * d.nblk * KA + (lane & 1);
-        const int nb = d.nblk;
+        const int nb = shape_of<MX>(d, d.wl[i]).nblk;
         for (int b0 = 0; b0 < nb; b0 += 16) {
             double x[16];
 #pragma unroll
@@ -2246,8 +2336,11 @@ __device__ inline void world_Cs_body(const NlpDev& d, WorldState& S, int i) {
 }
 
 // pass D: accept the trial point — slacks, multipliers, BFGS ingredients
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_D(NlpDev d) {
+template <bool MX>
+__device__ __attribute__((always_inline)) void ipm_rows_D_body(const NlpDev& d) {
     const int w = world_of(d, blockIdx.y);
+    const Shape sh = shape_of<MX>(d, w);
+    if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
     const WorldState& S = d.ws[w];
     if (S.status != 0) return;
     __shared__ double lds[(ROW_THREADS / 64) * NA];
@@ -2256,30 +2349,33 @@ __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_D(NlpDev d) {
 #pragma unroll
     for (int j = 0; j < NF; j++) wn[j] = 0;
     const long r0 = (long)blockIdx.x * d.chunk;
-    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < d.R; r += blockDim.x) {
+    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.R; r += blockDim.x) {
         double a[NF];
-        row_va(d, 1 - S.cur, w, (int)r, S.xt, a);
+        row_va(d, sh, 1 - S.cur, w, (int)r, S.xt, a);
         const long i = (long)w * d.R + r;
         double L, U;
-        row_bounds(d, i, (int)r, L, U);
+        row_bounds(d, sh, i, (int)r, L, U);
         row_D(d, i, a, L, U, mu, ad, alpha, wn);
     }
     double* out = d.partial2 + ((long)w * d.nblk + blockIdx.x) * KA2;
     const int kinds[NF] = {};
     block_reduce_n(wn, kinds, lds, out);
 }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_D(NlpDev d) { ipm_rows_D_body<false>(d); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_D_mx(NlpDev d) { ipm_rows_D_body<true>(d); }
 
 // pass D's world step: BFGS update, accept the trial point; every lane of the wave calls it. The
 // vectors and scalars are formed by every lane alike (the same arithmetic in the same order, so the
 // same values on every lane, at the cost of one lane), and lane l < 49 updates H's element l: the
 // update's 98 divisions run side by side instead of one after another on lane 0. Within the one
 // wave, every lane's reads of H precede the first write in program order.
+template <bool MX>
 __device__ inline void world_D_body(const NlpDev& d, WorldState& S, int w) {
     if (S.status != 0) return;
     double wn[NF];
     const double init[NF] = {};
     const int op[NF] = {};
-    world_partials_at(d.partial2 + (long)w * d.nblk * KA2, d.nblk, KA2, init, op, wn);
+    world_partials_at(d.partial2 + (long)w * d.nblk * KA2, shape_of<MX>(d, w).nblk, KA2, init, op, wn);
     const int lane = threadIdx.x;
     const double* grad = d.grad + ((long)S.cur * d.W + w) * NF;
     const double* gradt = d.grad + ((long)(1 - S.cur) * d.W + w) * NF;
@@ -2343,30 +2439,36 @@ __device__ inline void world_D_body(const NlpDev& d, WorldState& S, int w) {
     S.iter++;
     if (S.nfail >= 3) S.status = 3;
 }
-__global__ __launch_bounds__(64) void ipm_world_D(NlpDev d) {
+template <bool MX>
+__device__ __attribute__((always_inline)) void ipm_world_D_body(const NlpDev& d) {
     const int w = world_of(d, blockIdx.x);
     __shared__ WorldState S;
     ws_copy(S, d.ws[w]);
     __syncthreads();
     const bool act = S.status == 0;
-    world_D_body(d, S, w);
+    world_D_body<MX>(d, S, w);
     __syncthreads();
     if (act) ws_copy(d.ws[w], S);
 }
+__global__ __launch_bounds__(64) void ipm_world_D(NlpDev d) { ipm_world_D_body<false>(d); }
+__global__ __launch_bounds__(64) void ipm_world_D_mx(NlpDev d) { ipm_world_D_body<true>(d); }
 // the fused passes' world step: D's (of the previous iteration), then A's, one wave
-__global__ __launch_bounds__(64) void ipm_world_DA(NlpDev d, int nside) {
+template <bool MX>
+__device__ __attribute__((always_inline)) void ipm_world_DA_body(const NlpDev& d, int nside) {
     if (d.lcount && blockIdx.x >= *d.lcount) return;
     const int w = world_of(d, blockIdx.x);
     __shared__ WorldState S;
     ws_copy(S, d.ws[w]);
     __syncthreads();
     const bool act = S.status == 0;
-    world_D_body(d, S, w);
+    world_D_body<MX>(d, S, w);
     __syncthreads();  // lane 0's WorldState stores before every lane's reads in world_A_body
-    world_A_body(d, S, w, nside);
+    world_A_body<MX>(d, S, w, nside);
     __syncthreads();
     if (act) ws_copy(d.ws[w], S);
 }
+__global__ __launch_bounds__(64) void ipm_world_DA(NlpDev d, int nside) { ipm_world_DA_body<false>(d, nside); }
+__global__ __launch_bounds__(64) void ipm_world_DA_mx(NlpDev d, int nside) { ipm_world_DA_body<true>(d, nside); }
 
 // ------------------------------------------------------------------------------------------
 // Restoration phase (oracle/src/ipm.cpp restoration). A world whose line search
@@ -2402,9 +2504,12 @@ __device__ inline double resto_barrier(const NlpDev& d, const double* x) {
     return d.opt.resto_mu * b;
 }
 
-__global__ __launch_bounds__(ROW_THREADS) void resto_rows_G(NlpDev d) {
+template <bool MX>
+__device__ __attribute__((always_inline)) void resto_rows_G_body(const NlpDev& d) {
     if (d.lcount && blockIdx.y >= *d.lcount) return;
     const int w = world_of(d, blockIdx.y);
+    const Shape sh = shape_of<MX>(d, w);
+    if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
     const WorldState& S = d.ws[w];
     if (S.status != WS_RESTO) return;
     __shared__ double lds[(ROW_THREADS / 64) * NRG];
@@ -2415,11 +2520,11 @@ __global__ __launch_bounds__(ROW_THREADS) void resto_rows_G(NlpDev d) {
 #pragma unroll
     for (int j = 0; j < NF; j++) b[j] = 0;
     const long r0 = (long)blockIdx.x * d.chunk, wb = (long)w * d.R;
-    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < d.m; r += blockDim.x) {
+    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.m; r += blockDim.x) {
         const long i = wb + r;
-        const RowBounds B(d, i, wb, (int)r);
+        const RowBounds B(d, sh, i, wb, (int)r);
         double a[NF];
-        const double v = row_va(d, slot, w, (int)r, S.x, a);
+        const double v = row_va(d, sh, slot, w, (int)r, S.x, a);
         double e, sg, e0;
         resto_row(d, v, B.L(), B.U(), e, sg, e0);
         e0m = fmax(e0m, e0);
@@ -2447,6 +2552,8 @@ __global__ __launch_bounds__(ROW_THREADS) void resto_rows_G(NlpDev d) {
     for (int k = 0; k < NRG; k++) kinds[k] = k == 36 ? 1 : 0;
     block_reduce_n(v, kinds, lds, d.partial + ((long)w * d.nblk + blockIdx.x) * KA);
 }
+__global__ __launch_bounds__(ROW_THREADS) void resto_rows_G(NlpDev d) { resto_rows_G_body<false>(d); }
+__global__ __launch_bounds__(ROW_THREADS) void resto_rows_G_mx(NlpDev d) { resto_rows_G_body<true>(d); }
 
 // a restoration phase that reached a point within every bound hands the world back to the
 // interior point: a fresh filter and BFGS matrix at the current mu (slacks: ipm_rows_init)
@@ -2530,7 +2637,8 @@ __device__ inline void resto_count(const NlpDev& d, bool mine, int flag) {
     }
 }
 
-__global__ __launch_bounds__(64) void resto_world_G(NlpDev d) {
+template <bool MX>
+__device__ __attribute__((always_inline)) void resto_world_G_body(const NlpDev& d) {
     if (d.lcount && blockIdx.x >= *d.lcount) return;  // (one-round search: no count published)
     const int w = world_of(d, blockIdx.x);
     __shared__ WorldState S;
@@ -2542,7 +2650,7 @@ __global__ __launch_bounds__(64) void resto_world_G(NlpDev d) {
         int op[NRG];
 #pragma unroll
         for (int k = 0; k < NRG; k++) { init[k] = 0; op[k] = k == 36 ? 1 : 0; }
-        world_partials(d, w, init, op, P);
+        world_partials(d, w, shape_of<MX>(d, w).nblk, init, op, P);
         if (threadIdx.x == 0) {
             if (S.rpend) {  // the step chosen last iteration, evaluated in the trial slot
                 for (int j = 0; j < NF; j++) S.x[j] = S.xt[j];
@@ -2557,19 +2665,24 @@ __global__ __launch_bounds__(64) void resto_world_G(NlpDev d) {
     if (act) ws_copy(d.ws[w], S);
     if (threadIdx.x == 0 && d.rflag >= 0) resto_count(d, S.status == WS_RESTO, d.rflag);
 }
+__global__ __launch_bounds__(64) void resto_world_G(NlpDev d) { resto_world_G_body<false>(d); }
+__global__ __launch_bounds__(64) void resto_world_G_mx(NlpDev d) { resto_world_G_body<true>(d); }
 
 // sum e^2 at the trial point (the trial slot's full evaluation, mode 1)
-__global__ __launch_bounds__(ROW_THREADS) void resto_rows_V(NlpDev d) {
+template <bool MX>
+__device__ __attribute__((always_inline)) void resto_rows_V_body(const NlpDev& d) {
     const int w = world_of(d, blockIdx.y);
+    const Shape sh = shape_of<MX>(d, w);
+    if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
     const WorldState& S = d.ws[w];
     if (!(S.status == WS_RESTO && S.searching)) return;
     __shared__ double lds[(ROW_THREADS / 64) * NRG];
     const int slot = 1 - S.cur;
     double V = 0;
     const long r0 = (long)blockIdx.x * d.chunk, wb = (long)w * d.R;
-    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < d.m; r += blockDim.x) {
+    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.m; r += blockDim.x) {
         const long i = wb + r;
-        const RowBounds B(d, i, wb, (int)r);
+        const RowBounds B(d, sh, i, wb, (int)r);
         const double v = d.g[gidx(d, slot, w, r)];
         double e, sg, e0;
         resto_row(d, v, B.L(), B.U(), e, sg, e0);
@@ -2579,10 +2692,13 @@ __global__ __launch_bounds__(ROW_THREADS) void resto_rows_V(NlpDev d) {
     const int kinds[1] = {0};
     block_reduce_n(vv, kinds, lds, d.partial + ((long)w * d.nblk + blockIdx.x) * KA);
 }
+__global__ __launch_bounds__(ROW_THREADS) void resto_rows_V(NlpDev d) { resto_rows_V_body<false>(d); }
+__global__ __launch_bounds__(ROW_THREADS) void resto_rows_V_mx(NlpDev d) { resto_rows_V_body<true>(d); }
 
 // the Armijo test of the round's trial; a rejected trial halves alpha (max_ls trials, then the
 // phase fails: local infeasibility at the current point)
-__global__ __launch_bounds__(64) void resto_world_V(NlpDev d) {
+template <bool MX>
+__device__ __attribute__((always_inline)) void resto_world_V_body(const NlpDev& d) {
     const int w = world_of(d, blockIdx.x);
     __shared__ WorldState S;
     ws_copy(S, d.ws[w]);
@@ -2592,7 +2708,7 @@ __global__ __launch_bounds__(64) void resto_world_V(NlpDev d) {
         double P[1];
         const double init[1] = {0.0};
         const int op[1] = {0};
-        world_partials(d, w, init, op, P);
+        world_partials(d, w, shape_of<MX>(d, w).nblk, init, op, P);
         if (threadIdx.x == 0) {
             S.nevals++;
             const double phit = 0.5 * P[0] + resto_barrier(d, S.xt);
@@ -2612,25 +2728,30 @@ __global__ __launch_bounds__(64) void resto_world_V(NlpDev d) {
     if (act) ws_copy(d.ws[w], S);
     if (threadIdx.x == 0) resto_count(d, S.status == WS_RESTO && S.searching, 1);
 }
+__global__ __launch_bounds__(64) void resto_world_V(NlpDev d) { resto_world_V_body<false>(d); }
+__global__ __launch_bounds__(64) void resto_world_V_mx(NlpDev d) { resto_world_V_body<true>(d); }
 
 // The phase's Armijo search in one round (planner.hip run_resto, when the speculative machinery is
 // there): the values of all max_ls trials (eval_trials_all, d.resto) summed per trial
 // (resto_rows_Vs, list entry i and trial k at blockIdx.y = i K + k, the rows and partial sums of
 // resto_rows_V), the tests in trial order (resto_world_Vs), then the chosen trial in full (eval
 // mode 5, d.resto). The decisions and the chosen point are those of the sequential rounds.
-__global__ __launch_bounds__(ROW_THREADS) void resto_rows_Vs(NlpDev d) {
+template <bool MX>
+__device__ __attribute__((always_inline)) void resto_rows_Vs_body(const NlpDev& d) {
     const int i = blockIdx.y / d.K;
     if (d.lcount && (unsigned)i >= *d.lcount) return;
     const int w = d.wl[i];
+    const Shape sh = shape_of<MX>(d, w);
+    if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
     const WorldState& S = d.ws[w];
     if (!(S.status == WS_RESTO && S.searching)) return;
     __shared__ double lds[(ROW_THREADS / 64) * NRG];
     const double* G = d.gs + (long)blockIdx.y * d.m;
     double V = 0;
     const long r0 = (long)blockIdx.x * d.chunk, wb = (long)w * d.R;
-    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < d.m; r += blockDim.x) {
+    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.m; r += blockDim.x) {
         const long ii = wb + r;
-        const RowBounds B(d, ii, wb, (int)r);
+        const RowBounds B(d, sh, ii, wb, (int)r);
         double e, sg, e0;
         resto_row(d, G[r], B.L(), B.U(), e, sg, e0);
         V += e * e;
@@ -2639,10 +2760,13 @@ __global__ __launch_bounds__(ROW_THREADS) void resto_rows_Vs(NlpDev d) {
     const int kinds[1] = {0};
     block_reduce_n(vv, kinds, lds, d.partial_s + ((long)blockIdx.y * d.nblk + blockIdx.x) * KA);
 }
+__global__ __launch_bounds__(ROW_THREADS) void resto_rows_Vs(NlpDev d) { resto_rows_Vs_body<false>(d); }
+__global__ __launch_bounds__(ROW_THREADS) void resto_rows_Vs_mx(NlpDev d) { resto_rows_Vs_body<true>(d); }
 // ... and the list compaction of the one-round iterations: the worlds still in the phase go to the
 // next iteration's list (wl_run), whose length the last block stores for the next launches (lrun_out,
 // device) and for the host (nrun_flag, mapped; read one iteration late)
-__global__ __launch_bounds__(64) void resto_world_Vs(NlpDev d) {
+template <bool MX>
+__device__ __attribute__((always_inline)) void resto_world_Vs_body(const NlpDev& d) {
     const bool valid = !d.lcount || blockIdx.x < *d.lcount;
     const int i = blockIdx.x, w = valid ? d.wl[i] : 0;
     __shared__ WorldState S;
@@ -2658,13 +2782,14 @@ __global__ __launch_bounds__(64) void resto_world_Vs(NlpDev d) {
         double v = 0.0;
         if (lane < d.K) {
             const double* in = d.partial_s + ((long)i * d.K + lane) * d.nblk * KA;
-            for (int b0 = 0; b0 < d.nblk; b0 += 16) {
+            const int nblk = shape_of<MX>(d, w).nblk;
+            for (int b0 = 0; b0 < nblk; b0 += 16) {
                 double xb[16];
 #pragma unroll
-                for (int u = 0; u < 16; u++) xb[u] = in[(long)min(b0 + u, d.nblk - 1) * KA];
+                for (int u = 0; u < 16; u++) xb[u] = in[(long)min(b0 + u, nblk - 1) * KA];
 #pragma unroll
                 for (int u = 0; u < 16; u++)
-                    if (b0 + u < d.nblk) v = v + xb[u];
+                    if (b0 + u < nblk) v = v + xb[u];
             }
         }
         const uint64_t u = __builtin_bit_cast(uint64_t, v);
@@ -2709,6 +2834,8 @@ __global__ __launch_bounds__(64) void resto_world_Vs(NlpDev d) {
         d.cnt[2] = 0;
     }
 }
+__global__ __launch_bounds__(64) void resto_world_Vs(NlpDev d) { resto_world_Vs_body<false>(d); }
+__global__ __launch_bounds__(64) void resto_world_Vs_mx(NlpDev d) { resto_world_Vs_body<true>(d); }
 
 // the phase list of the next phase iteration: the worlds appended since the last publish (failed
 // line searches, and the worlds the last phase iteration kept) moved from the append list `src` to
@@ -2746,17 +2873,19 @@ __global__ __launch_bounds__(1024) void ipm_collect(NlpDev d, const int* in, int
 }
 
 // finalize_solution's feasibility re-check (NLPclass.cu:449-538): one block per world
-__global__ void feasible_kernel(NlpDev d, int* feasible) {
+template <bool MX>
+__device__ __attribute__((always_inline)) void feasible_body(const NlpDev& d, int* feasible) {
     const int w = blockIdx.x;
     const WorldState& S = d.ws[w];
     const RobotParams& rp = *d.rp;
     __shared__ int bad;
     if (threadIdx.x == 0) bad = 0;
     __syncthreads();
-    const int nt = d.nt, nc = d.T * d.NJ * d.O;
+    const Shape sh = shape_of<MX>(d, w);
+    const int nt = d.nt, nc = d.T * d.NJ * sh.O;
     // ARMTD's re-check covers the collision rows of links 0 .. NF-2 only (ACMP/NLPclass.cu:375)
-    const int nc_checked = d.armtd ? d.T * (NF - 1) * d.O : nc;
-    for (int r = threadIdx.x; r < d.m; r += blockDim.x) {
+    const int nc_checked = d.armtd ? d.T * (NF - 1) * sh.O : nc;
+    for (int r = threadIdx.x; r < sh.m; r += blockDim.x) {
         const double v = d.g[gidx(d, S.cur, w, r)];
         const long i = (long)w * d.R + r;
         bool b;
@@ -2772,5 +2901,7 @@ __global__ void feasible_kernel(NlpDev d, int* feasible) {
     __syncthreads();
     if (threadIdx.x == 0) feasible[w] = (bad || S.status == 4) ? 0 : 1;
 }
+__global__ void feasible_kernel(NlpDev d, int* feasible) { feasible_body<false>(d, feasible); }
+__global__ void feasible_kernel_mx(NlpDev d, int* feasible) { feasible_body<true>(d, feasible); }
 
 }  // namespace armour

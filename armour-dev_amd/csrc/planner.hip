@@ -131,7 +131,9 @@ struct armour_planner {
     int* h_feas = nullptr;
     unsigned* h_pcnext = nullptr;  // pinned: the plane cache pool records the last build needed
     // state of the last batch
-    int W = 0, O = 0;
+    int W = 0, O = 0;          // (a mixed batch: O is its largest count)
+    std::vector<int> Ow;       // obstacle count of each world of the last batch
+    int* d_Ow = nullptr;       // [max_worlds] device copy of a mixed batch's counts (NlpDev::Ow)
     bool reached = false, planned = false, evaluated = false;  // evaluated: slot 0 holds armour_eval_constraints' point
     std::vector<void*> allocs;
 
@@ -549,6 +551,8 @@ static int planner_init(armour_planner* p, const armour_config* cfg, const armou
     d.qdd0 = p->qdd0;
     d.qdes = p->qdes;
     d.obs = p->obs;
+    d.Ow = nullptr;
+    if ((rc = p->alloc(&p->d_Ow, (size_t)Wm))) return rc;
     return 0;
 }
 
@@ -577,9 +581,60 @@ static int upload_worlds(armour_planner* p, int W, const armour_world* worlds) {
     HIPCK(hipStreamSynchronize(p->stream));  // host staging vectors die at return
     p->W = W;
     p->O = O;
+    p->Ow.assign(W, O);
     NlpDev& d = p->d;
     d.W = W;
     d.O = O;
+    d.Ow = nullptr;
+    d.pcready = 0;
+    d.m = d.nt + p->T * p->NJ * O + NF * 4;
+    d.R = d.m + NF;
+    d.chunk = row_chunk();
+    d.nblk = (d.R + d.chunk - 1) / d.chunk;
+    return 0;
+}
+
+// A mixed batch: every world with its own obstacle count, 0 .. max_obstacles. The obstacle array is
+// padded to the batch's largest count (the stride of every per-world slab, as O is for a uniform
+// batch) and the counts go to the device (NlpDev::Ow); the solver then runs the _mx kernels.
+static int upload_worlds_mixed(armour_planner* p, int W, const armour_world* worlds) {
+    if (p->armtd) return fail(ARMOUR_E_ARG, "mixed batches are not available on an ARMTD planner");
+    if (p->eval_f32) return fail(ARMOUR_E_ARG, "mixed batches are not available with the fp32 study (ARMOUR_EVAL_F32)");
+    if (W <= 0 || W > p->Wmax || !worlds) return fail(ARMOUR_E_ARG, "num_worlds out of range");
+    int O = 0;
+    for (int w = 0; w < W; w++) {
+        const int n = worlds[w].num_obstacles;
+        if (n < 0 || n > p->Omax) return fail(ARMOUR_E_ARG, "num_obstacles exceeds max_obstacles");
+        if (n > 0 && !worlds[w].obstacles) return fail(ARMOUR_E_ARG, "null obstacles");
+        O = std::max(O, n);
+    }
+    std::vector<double> a(4 * (size_t)W * NF), ob((size_t)W * (O > 0 ? O : 1) * 12, 0.0);
+    std::vector<int> ow(W);
+    for (int w = 0; w < W; w++) {
+        for (int i = 0; i < NF; i++) {
+            a[0 * (size_t)W * NF + w * NF + i] = worlds[w].q0[i];
+            a[1 * (size_t)W * NF + w * NF + i] = worlds[w].qd0[i];
+            a[2 * (size_t)W * NF + w * NF + i] = worlds[w].qdd0[i];
+            a[3 * (size_t)W * NF + w * NF + i] = worlds[w].q_des[i];
+        }
+        ow[w] = worlds[w].num_obstacles;
+        if (ow[w] > 0) std::memcpy(&ob[(size_t)w * O * 12], worlds[w].obstacles, sizeof(double) * ow[w] * 12);
+    }
+    const size_t bytes = sizeof(double) * W * NF;
+    HIPCK(hipMemcpyAsync(p->q0, &a[0], bytes, hipMemcpyHostToDevice, p->stream));
+    HIPCK(hipMemcpyAsync(p->qd0, &a[(size_t)W * NF], bytes, hipMemcpyHostToDevice, p->stream));
+    HIPCK(hipMemcpyAsync(p->qdd0, &a[2 * (size_t)W * NF], bytes, hipMemcpyHostToDevice, p->stream));
+    HIPCK(hipMemcpyAsync(p->qdes, &a[3 * (size_t)W * NF], bytes, hipMemcpyHostToDevice, p->stream));
+    if (O > 0) HIPCK(hipMemcpyAsync(p->obs, ob.data(), sizeof(double) * ob.size(), hipMemcpyHostToDevice, p->stream));
+    HIPCK(hipMemcpyAsync(p->d_Ow, ow.data(), sizeof(int) * W, hipMemcpyHostToDevice, p->stream));
+    HIPCK(hipStreamSynchronize(p->stream));  // host staging vectors die at return
+    p->W = W;
+    p->O = O;
+    p->Ow = ow;
+    NlpDev& d = p->d;
+    d.W = W;
+    d.O = O;
+    d.Ow = p->d_Ow;
     d.pcready = 0;
     d.m = d.nt + p->T * p->NJ * O + NF * 4;
     d.R = d.m + NF;
@@ -760,6 +815,9 @@ static int run_reach(armour_planner* p) {
     return 0;
 }
 
+// a solver kernel of the last batch's kind: the uniform instantiation, or the mixed batch's (_mx)
+#define KSEL(k) (p->d.Ow ? k##_mx : k)
+
 // the certified plane cache of the current reach sets and obstacles (plane_cache_kernel)
 static void ensure_plane_cache(armour_planner* p) {
     NlpDev& d = p->d;
@@ -774,7 +832,7 @@ static void ensure_plane_cache(armour_planner* p) {
     // speculative searches that read only the cache (run_solver, ipm_loop, run_resto).
     bool fits = false;
     for (int attempt = 0; attempt < 3; attempt++) {
-        hipLaunchKernelGGL(plane_cache_kernel, dim3(p->T, p->W), dim3(EVAL_THREADS), 0, p->stream, d);
+        hipLaunchKernelGGL(KSEL(plane_cache_kernel), dim3(p->T, p->W), dim3(EVAL_THREADS), 0, p->stream, d);
         if (hipMemcpyAsync(p->h_pcnext, d.pcnext, sizeof(unsigned), hipMemcpyDeviceToHost, p->stream) != hipSuccess ||
             hipStreamSynchronize(p->stream) != hipSuccess)
             break;
@@ -819,7 +877,11 @@ static void launch_eval(armour_planner* p, dim3 grid, const NlpDev& d, int mode,
     if (!s) s = p->stream;
     const bool c = cached && d.pcready && d.O > 0;
     if (c && eval_small_fits(p) && eval_pair_doubles(p->NJ * d.O) <= UB_S) {
-        hipLaunchKernelGGL(eval_kernel_small, grid, dim3(EVAL_THREADS), 0, s, d, mode);
+        hipLaunchKernelGGL(KSEL(eval_kernel_small), grid, dim3(EVAL_THREADS), 0, s, d, mode);
+        return;
+    }
+    if (d.Ow) {  // a mixed batch (fp64 ARMOUR planner: upload_worlds_mixed)
+        hipLaunchKernelGGL(c ? eval_kernel_mx<true> : eval_kernel_mx<false>, grid, dim3(EVAL_THREADS), 0, s, d, mode);
         return;
     }
     auto k = p->eval_f32 ? (d.armtd ? eval_kernel_t<float, true, false> : eval_kernel_t<float, false, false>)
@@ -907,11 +969,11 @@ static int ipm_loop(armour_planner* p, int nrun) {
             dr.fs = d.fs + p->resto_soff;
             dr.partial_s = d.partial_s + p->resto_soff * (size_t)d.nblk * KA;
         }
-        hipLaunchKernelGGL(resto_rows_G, dim3(d.nblk, nb), dim3(ROW_THREADS), 0, s, dr);
-        hipLaunchKernelGGL(resto_world_G, dim3(nb), dim3(64), 0, s, dr);
-        hipLaunchKernelGGL(eval_trials_all, dim3(p->T, nb), dim3(EVAL_THREADS), 0, s, dr);
-        hipLaunchKernelGGL(resto_rows_Vs, dim3(d.nblk, nb * dr.K), dim3(ROW_THREADS), 0, s, dr);
-        hipLaunchKernelGGL(resto_world_Vs, dim3(nb), dim3(64), 0, s, dr);
+        hipLaunchKernelGGL(KSEL(resto_rows_G), dim3(d.nblk, nb), dim3(ROW_THREADS), 0, s, dr);
+        hipLaunchKernelGGL(KSEL(resto_world_G), dim3(nb), dim3(64), 0, s, dr);
+        hipLaunchKernelGGL(KSEL(eval_trials_all), dim3(p->T, nb), dim3(EVAL_THREADS), 0, s, dr);
+        hipLaunchKernelGGL(KSEL(resto_rows_Vs), dim3(d.nblk, nb * dr.K), dim3(ROW_THREADS), 0, s, dr);
+        hipLaunchKernelGGL(KSEL(resto_world_Vs), dim3(nb), dim3(64), 0, s, dr);
         launch_eval(p, dim3(p->T, nb), dr, 5, true, s);
         return 0;
     };
@@ -946,17 +1008,17 @@ static int ipm_loop(armour_planner* p, int nrun) {
         // pass D of the previous iteration (accept its trial point) shares one sweep over the rows
         // with this iteration's pass A
         if (it == 0) {
-            hipLaunchKernelGGL(ipm_rows_A, dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, di);
-            hipLaunchKernelGGL(ipm_world_A, dim3(nrun), dim3(64), 0, p->stream, di, ns);
+            hipLaunchKernelGGL(KSEL(ipm_rows_A), dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, di);
+            hipLaunchKernelGGL(KSEL(ipm_world_A), dim3(nrun), dim3(64), 0, p->stream, di, ns);
         } else {
             // the LDS-accumulator form for grids of several blocks per CU (nlp_kernels.hip rows_DA_body)
             const bool wide = p->da_lds && (long)d.nblk * nrun >= 4L * p->ncu;
-            hipLaunchKernelGGL(wide ? ipm_rows_DA_lds : ipm_rows_DA, dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, di);
-            hipLaunchKernelGGL(ipm_world_DA, dim3(nrun), dim3(64), 0, p->stream, di, ns);
+            hipLaunchKernelGGL(wide ? KSEL(ipm_rows_DA_lds) : KSEL(ipm_rows_DA), dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, di);
+            hipLaunchKernelGGL(KSEL(ipm_world_DA), dim3(nrun), dim3(64), 0, p->stream, di, ns);
         }
         const bool one = tl && p->spec_all && (p->tail_search == 2 || backtracked > 0);
-        hipLaunchKernelGGL(ipm_rows_B, dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, di);
-        if (!one) hipLaunchKernelGGL(ipm_world_B, dim3(nrun), dim3(64), 0, p->stream, di);
+        hipLaunchKernelGGL(KSEL(ipm_rows_B), dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, di);
+        if (!one) hipLaunchKernelGGL(KSEL(ipm_world_B), dim3(nrun), dim3(64), 0, p->stream, di);
         if (one) {
             // The tail's line search in one round: the values of all max_ls trials of every running
             // world at once (round 0's included, the step taken from pass B's partials), then pass
@@ -973,9 +1035,9 @@ static int ipm_loop(armour_planner* p, int nrun) {
             ds.lrun_out = d.cnt + 8 + ((it + 1) & 1);
             ds.nrun_flag = d.flags + 2 + (it & 1);
             ds.bt_flag = d.flags + 4 + (it & 1);
-            hipLaunchKernelGGL(eval_trials_all, dim3(p->T, nrun), dim3(EVAL_THREADS), 0, p->stream, ds);
-            hipLaunchKernelGGL(ipm_rows_Cs, dim3(d.nblk, nrun * ds.K), dim3(ROW_THREADS), 0, p->stream, ds);
-            hipLaunchKernelGGL(ipm_world_Cs_all, dim3(nrun), dim3(64), 0, p->stream, ds);
+            hipLaunchKernelGGL(KSEL(eval_trials_all), dim3(p->T, nrun), dim3(EVAL_THREADS), 0, p->stream, ds);
+            hipLaunchKernelGGL(KSEL(ipm_rows_Cs), dim3(d.nblk, nrun * ds.K), dim3(ROW_THREADS), 0, p->stream, ds);
+            hipLaunchKernelGGL(KSEL(ipm_world_Cs_all), dim3(nrun), dim3(64), 0, p->stream, ds);
             launch_eval(p, dim3(p->T, nrun), ds, 5);
             ub = std::min(W0, ub + nrun);
             if (int rc = resto_iter(it, pend_known > 0 || pub_known > 0 ? ub : 0, p->resto_conc)) return rc;
@@ -1014,8 +1076,8 @@ static int ipm_loop(armour_planner* p, int nrun) {
                 dc.bt_flag = d.flags + 4 + (it & 1);
             }
             launch_eval(p, dim3(p->T, nrun), dc, 1);
-            hipLaunchKernelGGL(ipm_rows_C, dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, dc);
-            hipLaunchKernelGGL(ipm_world_C, dim3(nrun), dim3(64), 0, p->stream, dc);
+            hipLaunchKernelGGL(KSEL(ipm_rows_C), dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, dc);
+            hipLaunchKernelGGL(KSEL(ipm_world_C), dim3(nrun), dim3(64), 0, p->stream, dc);
             if (!tl) {
                 HIPCK(hipStreamSynchronize(p->stream));
                 nnext = ((volatile int*)p->h_flags)[0];
@@ -1030,11 +1092,11 @@ static int ipm_loop(armour_planner* p, int nrun) {
             ds.wl = Ls[1];
             ds.lcount = d.cnt + 5;
             if (eval_small_fits(p) && d.K * p->NJ * d.O <= UB_TS)
-                hipLaunchKernelGGL(eval_trials_small, dim3(p->T, nrun), dim3(EVAL_THREADS), 0, p->stream, ds);
+                hipLaunchKernelGGL(KSEL(eval_trials_small), dim3(p->T, nrun), dim3(EVAL_THREADS), 0, p->stream, ds);
             else
-                hipLaunchKernelGGL(eval_trials_kernel, dim3(p->T, nrun), dim3(EVAL_THREADS), 0, p->stream, ds);
-            hipLaunchKernelGGL(ipm_rows_Cs, dim3(d.nblk, nrun * d.K), dim3(ROW_THREADS), 0, p->stream, ds);
-            hipLaunchKernelGGL(ipm_world_Cs, dim3(nrun), dim3(64), 0, p->stream, ds);
+                hipLaunchKernelGGL(KSEL(eval_trials_kernel), dim3(p->T, nrun), dim3(EVAL_THREADS), 0, p->stream, ds);
+            hipLaunchKernelGGL(KSEL(ipm_rows_Cs), dim3(d.nblk, nrun * d.K), dim3(ROW_THREADS), 0, p->stream, ds);
+            hipLaunchKernelGGL(KSEL(ipm_world_Cs), dim3(nrun), dim3(64), 0, p->stream, ds);
             launch_eval(p, dim3(p->T, nrun), ds, 5);
             ub = std::min(W0, ub + nrun);
             if (int rc = resto_iter(it, pend_known > 0 || pub_known > 0 ? ub : 0, p->resto_conc)) return rc;
@@ -1060,11 +1122,11 @@ static int ipm_loop(armour_planner* p, int nrun) {
             NlpDev ds = d;
             ds.wl = Ls[1];
             if (eval_small_fits(p) && d.K * p->NJ * d.O <= UB_TS)
-                hipLaunchKernelGGL(eval_trials_small, dim3(p->T, nsearch), dim3(EVAL_THREADS), 0, p->stream, ds);
+                hipLaunchKernelGGL(KSEL(eval_trials_small), dim3(p->T, nsearch), dim3(EVAL_THREADS), 0, p->stream, ds);
             else
-                hipLaunchKernelGGL(eval_trials_kernel, dim3(p->T, nsearch), dim3(EVAL_THREADS), 0, p->stream, ds);
-            hipLaunchKernelGGL(ipm_rows_Cs, dim3(d.nblk, nsearch * d.K), dim3(ROW_THREADS), 0, p->stream, ds);
-            hipLaunchKernelGGL(ipm_world_Cs, dim3(nsearch), dim3(64), 0, p->stream, ds);
+                hipLaunchKernelGGL(KSEL(eval_trials_kernel), dim3(p->T, nsearch), dim3(EVAL_THREADS), 0, p->stream, ds);
+            hipLaunchKernelGGL(KSEL(ipm_rows_Cs), dim3(d.nblk, nsearch * d.K), dim3(ROW_THREADS), 0, p->stream, ds);
+            hipLaunchKernelGGL(KSEL(ipm_world_Cs), dim3(nsearch), dim3(64), 0, p->stream, ds);
             launch_eval(p, dim3(p->T, nsearch), ds, 5);
         } else if (nsearch > 0) {
             for (int ls = 1; ls < d.opt.max_ls; ls++) {
@@ -1075,8 +1137,8 @@ static int ipm_loop(armour_planner* p, int nrun) {
                 dc.lcount_out = d.cnt + 4 + ((ls + 1) & 1);
                 dc.ls0 = 0;
                 launch_eval(p, dim3(p->T, nsearch), dc, 1);
-                hipLaunchKernelGGL(ipm_rows_C, dim3(d.nblk, nsearch), dim3(ROW_THREADS), 0, p->stream, dc);
-                hipLaunchKernelGGL(ipm_world_C, dim3(nsearch), dim3(64), 0, p->stream, dc);
+                hipLaunchKernelGGL(KSEL(ipm_rows_C), dim3(d.nblk, nsearch), dim3(ROW_THREADS), 0, p->stream, dc);
+                hipLaunchKernelGGL(KSEL(ipm_world_C), dim3(nsearch), dim3(64), 0, p->stream, dc);
             }
         }
         // (the phase list's bound: its length after round 0, plus the worlds that searched past
@@ -1132,11 +1194,11 @@ static int run_resto(armour_planner* p, const int* list, int n) {
             di.lcount = k == 0 ? nullptr : p->d.cnt + 8 + (k & 1);
             di.lrun_out = p->d.cnt + 8 + ((k + 1) & 1);
             di.nrun_flag = p->d.flags + 2 + (k & 1);
-            hipLaunchKernelGGL(resto_rows_G, dim3(dr.nblk, nb), dim3(ROW_THREADS), 0, p->stream, di);
-            hipLaunchKernelGGL(resto_world_G, dim3(nb), dim3(64), 0, p->stream, di);
-            hipLaunchKernelGGL(eval_trials_all, dim3(p->T, nb), dim3(EVAL_THREADS), 0, p->stream, di);
-            hipLaunchKernelGGL(resto_rows_Vs, dim3(dr.nblk, nb * dr.K), dim3(ROW_THREADS), 0, p->stream, di);
-            hipLaunchKernelGGL(resto_world_Vs, dim3(nb), dim3(64), 0, p->stream, di);
+            hipLaunchKernelGGL(KSEL(resto_rows_G), dim3(dr.nblk, nb), dim3(ROW_THREADS), 0, p->stream, di);
+            hipLaunchKernelGGL(KSEL(resto_world_G), dim3(nb), dim3(64), 0, p->stream, di);
+            hipLaunchKernelGGL(KSEL(eval_trials_all), dim3(p->T, nb), dim3(EVAL_THREADS), 0, p->stream, di);
+            hipLaunchKernelGGL(KSEL(resto_rows_Vs), dim3(dr.nblk, nb * dr.K), dim3(ROW_THREADS), 0, p->stream, di);
+            hipLaunchKernelGGL(KSEL(resto_world_Vs), dim3(nb), dim3(64), 0, p->stream, di);
             launch_eval(p, dim3(p->T, nb), di, 5);
             HIPCK(hipEventRecord(p->tev[k & 1], p->stream));
             HIPCK(hipGetLastError());
@@ -1153,14 +1215,14 @@ static int run_resto(armour_planner* p, const int* list, int n) {
     dr.rflag = 0;
     dr.lrun_out = nullptr;
     for (int k = 0; k < guard; k++) {
-        hipLaunchKernelGGL(resto_rows_G, dim3(dr.nblk, n), dim3(ROW_THREADS), 0, p->stream, dr);
-        hipLaunchKernelGGL(resto_world_G, dim3(n), dim3(64), 0, p->stream, dr);
+        hipLaunchKernelGGL(KSEL(resto_rows_G), dim3(dr.nblk, n), dim3(ROW_THREADS), 0, p->stream, dr);
+        hipLaunchKernelGGL(KSEL(resto_world_G), dim3(n), dim3(64), 0, p->stream, dr);
         HIPCK(hipStreamSynchronize(p->stream));
         if (fl[0] == 0) break;
         for (int ls = 0; ls < dr.opt.max_ls; ls++) {
             launch_eval(p, dim3(p->T, n), dr, 1);
-            hipLaunchKernelGGL(resto_rows_V, dim3(dr.nblk, n), dim3(ROW_THREADS), 0, p->stream, dr);
-            hipLaunchKernelGGL(resto_world_V, dim3(n), dim3(64), 0, p->stream, dr);
+            hipLaunchKernelGGL(KSEL(resto_rows_V), dim3(dr.nblk, n), dim3(ROW_THREADS), 0, p->stream, dr);
+            hipLaunchKernelGGL(KSEL(resto_world_V), dim3(n), dim3(64), 0, p->stream, dr);
             if (ls == 0) {
                 HIPCK(hipStreamSynchronize(p->stream));
                 if (fl[1] == 0) break;
@@ -1183,7 +1245,7 @@ static int run_solver(armour_planner* p) {
     ensure_plane_cache(p);
     hipLaunchKernelGGL(ipm_world_init, dim3((W + 63) / 64), dim3(64), 0, p->stream, d);
     launch_eval(p, dim3(p->T, W), d, 0);
-    hipLaunchKernelGGL(ipm_rows_init, dim3(d.nblk, W), dim3(ROW_THREADS), 0, p->stream, d);
+    hipLaunchKernelGGL(KSEL(ipm_rows_init), dim3(d.nblk, W), dim3(ROW_THREADS), 0, p->stream, d);
     HIPCK(hipGetLastError());
     int rc = ipm_loop(p, W);
     // Restoration phases: the worlds whose line search failed left the loop with
@@ -1205,13 +1267,13 @@ static int run_solver(armour_planner* p) {
         if (ni == 0) break;
         NlpDev di = d;
         di.wl = Li0;
-        hipLaunchKernelGGL(ipm_rows_init, dim3(d.nblk, ni), dim3(ROW_THREADS), 0, p->stream, di);
+        hipLaunchKernelGGL(KSEL(ipm_rows_init), dim3(d.nblk, ni), dim3(ROW_THREADS), 0, p->stream, di);
         rc = ipm_loop(p, ni);
     }
     if (rc) return rc;
     // feasibility re-check and the sliced link centres at the final iterate (the current slot's,
     // armour_joint_position_center.out payload)
-    hipLaunchKernelGGL(feasible_kernel, dim3(W), dim3(256), 0, p->stream, d, p->feas);
+    hipLaunchKernelGGL(KSEL(feasible_kernel), dim3(W), dim3(256), 0, p->stream, d, p->feas);
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -1426,6 +1488,32 @@ int armour_plan_armtd_batch(armour_planner* p, int W, const armour_armtd_world* 
     return rc ? rc : plan_uploaded(p, results, timing, t0);
 }
 
+int armour_reach_batch_mixed(armour_planner* p, int W, const armour_world* worlds, armour_timing* timing) {
+    DeviceScope device_scope(p);
+    if (!p) return fail(ARMOUR_E_ARG, "null planner");
+    p->reached = p->planned = p->evaluated = false;
+    auto t0 = std::chrono::steady_clock::now();
+    const int rc = upload_worlds_mixed(p, W, worlds);
+    return rc ? rc : reach_uploaded(p, timing, t0);
+}
+
+int armour_plan_batch_mixed(armour_planner* p, int W, const armour_world* worlds, armour_result* results,
+                            armour_timing* timing) {
+    DeviceScope device_scope(p);
+    if (!p || !results) return fail(ARMOUR_E_ARG, "null planner / results");
+    p->reached = p->planned = p->evaluated = false;
+    auto t0 = std::chrono::steady_clock::now();
+    const int rc = upload_worlds_mixed(p, W, worlds);
+    return rc ? rc : plan_uploaded(p, results, timing, t0);
+}
+
+int armour_world_num_obstacles(const armour_planner* p, int w) {
+    if (!p) return fail(ARMOUR_E_ARG, "null planner");
+    if (!p->reached) return fail(ARMOUR_E_STATE, "no batch: call a reach or plan entry first");
+    if (w < 0 || w >= p->W) return fail(ARMOUR_E_ARG, "world index out of range");
+    return p->Ow[w];
+}
+
 static int reach_uploaded(armour_planner* p, armour_timing* timing, std::chrono::steady_clock::time_point t0) {
     int rc = 0;
     HIPCK(hipEventRecord(p->ev[0], p->rstream));
@@ -1525,8 +1613,10 @@ int armour_eval_constraints(armour_planner* p, int w, const double* x, double* g
     for (int j = 0; j < NF; j++) inbox = inbox && std::fabs(x[j]) <= PC_XBOX;
     launch_eval(p, dim3(p->T, p->W), d, 0, inbox);
     HIPCK(hipGetLastError());
-    HIPCK(hipMemcpyAsync(g, d.g + gidx(d, 0, w, 0), sizeof(double) * d.m, hipMemcpyDeviceToHost, p->stream));
-    if (jac) HIPCK(hipMemcpyAsync(jac, d.J + gidx(d, 0, w, 0) * NF, sizeof(double) * d.m * NF, hipMemcpyDeviceToHost, p->stream));
+    // world w's own m values (a mixed batch: the first m_w of its slab, which holds them compactly)
+    const size_t mw = (size_t)armour_num_constraints(p, p->Ow[w]);
+    HIPCK(hipMemcpyAsync(g, d.g + gidx(d, 0, w, 0), sizeof(double) * mw, hipMemcpyDeviceToHost, p->stream));
+    if (jac) HIPCK(hipMemcpyAsync(jac, d.J + gidx(d, 0, w, 0) * NF, sizeof(double) * mw * NF, hipMemcpyDeviceToHost, p->stream));
     HIPCK(hipStreamSynchronize(p->stream));
     p->planned = false;
     p->evaluated = true;
@@ -1539,7 +1629,7 @@ int armour_get_constraints(armour_planner* p, int w, double* g) {
     if (!p->planned) return fail(ARMOUR_E_STATE, "no plan");
     if (w < 0 || w >= p->W) return fail(ARMOUR_E_ARG, "world index out of range");
     const int cur = p->h_ws[w].cur;
-    HIPCK(hipMemcpy(g, p->d.g + gidx(p->d, cur, w, 0), sizeof(double) * p->d.m, hipMemcpyDeviceToHost));
+    HIPCK(hipMemcpy(g, p->d.g + gidx(p->d, cur, w, 0), sizeof(double) * armour_num_constraints(p, p->Ow[w]), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1649,15 +1739,21 @@ int armour_get_plane_cache_stats(armour_planner* p, long long* out, int n) {
     HIPCK(hipMemcpyAsync(off.data(), d.pcoff, sizeof(unsigned) * off.size(), hipMemcpyDeviceToHost, p->stream));
     HIPCK(hipMemcpyAsync(ok.data(), d.pcok, blocks, hipMemcpyDeviceToHost, p->stream));
     HIPCK(hipStreamSynchronize(p->stream));
-    long long kept = 0, nok = 0, mx = 0;
-    for (unsigned v : off) {
-        kept += v & 255;
-        mx = std::max<long long>(mx, v & 255);
+    // only the pairs that exist: a mixed batch's world fills the first NJ * O_w entries of each block
+    long long kept = 0, nok = 0, mx = 0, pairs = 0;
+    for (size_t b = 0; b < blocks; b++) {
+        const size_t np = (size_t)p->NJ * p->Ow[b / p->T];
+        pairs += (long long)np;
+        for (size_t q = 0; q < np; q++) {
+            const unsigned v = off[b * NP + q];
+            kept += v & 255;
+            mx = std::max<long long>(mx, v & 255);
+        }
     }
     for (unsigned char v : ok) nok += v;
     unsigned miss = 0;
     HIPCK(hipMemcpy(&miss, d.cnt + 7, sizeof(unsigned), hipMemcpyDeviceToHost));
-    const long long st[ARMOUR_PC_COUNT] = {kept, (long long)off.size(), nok, (long long)blocks, mx, d.pc_pool, miss};
+    const long long st[ARMOUR_PC_COUNT] = {kept, pairs, nok, (long long)blocks, mx, d.pc_pool, miss};
     for (int k = 0; k < n && k < ARMOUR_PC_COUNT; k++) out[k] = st[k];
     return ARMOUR_PC_COUNT;
 }

@@ -135,6 +135,21 @@ int armour_num_constraints(const armour_planner* p, int num_obstacles);
 int armour_plan_batch(armour_planner* p, int num_worlds, const armour_world* worlds, armour_result* results,
                       armour_timing* timing);
 
+/* Plan a mixed batch: every world carries its own number of obstacles, 0 .. max_obstacles (zero
+ * included), and the whole batch runs in one reach launch and one solve. Each world's plan is the
+ * plan of a uniform batch of its own count (its constraint rows keep that batch's layout and order
+ * of summation). armour_plan_batch is unchanged and still refuses mixed counts. Not available on an
+ * ARMTD planner or with the fp32 study (ARMOUR_EVAL_F32): ARMOUR_E_ARG.
+ * After a mixed batch the getters below size their outputs per world: world w has
+ * m_w = armour_num_constraints(p, armour_world_num_obstacles(p, w)) constraints. */
+int armour_plan_batch_mixed(armour_planner* p, int num_worlds, const armour_world* worlds, armour_result* results,
+                            armour_timing* timing);
+/* Reach-set half only for a mixed batch; enables armour_eval_constraints. */
+int armour_reach_batch_mixed(armour_planner* p, int num_worlds, const armour_world* worlds, armour_timing* timing);
+/* Obstacle count of world w of the last batch (uniform or mixed); ARMOUR_E_STATE before any batch,
+ * ARMOUR_E_ARG for a world index out of range. */
+int armour_world_num_obstacles(const armour_planner* p, int w);
+
 /* One plan, the whole of one armour_main.cu process (:37-398) on a planner handle: the single-world
  * entry of SURVEY.md §8(b). Inputs are the content of armour.in (caller-owned); the result and timing
  * are written into *out, and so is every output array the caller supplies (null: skipped) — the
@@ -177,11 +192,12 @@ int armour_reach_armtd_batch(armour_planner* p, int num_worlds, const armour_arm
 int armour_reach_batch(armour_planner* p, int num_worlds, const armour_world* worlds, armour_timing* timing);
 
 /* eval_g / eval_jac_g (KPR/NLPclass.cu:272-396) of world w of the last batch at x; jac (m x 7,
- * row-major) may be null. The parity-pinning entry. */
+ * row-major) may be null. The parity-pinning entry. m is world w's own count (m_w after a mixed
+ * batch, in the reference's order for its O_w obstacles). */
 int armour_eval_constraints(armour_planner* p, int w, const double* x, double* g, double* jac);
 
 /* Outputs of world w of the last batch (the armour_*.out payloads, armour_main.cu:340-398) */
-int armour_get_constraints(armour_planner* p, int w, double* g);              /* m values at k_opt */
+int armour_get_constraints(armour_planner* p, int w, double* g);              /* m values at k_opt (m_w of world w) */
 int armour_get_link_centers(armour_planner* p, int w, double* centers);       /* [T][NJ][3] sliced at the
                                                                                last evaluated point: k_opt after a plan,
                                                                                x after armour_eval_constraints (which
@@ -216,7 +232,8 @@ int armour_get_reach_profile(armour_planner* p, unsigned long long* cycles_terms
  * writes [0] planes kept over all (world, t, link, obstacle) pairs, [1] pairs, [2] (world, t) blocks
  * whose cache region held every kept plane, [3] blocks, [4] most planes kept for one pair,
  * [5] records in the cache pool, [6] evaluations that found a point outside the cache's box (rows
- * NaN; the solver never produces one). Returns ARMOUR_PC_COUNT; ARMOUR_E_STATE when the cache is off. */
+ * NaN; the solver never produces one). Returns ARMOUR_PC_COUNT; ARMOUR_E_STATE when the cache is off.
+ * After a mixed batch [0], [1] and [4] count only the pairs that exist (NJ * O_w per block of world w). */
 #define ARMOUR_PC_COUNT 7
 int armour_get_plane_cache_stats(armour_planner* p, long long* out, int n);
 /* Execution span of the last reach launch on the device clock (wall_clock64): from the first
