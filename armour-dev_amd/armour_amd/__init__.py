@@ -103,7 +103,9 @@ def lib():
         # mixed entry on such a build raises)
         for name, args in (("armour_plan_batch_mixed", L.armour_plan_batch.argtypes),
                            ("armour_reach_batch_mixed", L.armour_reach_batch.argtypes),
-                           ("armour_world_num_obstacles", [ctypes.c_void_p, ctypes.c_int])):
+                           ("armour_world_num_obstacles", [ctypes.c_void_p, ctypes.c_int]),
+                           ("armour_eval_candidates", [ctypes.c_void_p, ctypes.c_int, _dp, _dp, _dp,
+                                                       ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = args
         L.armour_plan.argtypes = [ctypes.c_void_p, ctypes.POINTER(World), ctypes.POINTER(PlanOutput)]
@@ -133,7 +135,8 @@ ABI_SYMBOLS = ["armour_copy_bandwidth", "armour_create", "armour_create_robot", 
                "armour_get_reach_dump", "armour_get_reach_occupancy", "armour_get_monomial_counts",
                "armour_create_armtd", "armour_plan_armtd_batch", "armour_reach_armtd_batch",
                "armour_get_plane_cache_stats", "armour_plan", "armour_get_reach_span",
-               "armour_plan_batch_mixed", "armour_reach_batch_mixed", "armour_world_num_obstacles"]
+               "armour_plan_batch_mixed", "armour_reach_batch_mixed", "armour_world_num_obstacles",
+               "armour_eval_candidates"]
 
 
 def default_batch(T: int, device: int = 0, waves: int = 2) -> int:
@@ -162,6 +165,24 @@ def _ptr(a):
     return a.ctypes.data_as(_dp) if a is not None else None
 
 
+def candidates_array(x, W):
+    """the [W, N, 7] array Planner.eval_candidates hands to the library, from x of that shape or
+    [N, 7] (the same candidates for each of the W worlds); ValueError for a wrong shape, a non-finite
+    value or one outside [-1, 1] (the box the collision planes are certified for)"""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim == 2 and x.shape[1] == NF and x.shape[0] >= 1:
+        if W < 1:
+            raise ValueError("eval_candidates: x of shape [N, 7] needs a batch (reach or plan first)")
+        x = np.broadcast_to(x, (W,) + x.shape)
+    if x.ndim != 3 or x.shape[2] != NF or x.shape[0] < 1 or x.shape[1] < 1 or (W >= 1 and x.shape[0] != W):
+        raise ValueError(f"eval_candidates: x must have shape [W, N, {NF}] or [N, {NF}] (W = {W}), got {x.shape}")
+    if not np.all(np.isfinite(x)):
+        raise ValueError("eval_candidates: x holds a non-finite value")
+    if np.abs(x).max() > 1.0:
+        raise ValueError("eval_candidates: every candidate must lie in [-1, 1]")
+    return np.ascontiguousarray(x)
+
+
 class Planner:
     """Batched MI355X planner. A world is (q0, qd0, qdd0, q_des, obstacles[O, 12]). plan / reach take
     worlds that all carry the same O; plan_mixed / reach_mixed take any mix of counts."""
@@ -184,6 +205,7 @@ class Planner:
         self.max_worlds = max_worlds
         self._keep = []
         self.O = 0
+        self._W = 0   # worlds of the last batch handed to the library
 
     def close(self):
         if getattr(self, "h", None) and _LIB is not None:  # (module teardown may have cleared _LIB)
@@ -212,6 +234,7 @@ class Planner:
         starts = np.concatenate([[0], np.cumsum(counts)[:-1]]) * 12 * 8
         view["obstacles"] = np.where(counts > 0, block.ctypes.data + starts, 0)
         self.O = int(counts[0]) if n else 0
+        self._W = n
         return arr
 
     def plan_one(self, world):
@@ -302,6 +325,24 @@ class Planner:
         J = np.zeros((m, NF)) if jac else None
         _check(lib().armour_eval_constraints(self.h, w, _ptr(x), _ptr(g), _ptr(J)))
         return (g, J) if jac else g
+
+    def eval_candidates(self, x, num_worlds=None):
+        """armour_eval_candidates: N candidate parameters per world of the last batch, reduced on the
+        device. x: [W, N, 7], or [N, 7] for the same candidates in every world (W worlds: num_worlds,
+        default the last reach / plan call's). Returns dict(cost [W, N], violation [W, N, 3] (torque,
+        collision, extremum rows), feasible [W, N] bool, best [W] (-1: none)). The plan state, the
+        getters and the next plan are untouched. Raises ValueError for a wrong shape, a non-finite
+        value or one outside [-1, 1], before the library is called."""
+        x = candidates_array(x, self._W if num_worlds is None else int(num_worlds))
+        Wx, N = x.shape[:2]
+        cost = np.zeros((Wx, N))
+        viol = np.zeros((Wx, N, 3))
+        feas = np.zeros((Wx, N), dtype=np.int32)
+        best = np.zeros(Wx, dtype=np.int32)
+        ip = ctypes.POINTER(ctypes.c_int)
+        _check(lib().armour_eval_candidates(self.h, N, _ptr(x), _ptr(cost), _ptr(viol), feas.ctypes.data_as(ip),
+                                            best.ctypes.data_as(ip)))
+        return dict(cost=cost, violation=viol, feasible=feas.astype(bool), best=best)
 
     def constraints(self, w):
         g = np.zeros(self._m(w))
@@ -419,6 +460,7 @@ class ArmtdPlanner(Planner):
             a.obstacles = _ptr(o) if o.shape[0] else None
         self._keep = keep
         self.O = arr[0].num_obstacles if n else 0
+        self._W = n
         return arr
 
     def _plan_call(self, *a):
@@ -428,4 +470,4 @@ class ArmtdPlanner(Planner):
         return lib().armour_reach_armtd_batch(*a)
 
 
-__all__ = ["ArmtdPlanner", "Planner", "ArmourError", "ARMOUR_E_CAPACITY", "ARMOUR_E_INTERNAL", "copy_bandwidth", "default_batch", "make_world", "example_world", "csv_world", "straight_line_waypoint", "KINOVA", "LIB_PATH", "ABI_SYMBOLS"]
+__all__ = ["ArmtdPlanner", "Planner", "ArmourError", "ARMOUR_E_CAPACITY", "ARMOUR_E_INTERNAL", "copy_bandwidth", "default_batch", "make_world", "example_world", "csv_world", "straight_line_waypoint", "KINOVA", "LIB_PATH", "ABI_SYMBOLS", "candidates_array"]

@@ -2904,4 +2904,329 @@ __device__ __attribute__((always_inline)) void feasible_body(const NlpDev& d, in
 __global__ void feasible_kernel(NlpDev d, int* feasible) { feasible_body<false>(d, feasible); }
 __global__ void feasible_kernel_mx(NlpDev d, int* feasible) { feasible_body<true>(d, feasible); }
 
+// ------------------------------------------------------------------------------------------
+// Candidate evaluation (armour_eval_candidates): N caller points per world, reduced on the device to
+// the cost, the largest excess per row class and finalize_solution's verdict; g is never stored.
+//
+// cand_rows, grid (T, W, ceil(N / CAND_KC)): block (t, w, chunk) stages the (world, t) monomials
+// once (as eval_trials_body), slices the link centres and torque rows of its CAND_KC candidates with
+// eval_kernel_t's arithmetic and term order, and scans the block's certified-plane records once for
+// the whole chunk. Mapping of the scan: record-parallel, as eval_trials_body's. A thread takes
+// records tid, tid + 256, ... (coalesced loads, every record read by one thread) and forms the two
+// candidates of each of the chunk's points from the sliced centres in LDS; the (point, pair)
+// maximum is an LDS atomicMax on an order-preserving key, in the staging buffer, in passes of as
+// many points as its keys hold (UB / NP: the survey shape's 140 pairs take 16 points per pass, the
+// largest shape's 360 pairs 6 to 9). Measured against a lane per pair with four running maxima in
+// registers per wave (no atomics, but a gather: every wave walks all pairs' records, five strided
+// 8-byte loads per record) on 327 survey worlds x 256 points at 16 points per block: 15.7 ms against
+// 16.7 ms per launch (19.2 ms with four records per load round: fewer waves, more loads), so the
+// record-parallel form stays; both sit near one LDS atomic, or one gathered record, per (record,
+// point) and far from the record stream's HBM time.
+// A collision row is minus its pair's largest candidate above the scan's start value (-1e8), the
+// value eval_kernel_t stores; a maximum is exact in any order, so nothing depends on the chunking.
+// Per (candidate, t) the block stores the two class maxima and the comparison flags: [W][N][T],
+// never [N][m].
+// CAND_KC = 32 points per block: the most whose 7 coordinates one 256-thread block stages in one
+// step; the scan keeps no per-point registers (90 VGPRs, no spills), LDS per block 50.1 KB with the
+// reach's caps (three blocks per CU) and 36.8 KB with the small ones (four). 16 points per block
+// read the records twice as often for 15.7 against 15.4 ms.
+// cand_finish, one wave per (world, candidate): the maxima over t, the 28 extremum rows and the
+// cost (lanes 0..13 and 14: one division / root chain per lane), feasible. cand_best: per world the
+// lowest-cost feasible candidate, ties to the lowest index.
+constexpr int CAND_KC = 32;
+constexpr int CAND_PK = 2304;   // (point, pair) keys of a scan pass at least: 16 points of 144 pairs, 6 of 360
+static_assert(CAND_PK >= MAX_J * MAX_OBS, "a pass holds at least one point");
+static_assert(CAND_KC * NF <= EVAL_THREADS, "one thread per (candidate, variable) of the chunk");
+struct CandDev {
+    int N;              // candidates per world
+    const double* x;    // [W][N][NF]
+    double* ptq;        // [W][N][T] torque rows:    max(L - tv - v, v - U - tv) over the NF rows of t
+    double* pcol;       // [W][N][T] collision rows: max(v - cv) over the pairs of t (-inf: no obstacles)
+    int* pbad;          // [W][N][T] bit 0 / 1: a torque / collision row of t fails feasible_kernel's test
+    double* cost;       // [W][N]
+    double* viol;       // [W][N][3]
+    int* feas;          // [W][N]
+    int* best;          // [W]
+};
+
+template <int LM, int UM, bool MX>
+__device__ __attribute__((always_inline)) void cand_rows_body(const NlpDev& d, const CandDev& c) {
+    constexpr int KC = CAND_KC;
+    const int t = blockIdx.x, w = blockIdx.y, n0 = blockIdx.z * KC;
+    if (d.ro.err[w]) return;  // no reach set: cand_finish reports the world
+    const RobotParams& rp = *d.rp;
+    const int tid = threadIdx.x;
+    const int KN = c.N - n0 < KC ? c.N - n0 : KC;  // candidates of this chunk
+    const long jt = (long)w * d.T + t;
+    const int NJ = d.NJ, O = shape_of<MX>(d, w).O, NP = NJ * O;
+    __shared__ double ptab[KC][NF][4];  // x_j^g of candidate k (the value slices' factors)
+    __shared__ double lck[KC][MAX_J][3];
+    __shared__ double tqv[KC][NF];
+    __shared__ int tqb[KC][NF];
+    __shared__ double colv[KC];
+    __shared__ int colb[KC];
+    __shared__ uint16_t lh[MAX_J][LM];
+    __shared__ uint16_t th[NF][UM];
+    constexpr int UB = MAX_J * LM * 3 + NF * UM > CAND_PK ? MAX_J * LM * 3 + NF * UM : CAND_PK;
+    __shared__ double ubuf[UB];  // monomial staging, then the scan's (point, pair) keys
+    __shared__ int lcnt[MAX_J], tcnt[NF];
+    auto lco = reinterpret_cast<double (*)[LM][3]>(ubuf);
+    auto tco = reinterpret_cast<double (*)[UM]>(ubuf + MAX_J * LM * 3);
+    if (tid < KC * NF) {
+        const int kk = tid / NF, j = tid % NF;
+        const double xj = kk < KN ? c.x[((long)w * c.N + n0 + kk) * NF + j] : 0.0;
+        ptab[kk][j][0] = 1.0; ptab[kk][j][1] = xj; ptab[kk][j][2] = xj * xj; ptab[kk][j][3] = xj * xj * xj;
+    }
+    if (tid >= 128 && tid < 128 + NJ) lcnt[tid - 128] = min(d.ro.link_cnt[jt * NJ + tid - 128], LM);
+    if (tid >= 160 && tid < 160 + NF) tcnt[tid - 160] = min(d.ro.tq_cnt[jt * NF + tid - 160], UM);
+    __syncthreads();
+    {
+        int lpre[MAX_J + 1], tpre[NF + 1];
+        lpre[0] = 0;
+#pragma unroll
+        for (int l = 0; l < MAX_J; l++) lpre[l + 1] = lpre[l] + (l < NJ ? lcnt[l] : 0);
+        tpre[0] = 0;
+#pragma unroll
+        for (int j = 0; j < NF; j++) tpre[j + 1] = tpre[j] + tcnt[j];
+        const int L = lpre[MAX_J], M = tpre[NF];
+        for (int u = tid; u < L + M; u += blockDim.x) {
+            if (u < L) {
+                int l = 0, q0 = 0;
+#pragma unroll
+                for (int k = 1; k < MAX_J; k++) if (u >= lpre[k]) { l = k; q0 = lpre[k]; }
+                const int q = u - q0;
+                const long b = (jt * NJ + l) * CAP_LM + q;
+                lh[l][q] = d.ro.link_hash[b];
+                lco[l][q][0] = d.ro.link_coef[b * 3];
+                lco[l][q][1] = d.ro.link_coef[b * 3 + 1];
+                lco[l][q][2] = d.ro.link_coef[b * 3 + 2];
+            } else {
+                const int v = u - L;
+                int j = 0, q0 = 0;
+#pragma unroll
+                for (int k = 1; k < NF; k++) if (v >= tpre[k]) { j = k; q0 = tpre[k]; }
+                const int q = v - q0;
+                const long b = (jt * NF + j) * CAP_UM + q;
+                th[j][q] = d.ro.tq_hash[b];
+                tco[j][q] = d.ro.tq_coef[b];
+            }
+        }
+    }
+    __syncthreads();
+    // value slices of every candidate, monomial order: the KN * NF torque rows (the longest sums)
+    // first, then the link centres (k, l, e)
+    auto vterm = [&](double co, int h, int kk) {
+        double v = co;
+#pragma unroll
+        for (int j = 0; j < NF; j++) v = v * ptab[kk][j][(h >> (2 * j)) & 3];
+        return v;
+    };
+    const int ntv = KN * NF, nlv = KN * NJ * 3;
+    for (int u = tid; u < ntv + nlv; u += blockDim.x) {
+        if (u >= ntv) {
+            const int ul = u - ntv;
+            const int kk = ul / (NJ * 3), l = (ul / 3) % NJ, e = ul % 3;
+            const long base = jt * NJ + l;
+            double s = d.ro.link_center[base * 3 + e];
+            const int cnt = lcnt[l];
+            int q = 0;
+            for (; q + 4 <= cnt; q += 4) {
+                const double v0 = vterm(lco[l][q][e], lh[l][q], kk), v1 = vterm(lco[l][q + 1][e], lh[l][q + 1], kk);
+                const double v2 = vterm(lco[l][q + 2][e], lh[l][q + 2], kk), v3 = vterm(lco[l][q + 3][e], lh[l][q + 3], kk);
+                s = s + v0; s = s + v1; s = s + v2; s = s + v3;
+            }
+            for (; q < cnt; q++) s = s + vterm(lco[l][q][e], lh[l][q], kk);
+            const double r = d.ro.link_rad[base * 3 + e];
+            lck[kk][l][e] = ((s - r) + (s + r)) * 0.5;  // getCenter(Interval(c - r, c + r))
+        } else {
+            const int kk = u / NF, j = u % NF;
+            const long base = jt * NF + j;
+            double s = d.ro.tq_center[base];
+            const int cnt = tcnt[j];
+            int q = 0;
+            for (; q + 4 <= cnt; q += 4) {
+                const double v0 = vterm(tco[j][q], th[j][q], kk), v1 = vterm(tco[j][q + 1], th[j][q + 1], kk);
+                const double v2 = vterm(tco[j][q + 2], th[j][q + 2], kk), v3 = vterm(tco[j][q + 3], th[j][q + 3], kk);
+                s = s + v0; s = s + v1; s = s + v2; s = s + v3;
+            }
+            for (; q < cnt; q++) s = s + vterm(tco[j][q], th[j][q], kk);
+            const double r = d.ro.tq_rad[base];
+            const double v = ((s - r) + (s + r)) * 0.5;
+            // bounds_of's torque row and feasible_kernel's comparisons
+            const double tr = d.ro.torque_radius[base];
+            const double Lb = -rp.torque_limits[j] + tr, Ub = rp.torque_limits[j] - tr;
+            const double tv = rp.torque_violation;
+            tqv[kk][j] = fmax((Lb - tv) - v, (v - Ub) - tv);
+            tqb[kk][j] = (v < Lb - tv || v > Ub + tv) ? 1 : 0;
+        }
+    }
+    __syncthreads();
+    // collision rows, record-parallel: a thread takes records q = tid, tid + 256, ... (coalesced) and
+    // forms the candidates of KP points per pass; the (point, pair) maximum by an LDS atomicMax on an
+    // order-preserving key in the staging buffer (free now), KP = the points whose keys fit it
+    {
+        const int g = tid >> 6, lane = tid & 63;
+        const double cv = rp.collision_violation;
+        const double start = -100000000.0;
+        unsigned long long* const pkey = reinterpret_cast<unsigned long long*>(ubuf);  // [KP][NP]
+        const long NPS = (long)NJ * d.O;
+        const unsigned last = NP > 0 ? d.pcoff[jt * NPS + NP - 1] : 0u;
+        const int total = (int)(last >> 8) + (int)(last & 255);
+        const unsigned long long pb = NP > 0 ? d.pcbase[jt] : 0ull;
+        const double* const rec = d.pc + 5 * pb;
+        const uint16_t* const pcp = d.pcp + pb;
+        const int cap = total;  // the block's [5][n] record arrays
+        const int KP = NP > 0 ? min(KC, UB / NP) : KC;
+        for (int k0 = 0; k0 < KN; k0 += KP) {
+            const int kp = min(KP, KN - k0);
+            for (int u = tid; u < kp * NP; u += blockDim.x) pkey[u] = okey(start);
+            __syncthreads();
+            for (int q = tid; q < total; q += blockDim.x) {
+                const double a0 = rec[q], a1 = rec[cap + q], a2 = rec[2 * cap + q];
+                const double P = rec[3 * cap + q], N = rec[4 * cap + q];
+                const int pr = min((int)pcp[q], NP - 1), l = pr / O;
+                for (int kk = 0; kk < kp; kk++) {
+                    const double* const lc = lck[k0 + kk][l];
+                    const double Ac = a0 * lc[0] + a1 * lc[1] + a2 * lc[2];
+                    const double pos = Ac - P, neg = -Ac - N;
+                    const double v = (neg > pos || pos != pos) ? neg : pos;
+                    if (v > start) atomicMax(&pkey[kk * NP + pr], okey(v));
+                }
+            }
+            __syncthreads();
+            // wave g: points g, g + 4, ... of the pass; the maximum of row - cv over the pairs
+            for (int kk = g; kk < kp; kk += EVAL_THREADS / 64) {
+                double cm = -__builtin_inf();
+                int cb = 0;
+                for (int pr = lane; pr < NP; pr += 64) {
+                    const double row = -dkey(pkey[kk * NP + pr]);
+                    cm = fmax(cm, row - cv);
+                    cb |= row > cv ? 1 : 0;
+                }
+                cm = wave_max(cm);
+                cb = __any(cb);
+                if (lane == 0) {
+                    colv[k0 + kk] = cm;
+                    colb[k0 + kk] = cb ? 2 : 0;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (tid < KN) {
+        double m = tqv[tid][0];
+        int b = tqb[tid][0];
+#pragma unroll
+        for (int j = 1; j < NF; j++) {
+            m = fmax(m, tqv[tid][j]);
+            b |= tqb[tid][j];
+        }
+        const long o = ((long)w * c.N + n0 + tid) * d.T + t;
+        c.ptq[o] = m;
+        c.pcol[o] = colv[tid];
+        c.pbad[o] = b | colb[tid];
+    }
+}
+__global__ __launch_bounds__(EVAL_THREADS) void cand_rows(NlpDev d, CandDev c) { cand_rows_body<CAP_LM, CAP_UM, false>(d, c); }
+__global__ __launch_bounds__(EVAL_THREADS) void cand_rows_mx(NlpDev d, CandDev c) { cand_rows_body<CAP_LM, CAP_UM, true>(d, c); }
+__global__ __launch_bounds__(EVAL_THREADS) void cand_rows_small(NlpDev d, CandDev c) { cand_rows_body<LM_S, UM_S, false>(d, c); }
+__global__ __launch_bounds__(EVAL_THREADS) void cand_rows_small_mx(NlpDev d, CandDev c) { cand_rows_body<LM_S, UM_S, true>(d, c); }
+
+// grid (ceil(N / 4), W), one wave per (world, candidate)
+template <bool MX>
+__device__ __attribute__((always_inline)) void cand_finish_body(const NlpDev& d, const CandDev& c) {
+    const int w = blockIdx.y, n = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (n >= c.N) return;
+    const long o = (long)w * c.N + n;
+    if (d.ro.err[w]) {
+        // the world's reach set failed: nothing to evaluate
+        if (lane == 0) {
+            const double nan = __builtin_nan("");
+            c.cost[o] = nan;
+            c.viol[o * 3] = nan; c.viol[o * 3 + 1] = nan; c.viol[o * 3 + 2] = nan;
+            c.feas[o] = 0;
+        }
+        return;
+    }
+    const RobotParams& rp = *d.rp;
+    const Shape sh = shape_of<MX>(d, w);
+    const double ninf = -__builtin_inf();
+    double tq = ninf, col = ninf, ex = ninf;
+    int bad = 0;
+    for (int t = lane; t < d.T; t += 64) {
+        tq = fmax(tq, c.ptq[o * d.T + t]);
+        col = fmax(col, c.pcol[o * d.T + t]);
+        bad |= c.pbad[o * d.T + t];
+    }
+    const double* x = c.x + o * NF;
+    const double* q0 = d.q0 + w * NF;
+    const double* qd0 = d.qd0 + w * NF;
+    const double* qdd0 = d.qdd0 + w * NF;
+    const double D = rp.duration;
+    if (lane < 2 * NF) {
+        // extremum rows (eval_kernel_t's) against bounds_of's limits, feasible_kernel's comparisons
+        const int kind = lane / NF, j = lane % NF;
+        double mn, mx, e2, e3;
+        int mnid, mxid;
+        extremum(kind, q0[j], qd0[j] * D, qdd0[j] * D * D, rp.k_range[j] * x[j], &mn, &mx, &mnid, &mxid, &e2, &e3);
+        const double scale = kind == 0 ? 1.0 : D;
+        const double vmn = mn / scale, vmx = mx / scale;
+        double Lb, Ub;
+        bounds_of(d, sh, w, d.nt + d.T * d.NJ * sh.O + kind * 2 * NF + j, Lb, Ub);
+        ex = fmax(fmax(Lb - vmn, vmn - Ub), fmax(Lb - vmx, vmx - Ub));
+        if (vmn < Lb || vmn > Ub || vmx < Lb || vmx > Ub) bad |= 4;
+    } else if (lane == 2 * NF) {
+        // cost: wrapped joints summed first (NLPclass.cu:225-233)
+        const double tp = rp.t_plan;
+        double qp[NF];
+        for (int j = 0; j < NF; j++) qp[j] = bz_q(q0[j], qd0[j] * D, qdd0[j] * D * D, rp.k_range[j] * x[j], tp);
+        double fv = 0.0;
+        bool first = true;
+        for (int pass = 1; pass >= 0; pass--)
+            for (int j = 0; j < NF; j++) {
+                if (rp.wrap_mask[j] != pass) continue;
+                const double dd = pass ? wrap_to_pi(d.qdes[w * NF + j] - qp[j]) : (d.qdes[w * NF + j] - qp[j]);
+                const double term = dd * dd;
+                fv = first ? term : fv + term;
+                first = false;
+            }
+        c.cost[o] = (fv * rp.cost_scale) / rp.cost_scale;  // armour_result.cost: f / cost_scale
+    }
+    tq = wave_max(tq);
+    col = wave_max(col);
+    ex = wave_max(ex);
+    const int anybad = __any(bad != 0);
+    if (lane == 0) {
+        c.viol[o * 3] = tq;
+        c.viol[o * 3 + 1] = col;
+        c.viol[o * 3 + 2] = ex;
+        c.feas[o] = anybad ? 0 : 1;
+    }
+}
+__global__ __launch_bounds__(256) void cand_finish(NlpDev d, CandDev c) { cand_finish_body<false>(d, c); }
+__global__ __launch_bounds__(256) void cand_finish_mx(NlpDev d, CandDev c) { cand_finish_body<true>(d, c); }
+
+// grid W: lane k takes candidates k, k + 64, ... in order, lane 0 merges the lanes in order
+__global__ __launch_bounds__(64) void cand_best(NlpDev d, CandDev c) {
+    const int w = blockIdx.x, lane = threadIdx.x;
+    __shared__ double bc[64];
+    __shared__ int bi[64];
+    double f = 0.0;
+    int idx = -1;
+    for (int n = lane; n < c.N; n += 64) {
+        const long o = (long)w * c.N + n;
+        if (!c.feas[o]) continue;
+        const double v = c.cost[o];
+        if (idx < 0 || v < f) { f = v; idx = n; }
+    }
+    bc[lane] = f;
+    bi[lane] = idx;
+    __syncthreads();
+    if (lane == 0) {
+        for (int k = 1; k < 64; k++)
+            if (bi[k] >= 0 && (idx < 0 || bc[k] < f || (bc[k] == f && bi[k] < idx))) { f = bc[k]; idx = bi[k]; }
+        c.best[w] = idx;
+    }
+}
+
 }  // namespace armour

@@ -42,6 +42,13 @@ template <class T>
 hipError_t dalloc(T** p, size_t n) {
     return hipMalloc((void**)p, sizeof(T) * (n > 0 ? n : 1));
 }
+// the buffers of armour_eval_candidates (CandDev, nlp_kernels.hip)
+void cand_free(CandDev& c) {
+    for (const void* a : {(const void*)c.x, (const void*)c.ptq, (const void*)c.pcol, (const void*)c.pbad, (const void*)c.cost,
+                          (const void*)c.viol, (const void*)c.feas, (const void*)c.best})
+        if (a) (void)hipFree(const_cast<void*>(a));
+    c = CandDev{};
+}
 }  // namespace
 
 // planners alive per device (armour_create / armour_destroy): the bundle kernel's shape depends on
@@ -135,6 +142,10 @@ struct armour_planner {
     std::vector<int> Ow;       // obstacle count of each world of the last batch
     int* d_Ow = nullptr;       // [max_worlds] device copy of a mixed batch's counts (NlpDev::Ow)
     bool reached = false, planned = false, evaluated = false;  // evaluated: slot 0 holds armour_eval_constraints' point
+    // armour_eval_candidates: buffers of its own for max_worlds x cand_cap candidates (allocated on
+    // first use, regrown when a call brings more candidates per world)
+    CandDev cd{};
+    int cand_cap = 0;
     std::vector<void*> allocs;
 
     template <class T>
@@ -1407,6 +1418,7 @@ void armour_destroy(armour_planner* p) {
     if (!p) return;
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     for (void* a : p->allocs) (void)hipFree(a);
+    cand_free(p->cd);
     if (p->h_flags) (void)hipHostFree(p->h_flags);
     if (p->h_sum) (void)hipHostFree(p->h_sum);
     if (p->h_ws) (void)hipHostFree(p->h_ws);
@@ -1620,6 +1632,69 @@ int armour_eval_constraints(armour_planner* p, int w, const double* x, double* g
     HIPCK(hipStreamSynchronize(p->stream));
     p->planned = false;
     p->evaluated = true;
+    return 0;
+}
+
+// buffers of armour_eval_candidates for N candidates per world
+static int cand_reserve(armour_planner* p, int N) {
+    if (N <= p->cand_cap) return 0;
+    CandDev& c = p->cd;
+    HIPCK(hipStreamSynchronize(p->stream));
+    cand_free(c);
+    p->cand_cap = 0;
+    const size_t n = (size_t)p->Wmax * N, nT = n * p->T;
+    double* x = nullptr;
+    if (dalloc(&x, n * NF) != hipSuccess || dalloc(&c.ptq, nT) != hipSuccess || dalloc(&c.pcol, nT) != hipSuccess ||
+        dalloc(&c.pbad, nT) != hipSuccess || dalloc(&c.cost, n) != hipSuccess || dalloc(&c.viol, n * 3) != hipSuccess ||
+        dalloc(&c.feas, n) != hipSuccess || dalloc(&c.best, (size_t)p->Wmax) != hipSuccess) {
+        c.x = x;
+        cand_free(c);
+        return fail(ARMOUR_E_HIP, "hipMalloc failed for the candidate buffers (max_worlds x num_candidates x T partials)");
+    }
+    c.x = x;
+    p->cand_cap = N;
+    return 0;
+}
+
+int armour_eval_candidates(armour_planner* p, int N, const double* x, double* cost, double* violation, int* feasible,
+                           int* best) {
+    DeviceScope device_scope(p);
+    if (!p || !x) return fail(ARMOUR_E_ARG, "null planner / x");
+    if (p->armtd) return fail(ARMOUR_E_ARG, "candidate evaluation is not available on an ARMTD planner");
+    if (p->eval_f32) return fail(ARMOUR_E_ARG, "candidate evaluation is not available with the fp32 study (ARMOUR_EVAL_F32)");
+    if (N < 1) return fail(ARMOUR_E_ARG, "num_candidates must be at least 1");
+    if (!p->reached) return fail(ARMOUR_E_STATE, "no batch: call a reach or plan entry first");
+    const int W = p->W;
+    const size_t n = (size_t)W * N;
+    if (n > (size_t)1 << 30 || (size_t)((N + CAND_KC - 1) / CAND_KC) > 65535)
+        return fail(ARMOUR_E_ARG, "too many candidates (num_candidates <= 1048560, worlds x candidates <= 2^30)");
+    // the plane cache is certified for the box |x_i| <= 1 only
+    for (size_t i = 0; i < n * NF; i++)
+        if (!(std::fabs(x[i]) <= 1.0)) return fail(ARMOUR_E_ARG, "every candidate must be finite and inside [-1, 1]");
+    NlpDev& d = p->d;
+    ensure_plane_cache(p);
+    if (d.O > 0 && !d.pcready)
+        return fail(ARMOUR_E_STATE, d.pcache ? "the certified plane cache is unavailable (its build did not fit a pool); "
+                                               "candidate evaluation has no full-scan path"
+                                             : "the certified plane cache is unavailable (ARMOUR_PLANE_CACHE=0, or the batch "
+                                               "capacity exceeds its 32-bit pool); candidate evaluation has no full-scan path");
+    if (int rc = cand_reserve(p, N)) return rc;
+    CandDev c = p->cd;
+    c.N = N;
+    HIPCK(hipMemcpyAsync(const_cast<double*>(c.x), x, sizeof(double) * n * NF, hipMemcpyHostToDevice, p->stream));
+    const dim3 grid(p->T, W, (N + CAND_KC - 1) / CAND_KC);
+    if (eval_small_fits(p))
+        hipLaunchKernelGGL(KSEL(cand_rows_small), grid, dim3(EVAL_THREADS), 0, p->stream, d, c);
+    else
+        hipLaunchKernelGGL(KSEL(cand_rows), grid, dim3(EVAL_THREADS), 0, p->stream, d, c);
+    hipLaunchKernelGGL(KSEL(cand_finish), dim3((N + 3) / 4, W), dim3(256), 0, p->stream, d, c);
+    hipLaunchKernelGGL(cand_best, dim3(W), dim3(64), 0, p->stream, d, c);
+    HIPCK(hipGetLastError());
+    if (cost) HIPCK(hipMemcpyAsync(cost, c.cost, sizeof(double) * n, hipMemcpyDeviceToHost, p->stream));
+    if (violation) HIPCK(hipMemcpyAsync(violation, c.viol, sizeof(double) * n * 3, hipMemcpyDeviceToHost, p->stream));
+    if (feasible) HIPCK(hipMemcpyAsync(feasible, c.feas, sizeof(int) * n, hipMemcpyDeviceToHost, p->stream));
+    if (best) HIPCK(hipMemcpyAsync(best, c.best, sizeof(int) * W, hipMemcpyDeviceToHost, p->stream));
+    HIPCK(hipStreamSynchronize(p->stream));
     return 0;
 }
 

@@ -196,6 +196,30 @@ int armour_reach_batch(armour_planner* p, int num_worlds, const armour_world* wo
  * batch, in the reference's order for its O_w obstacles). */
 int armour_eval_constraints(armour_planner* p, int w, const double* x, double* g, double* jac);
 
+/* Evaluate N candidate parameters per world of the last batch (uniform or mixed; after any reach or
+ * plan entry) without forming g per candidate in memory and without touching the batch's plan state:
+ * the getters return what they returned before and the next plan is the one it would have been.
+ * x: [W][N][7], every |x| <= 1. Outputs, each optional (null: skipped):
+ *   cost      [W][N]     objective / COST_FUNCTION_OPTIMALITY_SCALE (as armour_result.cost)
+ *   violation [W][N][3]  largest excess over the finalize_solution test per row class:
+ *                        [0] torque rows   max(L - tv - v, v - U - tv)
+ *                        [1] collision rows max(v - cv)   (-infinity for a world with no obstacles)
+ *                        [2] the 28 position/velocity extremum rows max(L - v, v - U)
+ *   feasible  [W][N]     1 iff no row fails the finalize_solution re-check's comparisons (same
+ *                        strictness: what armour_result.feasible would be for a plan ending at that x)
+ *   best      [W]        lowest-cost feasible candidate, ties to the lowest index, -1 if none
+ * A world whose reach set failed (armour_result.error) gets NaN cost and violations, feasible 0 and
+ * best -1; the other worlds are evaluated and the call returns 0.
+ * ARMOUR_E_STATE before any batch; ARMOUR_E_ARG for a null p or x, num_candidates < 1, any x that is
+ * not finite or lies outside [-1, 1] (the box the collision planes are certified for), an ARMTD
+ * planner, or the fp32 study (ARMOUR_EVAL_F32).
+ * The collision rows are read from the certified plane cache, built on demand.
+ * When a batch with obstacles has no cache (ARMOUR_PLANE_CACHE=0, a batch capacity beyond the cache's
+ * 32-bit record pool, or a build that did not fit a pool that could be allocated) the call returns
+ * ARMOUR_E_STATE and says so: there is no full-scan path. */
+int armour_eval_candidates(armour_planner* p, int num_candidates, const double* x, double* cost, double* violation,
+                           int* feasible, int* best);
+
 /* Outputs of world w of the last batch (the armour_*.out payloads, armour_main.cu:340-398) */
 int armour_get_constraints(armour_planner* p, int w, double* g);              /* m values at k_opt (m_w of world w) */
 int armour_get_link_centers(armour_planner* p, int w, double* centers);       /* [T][NJ][3] sliced at the
