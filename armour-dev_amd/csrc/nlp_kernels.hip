@@ -661,6 +661,163 @@ __global__ __launch_bounds__(EVAL_THREADS) void plane_cache_kernel(NlpDev d) { p
 __global__ __launch_bounds__(EVAL_THREADS) void plane_cache_kernel_mx(NlpDev d) { plane_cache_body<true>(d); }
 
 // ------------------------------------------------------------------------------------------
+// The value path of a point, shared by the three evaluation bodies (eval_body: g and J;
+// eval_trials_body: the values of a line search's trials; cand_rows_body / cand_finish_body: the
+// reductions of a caller's candidates). They agree bitwise because they run this code.
+
+// The valid monomials of (world, t) = jt into LDS, enumerated compactly (one load round per
+// thread): u < L are link monomials, the rest torque monomials; prefix offsets from the per-PZ
+// counts lcnt / tcnt, which the caller has staged (and synchronised) before.
+// The text is a macro over the names d, jt, NJ, lcnt, tcnt, lh, lco, th, tco so that eval_body can
+// expand it in place: as a call, eval_kernel_small (held to 63 VGPRs, with spills) keeps its
+// registers, scratch and occupancy but comes out of the register allocator over 1 % slower
+// (DESIGN.md section 4). TRAJ_COST_BODY below likewise.
+#define STAGE_MONOMIALS_BODY                                                                        \
+    int lpre[MAX_J + 1], tpre[NF + 1];                                                              \
+    lpre[0] = 0;                                                                                    \
+    _Pragma("unroll") for (int l = 0; l < MAX_J; l++) lpre[l + 1] = lpre[l] + (l < NJ ? lcnt[l] : 0); \
+    tpre[0] = 0;                                                                                    \
+    _Pragma("unroll") for (int j = 0; j < NF; j++) tpre[j + 1] = tpre[j] + tcnt[j];                 \
+    const int L = lpre[MAX_J], M = tpre[NF];                                                        \
+    for (int u = threadIdx.x; u < L + M; u += blockDim.x) {                                         \
+        if (u < L) {                                                                                \
+            int l = 0, q0 = 0;                                                                      \
+            _Pragma("unroll") for (int k = 1; k < MAX_J; k++) if (u >= lpre[k]) { l = k; q0 = lpre[k]; } \
+            const int q = u - q0;                                                                   \
+            const long b = (jt * NJ + l) * CAP_LM + q;                                              \
+            lh[l][q] = d.ro.link_hash[b];                                                           \
+            lco[l][q][0] = d.ro.link_coef[b * 3];                                                   \
+            lco[l][q][1] = d.ro.link_coef[b * 3 + 1];                                               \
+            lco[l][q][2] = d.ro.link_coef[b * 3 + 2];                                               \
+        } else {                                                                                    \
+            const int v = u - L;                                                                    \
+            int j = 0, q0 = 0;                                                                      \
+            _Pragma("unroll") for (int k = 1; k < NF; k++) if (v >= tpre[k]) { j = k; q0 = tpre[k]; } \
+            const int q = v - q0;                                                                   \
+            const long b = (jt * NF + j) * CAP_UM + q;                                              \
+            th[j][q] = d.ro.tq_hash[b];                                                             \
+            tco[j][q] = d.ro.tq_coef[b];                                                            \
+        }                                                                                           \
+    }
+template <typename R, int LM, int UM>
+__device__ __attribute__((always_inline)) void stage_monomials(const NlpDev& d, long jt, int NJ, const int* lcnt,
+                                                               const int* tcnt, uint16_t (*lh)[LM], R (*lco)[LM][3],
+                                                               uint16_t (*th)[UM], R (*tco)[UM]) {
+    STAGE_MONOMIALS_BODY
+}
+
+// c + term(0) + ... + term(cnt - 1), summed in monomial order with four independent products in
+// flight: four terms are formed before the first of their adds
+template <typename R, typename F>
+__device__ __attribute__((always_inline)) R sum4(R c, int cnt, F term) {
+    int q = 0;
+    for (; q + 4 <= cnt; q += 4) {
+        const R v0 = term(q), v1 = term(q + 1), v2 = term(q + 2), v3 = term(q + 3);
+        c = c + v0; c = c + v1; c = c + v2; c = c + v3;
+    }
+    for (; q < cnt; q++) c = c + term(q);
+    return c;
+}
+// getCenter(Interval(c - r, c + r)), the value of a sliced PZ (the product is fp64 for a float R too)
+template <typename R>
+__device__ __attribute__((always_inline)) double interval_mid(R c, R r) { return ((c - r) + (c + r)) * 0.5; }
+
+// pw[g] = x^g, g = 0..3: the factors of a value slice (1.0 for a skipped factor, slice_term)
+template <typename R>
+__device__ __attribute__((always_inline)) void power_table(R xj, R* pw) {
+    pw[0] = (R)1.0; pw[1] = xj; pw[2] = xj * xj; pw[3] = xj * xj * xj;
+}
+// one monomial's contribution to a value slice: slice_term's k = 0, from a point's [NF][4] powers
+__device__ __attribute__((always_inline)) double value_term(double co, int h, const double (*pw)[4]) {
+    double v = co;
+#pragma unroll
+    for (int j = 0; j < NF; j++) v = v * pw[j][(h >> (2 * j)) & 3];
+    return v;
+}
+
+// a world's start state, as the extremum rows and the cost read it
+struct TrajStart {
+    const double *q0, *qd0, *qdd0;
+    double D;  // the trajectory's duration
+};
+__device__ __attribute__((always_inline)) TrajStart traj_start(const NlpDev& d, int w) {
+    return {d.q0 + w * NF, d.qd0 + w * NF, d.qdd0 + w * NF, d.rp->duration};
+}
+// the extremum rows of (kind, joint j) at x_j (NLPclass.cu:319-320, 390-391): the minimum and the
+// maximum over the trajectory in row units, and what extremum_grad needs for their derivatives
+struct ExtremumRows {
+    double mn, mx, scale, e2, e3;
+    int mnid, mxid;
+};
+__device__ __attribute__((always_inline)) ExtremumRows extremum_rows(const RobotParams& rp, TrajStart s, int kind,
+                                                                     int j, double xj) {
+    ExtremumRows r;
+    double mn, mx;
+    extremum(kind, s.q0[j], s.qd0[j] * s.D, s.qdd0[j] * s.D * s.D, rp.k_range[j] * xj, &mn, &mx, &r.mnid, &r.mxid, &r.e2, &r.e3);
+    r.scale = kind == 0 ? 1.0 : s.D;
+    r.mn = mn / r.scale;
+    r.mx = mx / r.scale;
+    return r;
+}
+// cost (NLPclass.cu:207-267) before rp.cost_scale, fv: the squared distance of qp = q(t_plan) from
+// the goal, wrapped joints summed first (NLPclass.cu:225-233). Over the names d, rp, ts, w, x, tp, qp
+#define TRAJ_COST_BODY                                                                              \
+    for (int j = 0; j < NF; j++)                                                                    \
+        qp[j] = bz_q(ts.q0[j], ts.qd0[j] * ts.D, ts.qdd0[j] * ts.D * ts.D, rp.k_range[j] * x[j], tp); \
+    double fv = 0.0;                                                                                \
+    bool first = true;                                                                              \
+    for (int pass = 1; pass >= 0; pass--)                                                           \
+        for (int j = 0; j < NF; j++) {                                                              \
+            if (rp.wrap_mask[j] != pass) continue;                                                  \
+            const double dd = pass ? wrap_to_pi(d.qdes[w * NF + j] - qp[j]) : (d.qdes[w * NF + j] - qp[j]); \
+            const double term = dd * dd;                                                            \
+            fv = first ? term : fv + term;                                                          \
+            first = false;                                                                          \
+        }
+__device__ __attribute__((always_inline)) double traj_cost(const NlpDev& d, const RobotParams& rp, TrajStart ts, int w,
+                                                           const double* x, double* qp) {
+    const double tp = rp.t_plan;
+    TRAJ_COST_BODY
+    return fv;
+}
+
+// the certified records of block (world, t) = jt (plane_cache_body): [5][total] doubles (A, d + delta,
+// -d + delta) and each record's pair. NP: the world's pairs. some = false for a world without
+// obstacles in a mixed batch: no records, and its pcoff entries are not read
+struct PlaneRecords {
+    const double* rec;
+    const uint16_t* pcp;
+    int total;
+};
+__device__ __attribute__((always_inline)) PlaneRecords plane_records(const NlpDev& d, long jt, int NP, bool some = true) {
+    const unsigned last = some ? d.pcoff[jt * (d.NJ * d.O) + NP - 1] : 0u;
+    const unsigned long long pb = d.pcbase[jt];
+    return {d.pc + 5 * pb, d.pcp + pb, (int)(last >> 8) + (int)(last & 255)};
+}
+struct PlaneRecord {
+    double a[3], P, N;
+    int pr;  // pair (link * O + obstacle)
+};
+__device__ __attribute__((always_inline)) PlaneRecord load_record(PlaneRecords pc, int q) {
+    const int cap = pc.total;
+    return {{pc.rec[q], pc.rec[cap + q], pc.rec[2 * cap + q]}, pc.rec[3 * cap + q], pc.rec[4 * cap + q], pc.pcp[q]};
+}
+// a record's candidate at the point whose sliced link centre is lc: A . c - P before -A . c - N, as
+// the serial scan — neg only when it beats pos (or pos is NaN)
+__device__ __attribute__((always_inline)) double record_candidate(PlaneRecord r, const double* lc, bool& neg) {
+    const double Ac = r.a[0] * lc[0] + r.a[1] * lc[1] + r.a[2] * lc[2];
+    const double pos = Ac - r.P, nv = -Ac - r.N;
+    neg = nv > pos || pos != pos;
+    return neg ? nv : pos;
+}
+// the scans start every pair at -1e8, as the reference's: a candidate counts only above it (NaN
+// never); the pair's maximum by an LDS atomicMax on its order-preserving key
+constexpr double SCAN_START = -100000000.0;
+__device__ __attribute__((always_inline)) void pair_max(unsigned long long* key, double v) {
+    if (v > SCAN_START) atomicMax(key, okey(v));
+}
+
+// ------------------------------------------------------------------------------------------
 // g(x) and dense Jacobian, grid (T, W). mode 0: ws.x into slot 0 (start point,
 // armour_eval_constraints); mode 1: the line-search trial ws.xt into the non-current slot (worlds
 // still searching only). The sliced link centres go to the slot's own region (feasible_kernel
@@ -736,7 +893,7 @@ __device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mo
         const double xd = mode == 0 ? S.x[tid] : S.xt[tid];
         x[tid] = xd;
         const R xj = (R)xd;
-        ptab[tid][0] = (R)1.0; ptab[tid][1] = xj; ptab[tid][2] = xj * xj; ptab[tid][3] = xj * xj * xj;
+        power_table(xj, ptab[tid]);
         ptab[tid][4] = (R)0.0; ptab[tid][5] = (R)1.0 * (R)1.0; ptab[tid][6] = (R)2.0 * xj; ptab[tid][7] = (R)3.0 * (xj * xj);
     }
     if (tid < NJ) lcnt[tid] = d.ro.link_cnt[jt * NJ + tid];
@@ -748,38 +905,7 @@ __device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mo
     __syncthreads();
     EVP_MARK
     if (!(d.diag & 1)) {
-        // only the valid monomials, enumerated compactly (one load round per thread): u < L are
-        // link monomials, the rest torque monomials; prefix offsets from the per-PZ counts
-        int lpre[MAX_J + 1], tpre[NF + 1];
-        lpre[0] = 0;
-#pragma unroll
-        for (int l = 0; l < MAX_J; l++) lpre[l + 1] = lpre[l] + (l < NJ ? lcnt[l] : 0);
-        tpre[0] = 0;
-#pragma unroll
-        for (int j = 0; j < NF; j++) tpre[j + 1] = tpre[j] + tcnt[j];
-        const int L = lpre[MAX_J], M = tpre[NF];
-        for (int u = tid; u < L + M; u += blockDim.x) {
-            if (u < L) {
-                int l = 0, q0 = 0;
-#pragma unroll
-                for (int k = 1; k < MAX_J; k++) if (u >= lpre[k]) { l = k; q0 = lpre[k]; }
-                const int q = u - q0;
-                const long b = (jt * NJ + l) * CAP_LM + q;
-                lh[l][q] = d.ro.link_hash[b];
-                lco[l][q][0] = d.ro.link_coef[b * 3];
-                lco[l][q][1] = d.ro.link_coef[b * 3 + 1];
-                lco[l][q][2] = d.ro.link_coef[b * 3 + 2];
-            } else {
-                const int v = u - L;
-                int j = 0, q0 = 0;
-#pragma unroll
-                for (int k = 1; k < NF; k++) if (v >= tpre[k]) { j = k; q0 = tpre[k]; }
-                const int q = v - q0;
-                const long b = (jt * NF + j) * CAP_UM + q;
-                th[j][q] = d.ro.tq_hash[b];
-                tco[j][q] = d.ro.tq_coef[b];
-            }
-        }
+        STAGE_MONOMIALS_BODY
     }
     __syncthreads();
     EVP_MARK
@@ -795,20 +921,10 @@ __device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mo
         const int l = ul / 24, e = (ul / 8) % 3, k = ul % 8;
         const long base = jt * NJ + l;
         R c = k == 0 ? d.ro.link_center[base * 3 + e] : 0.0;
-        const int cnt = lcnt[l];
-        // four independent products in flight, summed in monomial order
-        int q = 0;
-        for (; q + 4 <= cnt; q += 4) {
-            const R v0 = slice_term(lco[l][q][e], lh[l][q], k, ptab);
-            const R v1 = slice_term(lco[l][q + 1][e], lh[l][q + 1], k, ptab);
-            const R v2 = slice_term(lco[l][q + 2][e], lh[l][q + 2], k, ptab);
-            const R v3 = slice_term(lco[l][q + 3][e], lh[l][q + 3], k, ptab);
-            c = c + v0; c = c + v1; c = c + v2; c = c + v3;
-        }
-        for (; q < cnt; q++) c = c + slice_term(lco[l][q][e], lh[l][q], k, ptab);
+        c = sum4(c, lcnt[l], [&](int q) { return slice_term(lco[l][q][e], lh[l][q], k, ptab); });
         if (k == 0) {
             const R r = d.ro.link_rad[base * 3 + e];
-            const R cc = ((c - r) + (c + r)) * 0.5;  // getCenter(Interval(c - r, c + r))
+            const R cc = interval_mid(c, r);
             lc[l][e] = cc;
             Lcb[((long)t * NJ + l) * 3 + e] = cc;
         } else {
@@ -821,20 +937,11 @@ __device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mo
         const int j = u / 8, k = u % 8;
         const long base = jt * NF + j;
         R c = k == 0 ? d.ro.tq_center[base] : 0.0;
-        const int cnt = tcnt[j];
-        int q = 0;
-        for (; q + 4 <= cnt; q += 4) {
-            const R v0 = slice_term(tco[j][q], th[j][q], k, ptab);
-            const R v1 = slice_term(tco[j][q + 1], th[j][q + 1], k, ptab);
-            const R v2 = slice_term(tco[j][q + 2], th[j][q + 2], k, ptab);
-            const R v3 = slice_term(tco[j][q + 3], th[j][q + 3], k, ptab);
-            c = c + v0; c = c + v1; c = c + v2; c = c + v3;
-        }
-        for (; q < cnt; q++) c = c + slice_term(tco[j][q], th[j][q], k, ptab);
+        c = sum4(c, tcnt[j], [&](int q) { return slice_term(tco[j][q], th[j][q], k, ptab); });
         const long gi = (long)t * NF + j;
         if (k == 0) {
             const R r = d.ro.tq_rad[base];
-            Gb[gi] = ((c - r) + (c + r)) * 0.5;
+            Gb[gi] = interval_mid(c, r);
         } else {
             Jb[gi * NF + k - 1] = c;
         }
@@ -845,45 +952,26 @@ __device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mo
     } else if (t == 0 && tid >= (int)blockDim.x - 2 * NF - 1) {
         // extremum rows (NLPclass.cu:319-320, 390-391), one thread per (kind, joint), and the cost
         // (NLPclass.cu:207-267) on one more thread
-        const double* q0 = d.q0 + w * NF;
-        const double* qd0 = d.qd0 + w * NF;
-        const double* qdd0 = d.qdd0 + w * NF;
-        const double D = rp.duration;
+        const TrajStart ts = traj_start(d, w);
         const int v = tid - ((int)blockDim.x - 2 * NF - 1);
         if (v < 2 * NF) {
             const long off2 = (long)NF * d.T + (long)d.T * d.NJ * O;
             const int kind = v / NF, i = v % NF;
-            const double Tq = qd0[i] * D, TTq = qdd0[i] * D * D;
-            const double ka = rp.k_range[i] * x[i];
-            double mn, mx, e2, e3;
-            int mnid, mxid;
-            extremum(kind, q0[i], Tq, TTq, ka, &mn, &mx, &mnid, &mxid, &e2, &e3);
-            const double scale = kind == 0 ? 1.0 : D;
+            const ExtremumRows er = extremum_rows(rp, ts, kind, i, x[i]);
             const long gmin = off2 + kind * 2 * NF + i, gmax = gmin + NF;
-            Gb[gmin] = mn / scale;
-            Gb[gmax] = mx / scale;
-            const double gmn = extremum_grad(kind, mnid, e2, e3) * rp.k_range[i] / scale;
-            const double gmx = extremum_grad(kind, mxid, e2, e3) * rp.k_range[i] / scale;
+            Gb[gmin] = er.mn;
+            Gb[gmax] = er.mx;
+            const double gmn = extremum_grad(kind, er.mnid, er.e2, er.e3) * rp.k_range[i] / er.scale;
+            const double gmx = extremum_grad(kind, er.mxid, er.e2, er.e3) * rp.k_range[i] / er.scale;
 #pragma unroll
             for (int k = 0; k < NF; k++) {
                 Jb[gmin * NF + k] = (k == i) ? gmn : 0.0;
                 Jb[gmax * NF + k] = (k == i) ? gmx : 0.0;
             }
         } else {
-            // cost: wrapped joints summed first (NLPclass.cu:225-233)
             const double tp = rp.t_plan;
             double qp[NF];
-            for (int i = 0; i < NF; i++) qp[i] = bz_q(q0[i], qd0[i] * D, qdd0[i] * D * D, rp.k_range[i] * x[i], tp);
-            double fv = 0.0;
-            bool first = true;
-            for (int pass = 1; pass >= 0; pass--)
-                for (int i = 0; i < NF; i++) {
-                    if (rp.wrap_mask[i] != pass) continue;
-                    const double dd = pass ? wrap_to_pi(d.qdes[w * NF + i] - qp[i]) : (d.qdes[w * NF + i] - qp[i]);
-                    const double term = dd * dd;
-                    fv = first ? term : fv + term;
-                    first = false;
-                }
+            TRAJ_COST_BODY
             *fb = fv * rp.cost_scale;
             for (int i = 0; i < NF; i++) {
                 const double dk = tp * tp * tp * (6 * tp * tp - 15 * tp + 10) * rp.k_range[i];
@@ -925,18 +1013,14 @@ __device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mo
             // strict-> first maximum, value, plane and sign exactly. The pair tables live in the
             // slicing buffer (free now).
             const int NP = NJ * O;
-            const unsigned last = d.pcoff[jt * (NJ * OS) + NP - 1];
-            const int total = (int)(last >> 8) + (int)(last & 255);
-            const unsigned long long pb = d.pcbase[jt];
-            const double* const rec = d.pc + 5 * pb;
-            const uint16_t* const pcp = d.pcp + pb;
-            const int cap = total;  // the block's [5][n] record arrays
+            const PlaneRecords pc = plane_records(d, jt, NP);
+            const int total = pc.total;
             // eval_pair_doubles(NP) <= UB: always for UB_FULL, checked by the host for UB_S
             unsigned long long* const pkey = reinterpret_cast<unsigned long long*>(ubuf);  // [NP]
             unsigned* const pidx = reinterpret_cast<unsigned*>(ubuf + NP);                   // [NP]
             double* const pB = ubuf + NP + (NP + 1) / 2;                                     // [NP][4]: A, value
             static_assert(eval_pair_doubles(MAX_J * MAX_OBS) <= UB_FULL, "pair tables");
-            const double start = -100000000.0;
+            const double start = SCAN_START;
             for (int pr = tid; pr < NP; pr += blockDim.x) {
                 pkey[pr] = okey(start);
                 pidx[pr] = 0xFFFFFFFFu;
@@ -944,16 +1028,12 @@ __device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mo
             __syncthreads();
             EVP_MARK
             auto cand = [&](int q, double& v, int& sub, int& pr, double* a) {
-                a[0] = rec[q];
-                a[1] = rec[cap + q];
-                a[2] = rec[2 * cap + q];
-                const double P = rec[3 * cap + q], N = rec[4 * cap + q];
-                pr = pcp[q];
-                const int l = pr / O;
-                const double Ac = a[0] * lc[l][0] + a[1] * lc[l][1] + a[2] * lc[l][2];
-                const double pos = Ac - P, neg = -Ac - N;
-                sub = (neg > pos || pos != pos) ? 1 : 0;  // the serial scan takes neg only when it beats pos
-                v = sub ? neg : pos;
+                const PlaneRecord r = load_record(pc, q);
+                a[0] = r.a[0]; a[1] = r.a[1]; a[2] = r.a[2];
+                pr = r.pr;
+                bool neg;
+                v = record_candidate(r, lc[pr / O], neg);
+                sub = neg ? 1 : 0;
             };
             constexpr int RPT = 3;
             if (total <= RPT * EVAL_THREADS) {
@@ -967,7 +1047,7 @@ __device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mo
                     pq[s] = 0;
                     if (q < total) {
                         cand(q, v[s], sub[s], pq[s], a[s]);
-                        if (v[s] > start) atomicMax(&pkey[pq[s]], okey(v[s]));
+                        pair_max(&pkey[pq[s]], v[s]);
                     }
                 }
                 __syncthreads();
@@ -992,7 +1072,7 @@ __device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mo
                     double v, a[3];
                     int sub, pr;
                     cand(q, v, sub, pr, a);
-                    if (v > start) atomicMax(&pkey[pr], okey(v));
+                    pair_max(&pkey[pr], v);
                 }
                 __syncthreads();
                 EVP_MARK
@@ -1209,8 +1289,8 @@ template __global__ void eval_kernel_mx<true>(NlpDev, int);
 // ipm_world_C's sequential rounds would visit) — the constraint values and the cost, all the
 // acceptance test reads (ipm_rows_Cs / ipm_world_Cs); the Jacobian is formed only for the trial
 // chosen, by a full evaluation (eval_kernel_t mode 5). The monomials are staged and each
-// certified-plane record is loaded once for all K points; every value is formed with
-// eval_kernel_t's arithmetic.
+// certified-plane record is loaded once for all K points; every value is formed by the functions
+// eval_body forms it with (sum4 over value_term, extremum_rows, traj_cost, record_candidate).
 // LM, UM, UB as eval_body; the staging buffer then holds the (trial, pair) keys, K * NP <= UB
 constexpr int UB_TS = EV_MAXK * 280;   // small variant: 9 trials of up to 280 pairs (7 links x 40 obstacles)
 static_assert(UB_TS >= MAX_J * LM_S * 3 + NF * UM_S, "small trials staging buffer");
@@ -1246,83 +1326,29 @@ __device__ __attribute__((always_inline)) void eval_trials_body(const NlpDev& d)
         for (int q = 0; q < kk; q++) a *= 0.5;
         const double xj = S.x[j] + a * S.dx[j];
         xk[kk][j] = xj;
-        ptab[kk][j][0] = 1.0; ptab[kk][j][1] = xj; ptab[kk][j][2] = xj * xj; ptab[kk][j][3] = xj * xj * xj;
+        power_table(xj, ptab[kk][j]);
     }
     if (tid >= 64 && tid < 64 + NJ) lcnt[tid - 64] = d.ro.link_cnt[jt * NJ + tid - 64];
     if (tid >= 96 && tid < 96 + NF) tcnt[tid - 96] = d.nt ? d.ro.tq_cnt[jt * NF + tid - 96] : 0;
     __syncthreads();
     EVP_MARK
-    {
-        int lpre[MAX_J + 1], tpre[NF + 1];
-        lpre[0] = 0;
-#pragma unroll
-        for (int l = 0; l < MAX_J; l++) lpre[l + 1] = lpre[l] + (l < NJ ? lcnt[l] : 0);
-        tpre[0] = 0;
-#pragma unroll
-        for (int j = 0; j < NF; j++) tpre[j + 1] = tpre[j] + tcnt[j];
-        const int L = lpre[MAX_J], M = tpre[NF];
-        for (int u = tid; u < L + M; u += blockDim.x) {
-            if (u < L) {
-                int l = 0, q0 = 0;
-#pragma unroll
-                for (int k = 1; k < MAX_J; k++) if (u >= lpre[k]) { l = k; q0 = lpre[k]; }
-                const int q = u - q0;
-                const long b = (jt * NJ + l) * CAP_LM + q;
-                lh[l][q] = d.ro.link_hash[b];
-                lco[l][q][0] = d.ro.link_coef[b * 3];
-                lco[l][q][1] = d.ro.link_coef[b * 3 + 1];
-                lco[l][q][2] = d.ro.link_coef[b * 3 + 2];
-            } else {
-                const int v = u - L;
-                int j = 0, q0 = 0;
-#pragma unroll
-                for (int k = 1; k < NF; k++) if (v >= tpre[k]) { j = k; q0 = tpre[k]; }
-                const int q = v - q0;
-                const long b = (jt * NF + j) * CAP_UM + q;
-                th[j][q] = d.ro.tq_hash[b];
-                tco[j][q] = d.ro.tq_coef[b];
-            }
-        }
-    }
+    stage_monomials<double, LM, UM>(d, jt, NJ, lcnt, tcnt, lh, lco, th, tco);
     __syncthreads();
     EVP_MARK
     // value slices of every trial: link centres (k, l, e) and torque rows (k, j), monomial order
-    auto vterm = [&](double co, int h, int kk) {
-        double v = co;
-#pragma unroll
-        for (int j = 0; j < NF; j++) v = v * ptab[kk][j][(h >> (2 * j)) & 3];
-        return v;
-    };
     const int nlv = K * NJ * 3, ntv = d.nt ? K * NF : 0;
     for (int u = tid; u < nlv + ntv; u += blockDim.x) {
         if (u < nlv) {
             const int kk = u / (NJ * 3), l = (u / 3) % NJ, e = u % 3;
             const long base = jt * NJ + l;
-            double c = d.ro.link_center[base * 3 + e];
-            const int cnt = lcnt[l];
-            int q = 0;
-            for (; q + 4 <= cnt; q += 4) {
-                const double v0 = vterm(lco[l][q][e], lh[l][q], kk), v1 = vterm(lco[l][q + 1][e], lh[l][q + 1], kk);
-                const double v2 = vterm(lco[l][q + 2][e], lh[l][q + 2], kk), v3 = vterm(lco[l][q + 3][e], lh[l][q + 3], kk);
-                c = c + v0; c = c + v1; c = c + v2; c = c + v3;
-            }
-            for (; q < cnt; q++) c = c + vterm(lco[l][q][e], lh[l][q], kk);
-            const double r = d.ro.link_rad[base * 3 + e];
-            lck[kk][l][e] = ((c - r) + (c + r)) * 0.5;  // getCenter(Interval(c - r, c + r))
+            const double c = sum4(d.ro.link_center[base * 3 + e], lcnt[l],
+                                  [&](int q) { return value_term(lco[l][q][e], lh[l][q], ptab[kk]); });
+            lck[kk][l][e] = interval_mid(c, d.ro.link_rad[base * 3 + e]);
         } else {
             const int v = u - nlv, kk = v / NF, j = v % NF;
             const long base = jt * NF + j;
-            double c = d.ro.tq_center[base];
-            const int cnt = tcnt[j];
-            int q = 0;
-            for (; q + 4 <= cnt; q += 4) {
-                const double v0 = vterm(tco[j][q], th[j][q], kk), v1 = vterm(tco[j][q + 1], th[j][q + 1], kk);
-                const double v2 = vterm(tco[j][q + 2], th[j][q + 2], kk), v3 = vterm(tco[j][q + 3], th[j][q + 3], kk);
-                c = c + v0; c = c + v1; c = c + v2; c = c + v3;
-            }
-            for (; q < cnt; q++) c = c + vterm(tco[j][q], th[j][q], kk);
-            const double r = d.ro.tq_rad[base];
-            d.gs[((long)i * K + kk) * d.m + (long)t * NF + j] = ((c - r) + (c + r)) * 0.5;
+            const double c = sum4(d.ro.tq_center[base], tcnt[j], [&](int q) { return value_term(tco[j][q], th[j][q], ptab[kk]); });
+            d.gs[((long)i * K + kk) * d.m + (long)t * NF + j] = interval_mid(c, d.ro.tq_rad[base]);
         }
     }
     // extremum rows (NLPclass.cu:319-320, 390-391) and cost (NLPclass.cu:207-267) of every trial:
@@ -1334,36 +1360,18 @@ __device__ __attribute__((always_inline)) void eval_trials_body(const NlpDev& d)
         const int kk = tid - ((int)blockDim.x - K);
         const double* x = xk[kk];
         double* const Gb = d.gs + ((long)i * K + kk) * d.m;
-        const double* q0 = d.q0 + w * NF;
-        const double* qd0 = d.qd0 + w * NF;
-        const double* qdd0 = d.qdd0 + w * NF;
-        const double D = rp.duration;
+        const TrajStart ts = traj_start(d, w);
         if (v < 2 * NF) {
             const long off2 = (long)NF * d.T + (long)d.T * d.NJ * O;
             const int kind = v / NF, j = v % NF;
-            double mn, mx, e2, e3;
-            int mnid, mxid;
-            extremum(kind, q0[j], qd0[j] * D, qdd0[j] * D * D, rp.k_range[j] * x[j], &mn, &mx, &mnid, &mxid, &e2, &e3);
-            const double scale = kind == 0 ? 1.0 : D;
+            const ExtremumRows er = extremum_rows(rp, ts, kind, j, x[j]);
             const long rmin = off2 + kind * 2 * NF + j;
-            Gb[rmin] = mn / scale;
-            Gb[rmin + NF] = mx / scale;
+            Gb[rmin] = er.mn;
+            Gb[rmin + NF] = er.mx;
             continue;
         }
-        const double tp = rp.t_plan;
         double qp[NF];
-        for (int j = 0; j < NF; j++) qp[j] = bz_q(q0[j], qd0[j] * D, qdd0[j] * D * D, rp.k_range[j] * x[j], tp);
-        double fv = 0.0;
-        bool first = true;
-        for (int pass = 1; pass >= 0; pass--)
-            for (int j = 0; j < NF; j++) {
-                if (rp.wrap_mask[j] != pass) continue;
-                const double dd = pass ? wrap_to_pi(d.qdes[w * NF + j] - qp[j]) : (d.qdes[w * NF + j] - qp[j]);
-                const double term = dd * dd;
-                fv = first ? term : fv + term;
-                first = false;
-            }
-        d.fs[(long)i * K + kk] = fv * rp.cost_scale;
+        d.fs[(long)i * K + kk] = traj_cost(d, rp, ts, w, x, qp) * rp.cost_scale;
     }
     __syncthreads();
     EVP_MARK
@@ -1374,27 +1382,18 @@ __device__ __attribute__((always_inline)) void eval_trials_body(const NlpDev& d)
     // (Measured slower: one thread per pair scanning its records, 2x in the solver's tail: a pair's
     // records are a dependent chain of loads on one lane; and each thread reducing four consecutive
     // records before its atomics, strided loads.)
-    const unsigned last = NP > 0 ? d.pcoff[jt * (NJ * d.O) + NP - 1] : 0u;
-    const int total = (int)(last >> 8) + (int)(last & 255);
-    const unsigned long long pb = d.pcbase[jt];
-    const double* const rec = d.pc + 5 * pb;
-    const uint16_t* const pcp = d.pcp + pb;
-    const int cap = total;  // the block's [5][n] record arrays
+    const PlaneRecords pc = plane_records(d, jt, NP, NP > 0);
     unsigned long long* const pkey = reinterpret_cast<unsigned long long*>(ubuf);  // [K][NP]
     static_assert(EV_MAXK * MAX_J * MAX_OBS <= UB_FULL, "trial pair table");  // K * NP <= UB_TS: host check
-    const double start = -100000000.0;
-    for (int u = tid; u < K * NP; u += blockDim.x) pkey[u] = okey(start);
+    for (int u = tid; u < K * NP; u += blockDim.x) pkey[u] = okey(SCAN_START);
     __syncthreads();
     EVP_MARK
-    for (int q = tid; q < total; q += blockDim.x) {
-        const double a0 = rec[q], a1 = rec[cap + q], a2 = rec[2 * cap + q];
-        const double P = rec[3 * cap + q], N = rec[4 * cap + q];
-        const int pr = pcp[q], l = pr / O;
+    for (int q = tid; q < pc.total; q += blockDim.x) {
+        const PlaneRecord r = load_record(pc, q);
+        const int l = r.pr / O;
         for (int kk = 0; kk < K; kk++) {
-            const double Ac = a0 * lck[kk][l][0] + a1 * lck[kk][l][1] + a2 * lck[kk][l][2];
-            const double pos = Ac - P, neg = -Ac - N;
-            const double v = (neg > pos || pos != pos) ? neg : pos;
-            if (v > start) atomicMax(&pkey[kk * NP + pr], okey(v));
+            bool neg;
+            pair_max(&pkey[kk * NP + r.pr], record_candidate(r, lck[kk][l], neg));
         }
     }
     __syncthreads();
@@ -2909,9 +2908,9 @@ __global__ void feasible_kernel_mx(NlpDev d, int* feasible) { feasible_body<true
 // the cost, the largest excess per row class and finalize_solution's verdict; g is never stored.
 //
 // cand_rows, grid (T, W, ceil(N / CAND_KC)): block (t, w, chunk) stages the (world, t) monomials
-// once (as eval_trials_body), slices the link centres and torque rows of its CAND_KC candidates with
-// eval_kernel_t's arithmetic and term order, and scans the block's certified-plane records once for
-// the whole chunk. Mapping of the scan: record-parallel, as eval_trials_body's. A thread takes
+// once (stage_monomials), slices the link centres and torque rows of its CAND_KC candidates (sum4
+// over value_term: eval_body's terms in its order), and scans the block's certified-plane records
+// once for the whole chunk (load_record, record_candidate). Mapping of the scan: record-parallel, as eval_trials_body's. A thread takes
 // records tid, tid + 256, ... (coalesced loads, every record read by one thread) and forms the two
 // candidates of each of the chunk's points from the sliced centres in LDS; the (point, pair)
 // maximum is an LDS atomicMax on an order-preserving key, in the staging buffer, in passes of as
@@ -2975,83 +2974,29 @@ __device__ __attribute__((always_inline)) void cand_rows_body(const NlpDev& d, c
     if (tid < KC * NF) {
         const int kk = tid / NF, j = tid % NF;
         const double xj = kk < KN ? c.x[((long)w * c.N + n0 + kk) * NF + j] : 0.0;
-        ptab[kk][j][0] = 1.0; ptab[kk][j][1] = xj; ptab[kk][j][2] = xj * xj; ptab[kk][j][3] = xj * xj * xj;
+        power_table(xj, ptab[kk][j]);
     }
     if (tid >= 128 && tid < 128 + NJ) lcnt[tid - 128] = min(d.ro.link_cnt[jt * NJ + tid - 128], LM);
     if (tid >= 160 && tid < 160 + NF) tcnt[tid - 160] = min(d.ro.tq_cnt[jt * NF + tid - 160], UM);
     __syncthreads();
-    {
-        int lpre[MAX_J + 1], tpre[NF + 1];
-        lpre[0] = 0;
-#pragma unroll
-        for (int l = 0; l < MAX_J; l++) lpre[l + 1] = lpre[l] + (l < NJ ? lcnt[l] : 0);
-        tpre[0] = 0;
-#pragma unroll
-        for (int j = 0; j < NF; j++) tpre[j + 1] = tpre[j] + tcnt[j];
-        const int L = lpre[MAX_J], M = tpre[NF];
-        for (int u = tid; u < L + M; u += blockDim.x) {
-            if (u < L) {
-                int l = 0, q0 = 0;
-#pragma unroll
-                for (int k = 1; k < MAX_J; k++) if (u >= lpre[k]) { l = k; q0 = lpre[k]; }
-                const int q = u - q0;
-                const long b = (jt * NJ + l) * CAP_LM + q;
-                lh[l][q] = d.ro.link_hash[b];
-                lco[l][q][0] = d.ro.link_coef[b * 3];
-                lco[l][q][1] = d.ro.link_coef[b * 3 + 1];
-                lco[l][q][2] = d.ro.link_coef[b * 3 + 2];
-            } else {
-                const int v = u - L;
-                int j = 0, q0 = 0;
-#pragma unroll
-                for (int k = 1; k < NF; k++) if (v >= tpre[k]) { j = k; q0 = tpre[k]; }
-                const int q = v - q0;
-                const long b = (jt * NF + j) * CAP_UM + q;
-                th[j][q] = d.ro.tq_hash[b];
-                tco[j][q] = d.ro.tq_coef[b];
-            }
-        }
-    }
+    stage_monomials<double, LM, UM>(d, jt, NJ, lcnt, tcnt, lh, lco, th, tco);
     __syncthreads();
     // value slices of every candidate, monomial order: the KN * NF torque rows (the longest sums)
     // first, then the link centres (k, l, e)
-    auto vterm = [&](double co, int h, int kk) {
-        double v = co;
-#pragma unroll
-        for (int j = 0; j < NF; j++) v = v * ptab[kk][j][(h >> (2 * j)) & 3];
-        return v;
-    };
     const int ntv = KN * NF, nlv = KN * NJ * 3;
     for (int u = tid; u < ntv + nlv; u += blockDim.x) {
         if (u >= ntv) {
             const int ul = u - ntv;
             const int kk = ul / (NJ * 3), l = (ul / 3) % NJ, e = ul % 3;
             const long base = jt * NJ + l;
-            double s = d.ro.link_center[base * 3 + e];
-            const int cnt = lcnt[l];
-            int q = 0;
-            for (; q + 4 <= cnt; q += 4) {
-                const double v0 = vterm(lco[l][q][e], lh[l][q], kk), v1 = vterm(lco[l][q + 1][e], lh[l][q + 1], kk);
-                const double v2 = vterm(lco[l][q + 2][e], lh[l][q + 2], kk), v3 = vterm(lco[l][q + 3][e], lh[l][q + 3], kk);
-                s = s + v0; s = s + v1; s = s + v2; s = s + v3;
-            }
-            for (; q < cnt; q++) s = s + vterm(lco[l][q][e], lh[l][q], kk);
-            const double r = d.ro.link_rad[base * 3 + e];
-            lck[kk][l][e] = ((s - r) + (s + r)) * 0.5;  // getCenter(Interval(c - r, c + r))
+            const double s = sum4(d.ro.link_center[base * 3 + e], lcnt[l],
+                                  [&](int q) { return value_term(lco[l][q][e], lh[l][q], ptab[kk]); });
+            lck[kk][l][e] = interval_mid(s, d.ro.link_rad[base * 3 + e]);
         } else {
             const int kk = u / NF, j = u % NF;
             const long base = jt * NF + j;
-            double s = d.ro.tq_center[base];
-            const int cnt = tcnt[j];
-            int q = 0;
-            for (; q + 4 <= cnt; q += 4) {
-                const double v0 = vterm(tco[j][q], th[j][q], kk), v1 = vterm(tco[j][q + 1], th[j][q + 1], kk);
-                const double v2 = vterm(tco[j][q + 2], th[j][q + 2], kk), v3 = vterm(tco[j][q + 3], th[j][q + 3], kk);
-                s = s + v0; s = s + v1; s = s + v2; s = s + v3;
-            }
-            for (; q < cnt; q++) s = s + vterm(tco[j][q], th[j][q], kk);
-            const double r = d.ro.tq_rad[base];
-            const double v = ((s - r) + (s + r)) * 0.5;
+            const double s = sum4(d.ro.tq_center[base], tcnt[j], [&](int q) { return value_term(tco[j][q], th[j][q], ptab[kk]); });
+            const double v = interval_mid(s, d.ro.tq_rad[base]);
             // bounds_of's torque row and feasible_kernel's comparisons
             const double tr = d.ro.torque_radius[base];
             const double Lb = -rp.torque_limits[j] + tr, Ub = rp.torque_limits[j] - tr;
@@ -3067,30 +3012,19 @@ __device__ __attribute__((always_inline)) void cand_rows_body(const NlpDev& d, c
     {
         const int g = tid >> 6, lane = tid & 63;
         const double cv = rp.collision_violation;
-        const double start = -100000000.0;
         unsigned long long* const pkey = reinterpret_cast<unsigned long long*>(ubuf);  // [KP][NP]
-        const long NPS = (long)NJ * d.O;
-        const unsigned last = NP > 0 ? d.pcoff[jt * NPS + NP - 1] : 0u;
-        const int total = (int)(last >> 8) + (int)(last & 255);
-        const unsigned long long pb = NP > 0 ? d.pcbase[jt] : 0ull;
-        const double* const rec = d.pc + 5 * pb;
-        const uint16_t* const pcp = d.pcp + pb;
-        const int cap = total;  // the block's [5][n] record arrays
+        const PlaneRecords pc = NP > 0 ? plane_records(d, jt, NP) : PlaneRecords{nullptr, nullptr, 0};
         const int KP = NP > 0 ? min(KC, UB / NP) : KC;
         for (int k0 = 0; k0 < KN; k0 += KP) {
             const int kp = min(KP, KN - k0);
-            for (int u = tid; u < kp * NP; u += blockDim.x) pkey[u] = okey(start);
+            for (int u = tid; u < kp * NP; u += blockDim.x) pkey[u] = okey(SCAN_START);
             __syncthreads();
-            for (int q = tid; q < total; q += blockDim.x) {
-                const double a0 = rec[q], a1 = rec[cap + q], a2 = rec[2 * cap + q];
-                const double P = rec[3 * cap + q], N = rec[4 * cap + q];
-                const int pr = min((int)pcp[q], NP - 1), l = pr / O;
+            for (int q = tid; q < pc.total; q += blockDim.x) {
+                const PlaneRecord r = load_record(pc, q);
+                const int pr = min(r.pr, NP - 1), l = pr / O;
                 for (int kk = 0; kk < kp; kk++) {
-                    const double* const lc = lck[k0 + kk][l];
-                    const double Ac = a0 * lc[0] + a1 * lc[1] + a2 * lc[2];
-                    const double pos = Ac - P, neg = -Ac - N;
-                    const double v = (neg > pos || pos != pos) ? neg : pos;
-                    if (v > start) atomicMax(&pkey[kk * NP + pr], okey(v));
+                    bool neg;
+                    pair_max(&pkey[kk * NP + pr], record_candidate(r, lck[k0 + kk][l], neg));
                 }
             }
             __syncthreads();
@@ -3159,38 +3093,19 @@ __device__ __attribute__((always_inline)) void cand_finish_body(const NlpDev& d,
         bad |= c.pbad[o * d.T + t];
     }
     const double* x = c.x + o * NF;
-    const double* q0 = d.q0 + w * NF;
-    const double* qd0 = d.qd0 + w * NF;
-    const double* qdd0 = d.qdd0 + w * NF;
-    const double D = rp.duration;
+    const TrajStart ts = traj_start(d, w);
     if (lane < 2 * NF) {
-        // extremum rows (eval_kernel_t's) against bounds_of's limits, feasible_kernel's comparisons
+        // extremum rows (extremum_rows) against bounds_of's limits, feasible_kernel's comparisons
         const int kind = lane / NF, j = lane % NF;
-        double mn, mx, e2, e3;
-        int mnid, mxid;
-        extremum(kind, q0[j], qd0[j] * D, qdd0[j] * D * D, rp.k_range[j] * x[j], &mn, &mx, &mnid, &mxid, &e2, &e3);
-        const double scale = kind == 0 ? 1.0 : D;
-        const double vmn = mn / scale, vmx = mx / scale;
+        const ExtremumRows er = extremum_rows(rp, ts, kind, j, x[j]);
+        const double vmn = er.mn, vmx = er.mx;
         double Lb, Ub;
         bounds_of(d, sh, w, d.nt + d.T * d.NJ * sh.O + kind * 2 * NF + j, Lb, Ub);
         ex = fmax(fmax(Lb - vmn, vmn - Ub), fmax(Lb - vmx, vmx - Ub));
         if (vmn < Lb || vmn > Ub || vmx < Lb || vmx > Ub) bad |= 4;
     } else if (lane == 2 * NF) {
-        // cost: wrapped joints summed first (NLPclass.cu:225-233)
-        const double tp = rp.t_plan;
         double qp[NF];
-        for (int j = 0; j < NF; j++) qp[j] = bz_q(q0[j], qd0[j] * D, qdd0[j] * D * D, rp.k_range[j] * x[j], tp);
-        double fv = 0.0;
-        bool first = true;
-        for (int pass = 1; pass >= 0; pass--)
-            for (int j = 0; j < NF; j++) {
-                if (rp.wrap_mask[j] != pass) continue;
-                const double dd = pass ? wrap_to_pi(d.qdes[w * NF + j] - qp[j]) : (d.qdes[w * NF + j] - qp[j]);
-                const double term = dd * dd;
-                fv = first ? term : fv + term;
-                first = false;
-            }
-        c.cost[o] = (fv * rp.cost_scale) / rp.cost_scale;  // armour_result.cost: f / cost_scale
+        c.cost[o] = (traj_cost(d, rp, ts, w, x, qp) * rp.cost_scale) / rp.cost_scale;  // armour_result.cost: f / cost_scale
     }
     tq = wave_max(tq);
     col = wave_max(col);

@@ -900,6 +900,12 @@ static void launch_eval(armour_planner* p, dim3 grid, const NlpDev& d, int mode,
                              : (d.armtd ? eval_kernel_t<double, true, false> : eval_kernel_t<double, false, false>);
     hipLaunchKernelGGL(k, grid, dim3(EVAL_THREADS), 0, s, d, mode);
 }
+// the values of the K remaining trials of n listed worlds (eval_trials_kernel), from the small-capacity
+// kernel when the (trial, pair) keys fit its buffer too
+static void launch_trials(armour_planner* p, int n, const NlpDev& d) {
+    const bool small = eval_small_fits(p) && d.K * p->NJ * d.O <= UB_TS;
+    hipLaunchKernelGGL(small ? KSEL(eval_trials_small) : KSEL(eval_trials_kernel), dim3(p->T, n), dim3(EVAL_THREADS), 0, p->stream, d);
+}
 
 // The interior-point loop over the nrun worlds listed in the first iteration list (d_lists[0..]):
 // every world there starts an iteration with pass A at its current point (a fresh solve, or a
@@ -1102,10 +1108,7 @@ static int ipm_loop(armour_planner* p, int nrun) {
             NlpDev ds = d;
             ds.wl = Ls[1];
             ds.lcount = d.cnt + 5;
-            if (eval_small_fits(p) && d.K * p->NJ * d.O <= UB_TS)
-                hipLaunchKernelGGL(KSEL(eval_trials_small), dim3(p->T, nrun), dim3(EVAL_THREADS), 0, p->stream, ds);
-            else
-                hipLaunchKernelGGL(KSEL(eval_trials_kernel), dim3(p->T, nrun), dim3(EVAL_THREADS), 0, p->stream, ds);
+            launch_trials(p, nrun, ds);
             hipLaunchKernelGGL(KSEL(ipm_rows_Cs), dim3(d.nblk, nrun * d.K), dim3(ROW_THREADS), 0, p->stream, ds);
             hipLaunchKernelGGL(KSEL(ipm_world_Cs), dim3(nrun), dim3(64), 0, p->stream, ds);
             launch_eval(p, dim3(p->T, nrun), ds, 5);
@@ -1132,10 +1135,7 @@ static int ipm_loop(armour_planner* p, int nrun) {
             // tests in trial order, then the chosen trial in full
             NlpDev ds = d;
             ds.wl = Ls[1];
-            if (eval_small_fits(p) && d.K * p->NJ * d.O <= UB_TS)
-                hipLaunchKernelGGL(KSEL(eval_trials_small), dim3(p->T, nsearch), dim3(EVAL_THREADS), 0, p->stream, ds);
-            else
-                hipLaunchKernelGGL(KSEL(eval_trials_kernel), dim3(p->T, nsearch), dim3(EVAL_THREADS), 0, p->stream, ds);
+            launch_trials(p, nsearch, ds);
             hipLaunchKernelGGL(KSEL(ipm_rows_Cs), dim3(d.nblk, nsearch * d.K), dim3(ROW_THREADS), 0, p->stream, ds);
             hipLaunchKernelGGL(KSEL(ipm_world_Cs), dim3(nsearch), dim3(64), 0, p->stream, ds);
             launch_eval(p, dim3(p->T, nsearch), ds, 5);

@@ -18,6 +18,7 @@ import pytest
 
 import armour_amd as A
 import boundary_worlds as B
+from armour_amd.robots import KINOVA
 from conftest import engine
 from oracle import OraclePlanner
 from test_boundary import load, world
@@ -158,18 +159,33 @@ def test_oracle_parity_at_the_decision_boundary(small):
 
 
 def test_same_value_path_as_the_evaluation(small):
-    """the collision class maximum is bitwise max(g_collision) - cv of armour_eval_constraints"""
+    """every class maximum is bitwise the one formed, in the kernels' own order, from the g of
+    armour_eval_constraints: collision max(g) - cv; torque max((Lb - tv) - v, (v - Ub) - tv) with
+    Lb = -limit + radius, Ub = limit - radius; extremum max(L - v, v - U) over the last 28 rows
+    (minima and maxima of the 7 positions, then of the 7 velocities) against joint_bounds()"""
     T, W, O, worlds = small["T"], small["W"], small["O"], small["worlds"]
     X = candidates(0, 18)   # the same points for every world: [N, 7]
     P = A.Planner(T=T, max_obstacles=O, max_worlds=W)   # a planner of its own: that call resets plan state
     P.reach(worlds)
     out = P.eval_candidates(X)
     cs = B.collision_slice(T, P.NJ, O)
-    want = np.zeros((W, len(X)))
-    for n, x in enumerate(X):
-        for w in range(W):
-            want[w, n] = P.eval_constraints(w, x, jac=False)[cs].max() - CV
-    assert out["violation"][..., 1].tobytes() == want.tobytes()
+    lim = KINOVA.torque_limits
+    jb = P.joint_bounds()   # per joint [L, U] of its position rows, then of its velocity rows
+    Lx = np.concatenate([jb[0:14:2], jb[0:14:2], jb[14:28:2], jb[14:28:2]])
+    Ux = np.concatenate([jb[1:14:2], jb[1:14:2], jb[15:28:2], jb[15:28:2]])
+    want = np.zeros((W, len(X), 3))
+    for w in range(W):
+        tr = P.torque_radius(w)   # [T, 7]
+        Lb, Ub = -lim + tr, lim - tr
+        for n, x in enumerate(X):
+            g = P.eval_constraints(w, x, jac=False)
+            v = g[:7 * T].reshape(T, 7)
+            want[w, n, 0] = np.maximum((Lb - TV) - v, (v - Ub) - TV).max()
+            want[w, n, 1] = g[cs].max() - CV
+            want[w, n, 2] = np.maximum(Lx - g[-28:], g[-28:] - Ux).max()
+    assert out["violation"][..., 1].tobytes() == want[..., 1].tobytes()
+    assert out["violation"][..., 0].tobytes() == want[..., 0].tobytes()
+    assert out["violation"][..., 2].tobytes() == want[..., 2].tobytes()
     P.close()
 
 
