@@ -123,6 +123,9 @@ def lib():
         for name in ("armour_get_constraints", "armour_get_link_centers", "armour_get_link_generators",
                      "armour_get_torque_radius"):
             getattr(L, name).argtypes = [ctypes.c_void_p, ctypes.c_int, _dp]
+        if hasattr(L, "armour_sq_selfcheck"):  # absent from older libraries loaded through ARMOUR_LIB
+            L.armour_sq_selfcheck.argtypes = [ctypes.c_int, ctypes.c_double, ctypes.c_longlong, _dp, ctypes.c_longlong,
+                                              _dp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_longlong)]
         _LIB = L
     return _LIB
 
@@ -136,7 +139,7 @@ ABI_SYMBOLS = ["armour_copy_bandwidth", "armour_create", "armour_create_robot", 
                "armour_create_armtd", "armour_plan_armtd_batch", "armour_reach_armtd_batch",
                "armour_get_plane_cache_stats", "armour_plan", "armour_get_reach_span",
                "armour_plan_batch_mixed", "armour_reach_batch_mixed", "armour_world_num_obstacles",
-               "armour_eval_candidates"]
+               "armour_eval_candidates", "armour_sq_selfcheck"]
 
 
 def default_batch(T: int, device: int = 0, waves: int = 2) -> int:
@@ -154,6 +157,17 @@ def copy_bandwidth(device: int = 0, nbytes: int = 2 << 30, reps: int = 10) -> fl
     if v < 0:
         raise ArmourError(f"armour_copy_bandwidth: {lib().armour_last_error().decode()}")
     return v
+
+
+def sq_selfcheck(thr: float, half_width: int, values=None, device: int = 0):
+    """(S*, valid, mismatches) of armour_sq_selfcheck: the squared form S* of the keep / prune threshold
+    thr as the device finds it, whether the device verified it, and how often sqrt(S) against thr and S
+    against S* decide differently over the doubles within half_width ulps of S* and over `values`"""
+    v = np.ascontiguousarray(values if values is not None else np.zeros(0), dtype=np.float64)
+    s, ok, bad = ctypes.c_double(0), ctypes.c_int(0), ctypes.c_longlong(0)
+    _check(lib().armour_sq_selfcheck(device, float(thr), int(half_width), _ptr(v) if v.size else None, v.size,
+                                     ctypes.byref(s), ctypes.byref(ok), ctypes.byref(bad)))
+    return s.value, bool(ok.value), int(bad.value)
 
 
 def _check(rc):

@@ -66,6 +66,11 @@ struct RobotParams {
     double t_plan;
     // pre-computed RPY rotation matrices of each joint (column-major) and their transposes
     double rpy[MAX_J + 1][9];
+    // simplify_threshold on squared norms (pz_engine.h SqThr), filled in on the device when the
+    // planner is created: the largest S whose square root is <= simplify_threshold, and whether
+    // that was verified with the device's own sqrt (0: the reach kernels decide with sqrt)
+    double simplify_sq;
+    int simplify_sq_valid;
 };
 
 }  // namespace armour

@@ -116,7 +116,9 @@ struct LCtx {
     int* err;              // LDS
     int* occ;              // LDS [4]: largest operator term count, link / torque k-only monomials,
                            // arena coefficient rows in use
-    double thr;
+    double thr;            // simplify_threshold, its squared form and whether that one is verified
+    double thr_sq;         // (pz_engine.h SqThr, from RobotParams)
+    int thr_valid;
     const JrsJoint* jrs;   // this lane's job: jrs[i], i < NF
     unsigned long long* prof;  // optional per-op [cycles, terms] + phase cycles (null: off)
     int nops;
@@ -550,24 +552,25 @@ DI void header_add_one_dim(const LCtx& x, const LH& A, const LH& B, const LH& h,
 
 // pruned amount into both independent parts, kept |sum| into absum (PZsparse.cu:347-349)
 DI void finish_block(const LCtx& x, const LH& h, const double* red, const double* ab, int n) {
-    if (frob_norm(red, n) != 0)
+    if (frob_sq(red, n) != 0)
         for (int v = 0; v < 2; v++)
             for (int e = 0; e < n; e++) ind(x, h, v, e) = ind(x, h, v, e) + red[e];
     for (int e = 0; e < n; e++) abs_(x, h, e) = ab[e];
 }
 
 // ---- group policies (lane form of pz_engine.h PolBlock / PolCrossPP) --------------------------
-template <int NN>
+template <int NN, class D>
 struct LPolBlock {
     static constexpr int NV = NN, NO = NN, NR = 2 * NN;
-    PolBlock<NN> base;
+    PolBlock<NN, D> base;
     DI bool group(const double* s, double* out, double* red) const { return base.group(s, out, red); }
     DI void finish(const LCtx& x, int o, const double* red) const { finish_block(x, x.H[o], red, red + NN, NN); }
 };
 
+template <class D>
 struct LPolCrossPP {
     static constexpr int NV = 6, NO = 3, NR = 15;
-    PolCrossPP base;
+    PolCrossPPT<D> base;
     int a, b;
     DI bool group(const double* s, double* out, double* red) const { return base.group(s, out, red); }
     DI void finish(const LCtx& x, int o, const double* red) const {
@@ -586,20 +589,20 @@ struct LPolCrossPP {
             for (int v = 0; v < 2; v++) {
                 const double ai = ind(x, A, v, ea[p]), bi = ind(x, B, v, fb[p]);
                 pi[v][p] = ai * bi + (r2 * bi + ai * r3);
-                if (frob1(red[p]) != 0) pi[v][p] = pi[v][p] + red[p];
+                if (frob1_sq(red[p]) != 0) pi[v][p] = pi[v][p] + red[p];
             }
         }
         double sred[3];
 #pragma unroll
         for (int e = 0; e < 3; e++) sred[e] = red[9 + e];
-        const bool sadd = frob_norm(sred, 3) != 0;
+        const bool sadd = frob_sq(sred, 3) != 0;
 #pragma unroll
         for (int e = 0; e < 3; e++) {
             cen(x, h, e) = pc[2 * e] - pc[2 * e + 1];
 #pragma unroll
             for (int v = 0; v < 2; v++) {
                 double iv = pi[v][2 * e] + pi[v][2 * e + 1];
-                if (frob1(red[6 + e]) != 0) iv = iv + red[6 + e];
+                if (frob1_sq(red[6 + e]) != 0) iv = iv + red[6 + e];
                 if (sadd) iv = iv + sred[e];
                 ind(x, h, v, e) = iv;
             }
@@ -1020,14 +1023,14 @@ DI void cross_const_finish(const LCtx& x, const LH& h, const LH& A, const CrossC
     double sred[3];
 #pragma unroll
     for (int e = 0; e < 3; e++) sred[e] = red[3 + e];
-    const bool sadd = frob_norm(sred, 3) != 0;
+    const bool sadd = frob_sq(sred, 3) != 0;
 #pragma unroll
     for (int e = 0; e < 3; e++) {
         cen(x, h, e) = cen(x, A, C.iA[e]) * C.sA[e] - cen(x, A, C.iB[e]) * C.sB[e];
 #pragma unroll
         for (int v = 0; v < 2; v++) {
             double iv = ind(x, A, v, C.iA[e]) * fabs(C.sA[e]) + ind(x, A, v, C.iB[e]) * fabs(C.sB[e]);
-            if (frob1(red[e]) != 0) iv = iv + red[e];
+            if (frob1_sq(red[e]) != 0) iv = iv + red[e];
             if (sadd) iv = iv + sred[e];
             ind(x, h, v, e) = iv;
         }
@@ -1045,8 +1048,10 @@ DI void cross_const_finish(const LCtx& x, const LH& h, const LH& A, const CrossC
 // as simplify() does: the arena's peak use counts the reservation, so a bundle within N - K monomials
 // of its arena's end overflows here (ERR_ARENA, cnt = 0) and takes the planner's capacity retry.
 // Ends with a barrier.
+template <bool SQ>
 DI void cross_const(LCtx& x, int o, int a, const CrossC& C) {
     constexpr int UXC = LANE_UXC, RG = LW * UXC;
+    const Decide<SQ> thr{x.thr, x.thr_sq};
     static_assert(RG <= 64, "round masks fit one wave ballot");
     const LH& A = x.H[a];
     const int N = ui(A.cnt);
@@ -1105,7 +1110,7 @@ DI void cross_const(LCtx& x, int o, int a, const CrossC& C) {
                 out[u][e] = 0.0;
             }
             bool keep = false;
-            if (in) keep = cross_const_mono(C, v, x.thr, out[u], red);
+            if (in) keep = cross_const_mono(C, v, thr, out[u], red);
             mk[u] = ballot(keep);
             if (x.lane == 0) x.rmask[par * 64 + u * LW + x.wave] = mk[u];
             if (in) b += (unsigned long long)__popcll(sm[u]) * 32ull + (unsigned long long)__popcll(mk[u]) * 32ull;
@@ -1176,7 +1181,7 @@ DI void make_raw(const LCtx& x, int o, int R, int C, const double* center, int n
             if (m2 < nc && h[m2] == h[m])
 #pragma unroll
                 for (int e = 0; e < 9; e++) if (e < n) acc[m][e] = acc[m][e] + cf[m2][e];
-        keep[m] = head[m] && !(frob_norm(acc[m], n) <= x.thr);
+        keep[m] = head[m] && sq_not_le(frob_sq(acc[m], n), x.thr, x.thr_sq, x.thr_valid);
     }
     unsigned long long km[M];
     bool uk[M];
@@ -1224,7 +1229,7 @@ DI void make_raw(const LCtx& x, int o, int R, int C, const double* center, int n
     // header rows of this lane's job
     for (int q = 0; q < 4 * n; q++) x.pool[(long)(off + q) * LG + x.lane] = 0.0;
     for (int e = 0; e < n; e++) x.pool[(long)(off + e) * LG + x.lane] = center[e];
-    if (frob_norm(red, n) != 0)
+    if (frob_sq(red, n) != 0)
         for (int e = 0; e < n; e++) {
             x.pool[(long)(off + n + e) * LG + x.lane] += red[e];
             x.pool[(long)(off + 2 * n + e) * LG + x.lane] += red[e];
@@ -1586,7 +1591,11 @@ DI void dump_op(const LCtx& x, const Op* prog, int pc, int par, double* dump) {
     sync();
 }
 
+// SQ: keep / prune decisions on squared norms (pz_engine.h SqThr; x.thr_valid holds), else with sqrt
+template <bool SQ>
 DI void run_program(LCtx& x, const RobotParams& rp, const Op* prog, int nops, const ReachOut& out, double* dump) {
+    using D = Decide<SQ>;
+    const D dec{x.thr, x.thr_sq};
     for (int pc = 0; pc < nops; pc++) {
         const Op op = prog[pc];
         const int par = op.par > 1 ? op.par : 1;
@@ -1648,7 +1657,7 @@ DI void run_program(LCtx& x, const RobotParams& rp, const Op* prog, int nops, co
                 }
                 sync();
                 nterms = x.H[op.a].cnt;
-                cross_const(x, op.o, op.a, C);
+                cross_const<SQ>(x, op.o, op.a, C);
                 break;
             }
             default: {
@@ -1666,40 +1675,40 @@ DI void run_program(LCtx& x, const RobotParams& rp, const Op* prog, int nops, co
                 const int na = ui(A.R * A.C), nb = ui(B.R * B.C);
                 const bool views = ui(A.comp) >= 0 || ui(A.scaled) || ui(B.comp) >= 0 || ui(B.scaled);
                 if (op.code == OP_CROSS_PP && !views && na == 3 && nb == 3) {
-                    LPolCrossPP pol;
-                    pol.base.thr = x.thr;
+                    LPolCrossPP<D> pol;
+                    pol.base.thr = dec;
                     pol.a = op.a;
                     pol.b = op.b;
                     GCross Gc;
                     Gc.M = gen_mul<3, 3>(x, A, B);
                     simplify(x, op.o, T, Gc, pol, N);
                 } else if (op.code == OP_MUL && !views && na == 9 && nb == 3) {
-                    simplify(x, op.o, T, gen_mul<9, 3>(x, A, B), LPolBlock<3>{PolBlock<3>{x.thr}}, N);
+                    simplify(x, op.o, T, gen_mul<9, 3>(x, A, B), LPolBlock<3, D>{PolBlock<3, D>{dec}}, N);
                 } else if (op.code == OP_MUL && !views && na == 9 && nb == 9) {
-                    simplify(x, op.o, T, gen_mul<9, 9>(x, A, B), LPolBlock<9>{PolBlock<9>{x.thr}}, N);
+                    simplify(x, op.o, T, gen_mul<9, 9>(x, A, B), LPolBlock<9, D>{PolBlock<9, D>{dec}}, N);
                 } else if (op.code == OP_MUL && !views && na == 1 && nb == 3) {
-                    simplify(x, op.o, T, gen_mul<1, 3>(x, A, B), LPolBlock<3>{PolBlock<3>{x.thr}}, N);
+                    simplify(x, op.o, T, gen_mul<1, 3>(x, A, B), LPolBlock<3, D>{PolBlock<3, D>{dec}}, N);
                 } else if (op.code != OP_MUL && op.code != OP_CROSS_PP && T.nout == 3) {
-                    simplify(x, op.o, T, gen_cat<3>(x, op), LPolBlock<3>{PolBlock<3>{x.thr}}, N);
+                    simplify(x, op.o, T, gen_cat<3>(x, op), LPolBlock<3, D>{PolBlock<3, D>{dec}}, N);
                 } else if (op.code != OP_MUL && op.code != OP_CROSS_PP && T.nout == 1) {
-                    simplify(x, op.o, T, gen_cat<1>(x, op), LPolBlock<1>{PolBlock<1>{x.thr}}, N);
+                    simplify(x, op.o, T, gen_cat<1>(x, op), LPolBlock<1, D>{PolBlock<1, D>{dec}}, N);
                 } else if (op.code == OP_CROSS_PP) {
                     terms_centres(x, op, T);
-                    LPolCrossPP pol;
-                    pol.base.thr = x.thr;
+                    LPolCrossPP<D> pol;
+                    pol.base.thr = dec;
                     pol.a = op.a;
                     pol.b = op.b;
                     GAnyCross Gc{&T};
                     simplify(x, op.o, T, Gc, pol, N);
                 } else if (T.nout == 1) {
                     terms_centres(x, op, T);
-                    simplify(x, op.o, T, GAny<1>{&T}, LPolBlock<1>{PolBlock<1>{x.thr}}, N);
+                    simplify(x, op.o, T, GAny<1>{&T}, LPolBlock<1, D>{PolBlock<1, D>{dec}}, N);
                 } else if (T.nout == 3) {
                     terms_centres(x, op, T);
-                    simplify(x, op.o, T, GAny<3>{&T}, LPolBlock<3>{PolBlock<3>{x.thr}}, N);
+                    simplify(x, op.o, T, GAny<3>{&T}, LPolBlock<3, D>{PolBlock<3, D>{dec}}, N);
                 } else {
                     terms_centres(x, op, T);
-                    simplify(x, op.o, T, GAny<9>{&T}, LPolBlock<9>{PolBlock<9>{x.thr}}, N);
+                    simplify(x, op.o, T, GAny<9>{&T}, LPolBlock<9, D>{PolBlock<9, D>{dec}}, N);
                 }
                 break;
             }

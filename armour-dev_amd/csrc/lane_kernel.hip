@@ -51,6 +51,18 @@ struct LaneWide {
 struct LaneDense {
     static constexpr int KEYS = 1344, STAGE = 1024, WPE = 3, PER_CU = 3;
 };
+// the same two shapes deciding keep / prune with sqrt, as before the squared threshold: launched
+// only when the robot's squared threshold could not be verified (RobotParams::simplify_sq_valid = 0)
+struct LaneWideSqrt : LaneWide {
+    static constexpr bool SQ = false;
+};
+struct LaneDenseSqrt : LaneDense {
+    static constexpr bool SQ = false;
+};
+template <class S, class = void>
+struct lane_sq { static constexpr bool value = true; };
+template <class S>
+struct lane_sq<S, decltype((void)S::SQ)> { static constexpr bool value = S::SQ; };
 
 // S::WPE waves per SIMD (2: 256 VGPRs, 3: 168)
 template <class S>
@@ -99,6 +111,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(LT, LT), amdgpu_waves_per_
     x.err = &err;
     x.occ = occ;
     x.thr = rp.simplify_threshold;
+    x.thr_sq = rp.simplify_sq;
+    x.thr_valid = lane_sq<S>::value ? 1 : 0;
     x.prof = LANE_PROF ? a.prof : nullptr;
     x.nops = a.nops;
 
@@ -127,7 +141,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(LT, LT), amdgpu_waves_per_
         __syncthreads();
         unsigned long long* const btime = LANE_PROF ? a.btime : nullptr;
         const unsigned long long t0 = btime ? wall_clock64() : 0;
-        run_program(x, rp, a.prog, a.nops, out, b == 0 ? a.dump : nullptr);
+        run_program<lane_sq<S>::value>(x, rp, a.prog, a.nops, out, b == 0 ? a.dump : nullptr);
         __syncthreads();
         if (btime && x.tid == 0) {
             btime[2 * b] = t0;

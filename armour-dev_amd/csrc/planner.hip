@@ -107,6 +107,7 @@ struct armour_planner {
     int lane_grid = 0;        // workgroups with an arena: the larger (dense) shape's resident set
     int lane_slots[2] = {0, 0};  // resident bundle workgroups of the wide / dense kernel shape
     int lane_shape = -1;      // ARMOUR_LANE_SHAPE: 0 wide, 1 dense, -1 chosen per launch
+    bool sq = true;           // reach kernels decide keep / prune on squared norms (rp.simplify_sq_valid)
     int last_shape = 0;       // shape of the last first launch (a capacity retry uses it too)
     int dev = 0;              // the planner's device
     bool counted = false;     // counted in g_planners[dev]
@@ -239,6 +240,19 @@ static int planner_init(armour_planner* p, const armour_config* cfg, const armou
     int rc = 0;
     if ((rc = p->alloc(&p->d_rp, 1))) return rc;
     HIPCK(hipMemcpy(p->d_rp, &p->rp, sizeof(RobotParams), hipMemcpyHostToDevice));
+    {
+        // the simplify threshold on squared norms, found and verified on the device once per robot
+        // (pz_engine.h SqThr). Not verified, or ARMOUR_SQ_THRESHOLD=0: the sqrt kernels run.
+        hipLaunchKernelGGL(sq_threshold_kernel, dim3(1), dim3(1), 0, nullptr, p->d_rp);
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpy(&p->rp, p->d_rp, sizeof(RobotParams), hipMemcpyDeviceToHost));
+        const char* e = std::getenv("ARMOUR_SQ_THRESHOLD");
+        if (e && std::atoi(e) == 0 && p->rp.simplify_sq_valid) {
+            p->rp.simplify_sq_valid = 0;
+            HIPCK(hipMemcpy(p->d_rp, &p->rp, sizeof(RobotParams), hipMemcpyHostToDevice));
+        }
+        p->sq = p->rp.simplify_sq_valid != 0;
+    }
     if ((rc = p->alloc(&p->q0, (size_t)Wm * NF)) || (rc = p->alloc(&p->qd0, (size_t)Wm * NF)) ||
         (rc = p->alloc(&p->qdd0, (size_t)Wm * NF)) || (rc = p->alloc(&p->qdes, (size_t)Wm * NF)) ||
         (rc = p->alloc(&p->xin, (size_t)Wm * NF)) || (rc = p->alloc(&p->obs, (size_t)Wm * Om * 12)))
@@ -694,12 +708,16 @@ static int lane_shape_for(armour_planner* p, long bundles) {
     p->last_shape = shape;
     return shape;
 }
-static void launch_lane(int shape, int grid, hipStream_t s, const RobotParams* rp, const lane::LaneArgs& la,
+static void launch_lane(int shape, bool sq, int grid, hipStream_t s, const RobotParams* rp, const lane::LaneArgs& la,
                         const ReachOut& ro) {
-    if (shape == 1)
+    if (shape == 1 && sq)
         hipLaunchKernelGGL(lane::lane_reach_kernel<lane::LaneDense>, dim3(grid), dim3(lane::LT), 0, s, rp, la, ro);
-    else
+    else if (shape == 1)
+        hipLaunchKernelGGL(lane::lane_reach_kernel<lane::LaneDenseSqrt>, dim3(grid), dim3(lane::LT), 0, s, rp, la, ro);
+    else if (sq)
         hipLaunchKernelGGL(lane::lane_reach_kernel<lane::LaneWide>, dim3(grid), dim3(lane::LT), 0, s, rp, la, ro);
+    else
+        hipLaunchKernelGGL(lane::lane_reach_kernel<lane::LaneWideSqrt>, dim3(grid), dim3(lane::LT), 0, s, rp, la, ro);
 }
 
 // reach set for the uploaded batch. The whole phase is three kernel launches on the reach stream
@@ -739,13 +757,18 @@ static int run_reach(armour_planner* p) {
         const int shape = lane_shape_for(p, bundles);
         const long slots = std::min<long>(p->lane_slots[shape], p->lane_grid);
         const int lg = (int)(bundles < slots ? bundles : slots);
-        launch_lane(shape, lg, rs, p->d_rp, la, p->ro);
+        launch_lane(shape, p->sq, lg, rs, p->d_rp, la, p->ro);
     } else {
         // a batch that fits the chip in one round at two jobs per CU takes the wide kernel
-        if (jobs <= (long)REACH_WIDE_PER_CU * p->ncu && !p->job_narrow)
-            hipLaunchKernelGGL(reach_kernel<REACH_WIDE_THREADS>, dim3(grid), dim3(REACH_WIDE_THREADS), 0, rs, p->d_rp, ra, p->ro);
+        const bool wide = jobs <= (long)REACH_WIDE_PER_CU * p->ncu && !p->job_narrow;
+        if (wide && p->sq)
+            hipLaunchKernelGGL((reach_kernel<REACH_WIDE_THREADS, true>), dim3(grid), dim3(REACH_WIDE_THREADS), 0, rs, p->d_rp, ra, p->ro);
+        else if (wide)
+            hipLaunchKernelGGL((reach_kernel<REACH_WIDE_THREADS, false>), dim3(grid), dim3(REACH_WIDE_THREADS), 0, rs, p->d_rp, ra, p->ro);
+        else if (p->sq)
+            hipLaunchKernelGGL((reach_kernel<REACH_THREADS, true>), dim3(grid), dim3(REACH_THREADS), 0, rs, p->d_rp, ra, p->ro);
         else
-            hipLaunchKernelGGL(reach_kernel<REACH_THREADS>, dim3(grid), dim3(REACH_THREADS), 0, rs, p->d_rp, ra, p->ro);
+            hipLaunchKernelGGL((reach_kernel<REACH_THREADS, false>), dim3(grid), dim3(REACH_THREADS), 0, rs, p->d_rp, ra, p->ro);
     }
     HIPCK(hipGetLastError());
     HIPCK(hipEventRecord(p->ev[4], rs));
@@ -796,7 +819,7 @@ static int run_reach(armour_planner* p) {
         HIPCK(hipMemsetAsync(p->ro.err, 0, sizeof(int) * p->W, rs));
         const long bundles = ((long)retry.size() * p->T + lane::LG - 1) / lane::LG;
         const long g = std::max(p->lane_grid, RETRY_SCALE) / RETRY_SCALE;
-        launch_lane(p->last_shape, (int)(bundles < g ? bundles : g), rs, p->d_rp, la, p->ro);
+        launch_lane(p->last_shape, p->sq, (int)(bundles < g ? bundles : g), rs, p->d_rp, la, p->ro);
         HIPCK(hipGetLastError());
         HIPCK(hipEventRecord(p->ev[5], rs));
         HIPCK(hipEventSynchronize(p->ev[5]));
@@ -1333,6 +1356,52 @@ __global__ __launch_bounds__(256) void copy_kernel(const copy_v2d* __restrict__ 
         const long i = base + k * 256;
         if (i < n) __builtin_nontemporal_store(v[k], &dst[i]);
     }
+}
+
+int armour_sq_selfcheck(int device, double thr, long long half_width, const double* values, long long n,
+                        double* s_star, int* valid, long long* mismatches) {
+    int prev = -1;
+    (void)hipGetDevice(&prev);
+    struct Restore {
+        int d;
+        ~Restore() { if (d >= 0) (void)hipSetDevice(d); }
+    } restore{prev};
+    if (half_width < 0 || n < 0 || (n > 0 && !values) || !s_star || !valid || !mismatches)
+        return fail(ARMOUR_E_ARG, "half_width >= 0, n >= 0, values unless n = 0, and the three outputs");
+    if (hipSetDevice(device) != hipSuccess) return fail(ARMOUR_E_HIP, "hipSetDevice failed (no device?)");
+    RobotParams* rp = nullptr;
+    double* dv = nullptr;
+    unsigned long long* dbad = nullptr;
+    struct Free {
+        RobotParams*& a; double*& b; unsigned long long*& c;
+        ~Free() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (c) (void)hipFree(c); }
+    } freer{rp, dv, dbad};
+    HIPCK(hipMalloc((void**)&rp, sizeof(RobotParams)));
+    HIPCK(hipMalloc((void**)&dbad, sizeof(unsigned long long)));
+    if (n > 0) {
+        HIPCK(hipMalloc((void**)&dv, sizeof(double) * (size_t)n));
+        HIPCK(hipMemcpy(dv, values, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    }
+    HIPCK(hipMemset(rp, 0, sizeof(RobotParams)));
+    HIPCK(hipMemset(dbad, 0, sizeof(unsigned long long)));
+    HIPCK(hipMemcpy(&rp->simplify_threshold, &thr, sizeof(double), hipMemcpyHostToDevice));
+    // the planner's own search (planner_init), then the comparison of the two decisions
+    hipLaunchKernelGGL(sq_threshold_kernel, dim3(1), dim3(1), 0, nullptr, rp);
+    HIPCK(hipGetLastError());
+    SqThr q;
+    q.thr = thr;
+    HIPCK(hipMemcpy(&q.s, &rp->simplify_sq, sizeof(double), hipMemcpyDeviceToHost));
+    HIPCK(hipMemcpy(&q.valid, &rp->simplify_sq_valid, sizeof(int), hipMemcpyDeviceToHost));
+    const long long total = 2 * half_width + 1 + n;
+    const int blocks = (int)std::min<long long>((total + 255) / 256, 1024);
+    hipLaunchKernelGGL(sq_selfcheck_kernel, dim3(blocks), dim3(256), 0, nullptr, q, half_width, dv, n, dbad);
+    HIPCK(hipGetLastError());
+    unsigned long long bad = 0;
+    HIPCK(hipMemcpy(&bad, dbad, sizeof(bad), hipMemcpyDeviceToHost));
+    *s_star = q.s;
+    *valid = q.valid;
+    *mismatches = (long long)bad;
+    return ARMOUR_OK;
 }
 
 double armour_copy_bandwidth(int device, size_t bytes, int reps) {

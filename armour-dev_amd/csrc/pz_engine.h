@@ -94,6 +94,8 @@ struct Ctx {
     int* iscan;        // scan scratch (LDS): [waves] on device, [2 * n] in the emulation
     int* err;          // error word (LDS)
     double thr;
+    double thr_sq;     // SqThr::s and ::valid of thr (set by the kernel from RobotParams; the
+    int thr_valid;     // emulation's run_program finds them)
     unsigned long long* phase;  // optional large-operator phase cycle counters [8] (profiling)
     int mode;          // diagnostics: bit 0 = no wave-0 path
 };
@@ -102,14 +104,75 @@ enum : int { ERR_ARENA = 1, ERR_SORTCAP = 2, ERR_LINKGEN = 4, ERR_OUTCAP = 8, ER
 
 // ---------------------------------------------------------------------------------------------
 // scalar helpers (fixed 9-element blocks, unrolled so blocks stay in registers)
-AI double frob_norm(const double* x, int n) {
-    // Eigen 3.3 MatrixXd::norm(): packet-of-2 redux order (same as oracle/src/pz.cpp)
-    if (n == 1) return sqrt(x[0] * x[0]);
-    if (n == 3) return sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
+// sum of squares in the Eigen 3.3 MatrixXd::norm() packet-of-2 redux order (same as oracle/src/pz.cpp)
+AI double frob_sq(const double* x, int n) {
+    if (n == 1) return x[0] * x[0];
+    if (n == 3) return (x[0] * x[0] + x[1] * x[1]) + x[2] * x[2];
     const double s0 = x[0] * x[0], s1 = x[1] * x[1], s2 = x[2] * x[2], s3 = x[3] * x[3], s4 = x[4] * x[4];
     const double s5 = x[5] * x[5], s6 = x[6] * x[6], s7 = x[7] * x[7], s8 = x[8] * x[8];
-    return sqrt((((s0 + s4) + (s2 + s6)) + ((s1 + s5) + (s3 + s7))) + s8);
+    return (((s0 + s4) + (s2 + s6)) + ((s1 + s5) + (s3 + s7))) + s8;
 }
+AI double frob_norm(const double* x, int n) { return sqrt(frob_sq(x, n)); }
+AI double frob1_sq(double v) { return v * v; }
+
+// ---------------------------------------------------------------------------------------------
+// The keep / prune threshold on squared norms. Every simplify decision compares a Frobenius norm
+// f = sqrt(S) with the robot's simplify_threshold thr. sqrt is monotone, so f > thr is S > s with
+// s the largest double whose square root is still <= thr: the decision needs no square root. s is
+// found once per robot by sq_threshold(), with the very sqrt the decisions would call (the device's
+// on the device, the host's in the emulation), and verified there: valid says that
+// sqrt(s) <= thr < sqrt(next(s)) holds (or one of the special cases below), and only then is the
+// squared form used; otherwise every decision takes the sqrt form (Decide<false>).
+struct SqThr {
+    double thr;
+    double s;
+    int valid;
+};
+AI double sq_next(double c) {   // next double above c >= +0 (+inf stays)
+    unsigned long long b;
+    __builtin_memcpy(&b, &c, 8);
+    if (b < 0x7ff0000000000000ull) b++;
+    __builtin_memcpy(&c, &b, 8);
+    return c;
+}
+AI double sq_prev(double c) {   // next double below c > +0
+    unsigned long long b;
+    __builtin_memcpy(&b, &c, 8);
+    if (b > 0 && b <= 0x7ff0000000000000ull) b--;
+    __builtin_memcpy(&c, &b, 8);
+    return c;
+}
+AI SqThr sq_threshold(double thr) {
+    SqThr q;
+    q.thr = thr;
+    if (thr != thr) { q.s = thr; q.valid = 1; return q; }      // NaN: S > NaN and S <= NaN are false, as f > NaN
+    if (thr < 0) { q.s = -1.0; q.valid = 1; return q; }         // S >= +0 > s always, as f >= +0 > thr
+    const double inf = __builtin_inf(), dmax = 1.7976931348623157e308;
+    if (thr == inf) { q.s = inf; q.valid = 1; return q; }       // only S = NaN differs from "never"
+    double c = thr * thr;
+    if (c == inf) c = dmax;                                     // S = inf must still compare above s
+    for (int i = 0; i < 4; i++) {                               // up while the next one still fits
+        const double n = sq_next(c);
+        if (n == inf || !(sqrt(n) <= thr)) break;
+        c = n;
+    }
+    for (int i = 0; i < 4; i++) {                               // down while this one does not
+        if (!(c > 0) || !(sqrt(c) > thr)) break;
+        c = sq_prev(c);
+    }
+    q.s = c;
+    q.valid = (sqrt(c) <= thr && thr < sqrt(sq_next(c))) ? 1 : 0;   // next(DBL_MAX) = inf: sqrt = inf > thr
+    return q;
+}
+// the decision in the polarities the engines use (a NaN sum fails gt and le alike, in both forms)
+template <bool SQ>
+struct Decide {
+    double thr, s;
+    AI bool gt(double S) const { return SQ ? S > s : sqrt(S) > thr; }
+    AI bool le(double S) const { return SQ ? S <= s : sqrt(S) <= thr; }
+};
+// !(f <= thr) of the raw constructors (thread-0 work outside the round loops: decided at run time)
+AI bool sq_not_le(double S, double thr, double s, int valid) { return valid ? !(S <= s) : !(sqrt(S) <= thr); }
 
 // column-major coefficient-based product, inner index summed in order. The program only forms
 // (3x3)(3x3) and (3x3)(3x1) block products (1x1 operands are handled as scalings); any other
@@ -563,13 +626,12 @@ AI void arena_alloc_t0(Ctx& x, PZH& h, int K, int stride) {
 
 // output header finish (thread 0): pruned amount into both independent parts (PZsparse.cu:347-349)
 AI void finish_t0(const Ctx& x, PZH& h, const double* red, const double* abs, int n) {
-    if (frob_norm(red, n) != 0)
+    if (frob_sq(red, n) != 0)   // S >= +0: sqrt(S) != 0 exactly when S != 0 (NaN and inf included)
         UNR for (int v = 0; v < 2; v++)
             UNR for (int e = 0; e < 9; e++) if (e < n) ind(x, h, v)[e] = ind(x, h, v)[e] + red[e];
     UNR for (int e = 0; e < 9; e++) if (e < n) abs_(x, h)[e] = abs[e];
 }
 
-AI double frob1(double v) { return frob_norm(&v, 1); }
 AI double pick3(const double* m, int i) { return i == 0 ? m[0] : (i == 1 ? m[1] : m[2]); }
 
 // ---------------------------------------------------------------------------------------------
@@ -581,12 +643,12 @@ AI double pick3(const double* m, int i) { return i == 0 ? m[0] : (i == 1 ? m[1] 
 // plain simplify (PZsparse.cu:284-350): group sum of coefficient blocks, prune by Frobenius norm.
 // Instantiated per output class NN (1x1, 3x1, 3x3) so the frequent small blocks carry no 9-element
 // arrays: the register budget of the common paths stays clear of the 3x3 one.
-template <int NN>
+template <int NN, class D = Decide<true>>
 struct PolBlock {
     static constexpr int NV = NN;
     static constexpr int NO = NN;
     static constexpr int NR = 2 * NN;   // [0, NN): pruned |sum|, [NN, 2NN): kept |sum| (absum)
-    double thr;
+    D thr;
     AI unsigned mask() const { return (1u << NR) - 1; }
     AI void term(const Terms& T, int p, double* v) const {
         double t[9];
@@ -594,7 +656,7 @@ struct PolBlock {
         UNR for (int e = 0; e < NN; e++) v[e] = t[e];
     }
     AI bool group(const double* s, double* out, double* red) const {
-        const bool keep = frob_norm(s, NN) > thr;
+        const bool keep = thr.gt(frob_sq(s, NN));
         UNR for (int e = 0; e < NN; e++) {
             if (keep) { out[e] = s[e]; red[NN + e] = red[NN + e] + fabs(s[e]); }
             else red[e] = red[e] + fabs(s[e]);
@@ -609,11 +671,12 @@ struct PolBlock {
 // each simplified; r_e = P_2e - P_2e+1, each simplified; stack(r0, r1, r2), simplified. All six
 // products share one term list (T1 a_i, T2 b_j, T3 a_i + b_j), so one ordering serves them all;
 // every intermediate prune is replicated per hash group.
-struct PolCrossPP {
+template <class D = Decide<true>>
+struct PolCrossPPT {
     static constexpr int NV = 6;
     static constexpr int NO = 3;
     static constexpr int NR = 15;   // [0,6) product prunes, [6,9) difference prunes, [9,12) stack prunes, [12,15) absum
-    double thr;
+    D thr;
     const double* ac;               // operand centres (LDS handles)
     const double* bc;
     int a, b;                       // operand handle slots
@@ -642,7 +705,7 @@ struct PolCrossPP {
     AI bool group(const double* s, double* out, double* red) const {
         bool pres[6];
         UNR for (int p = 0; p < 6; p++) {
-            pres[p] = frob1(s[p]) > thr;
+            pres[p] = thr.gt(frob1_sq(s[p]));
             if (!pres[p]) red[p] = red[p] + fabs(s[p]);
         }
         double vec[3];
@@ -651,12 +714,12 @@ struct PolCrossPP {
             const int P = 2 * e, Q = 2 * e + 1;
             bool have = pres[P] || pres[Q];
             const double v = pres[P] ? (pres[Q] ? s[P] + (-s[Q]) : s[P]) : (pres[Q] ? -s[Q] : 0.0);
-            if (have && !(frob1(v) > thr)) { red[6 + e] = red[6 + e] + fabs(v); have = false; }
+            if (have && !thr.gt(frob1_sq(v))) { red[6 + e] = red[6 + e] + fabs(v); have = false; }
             vec[e] = have ? v : 0.0;
             any = any || have;
         }
         if (!any) return false;
-        if (!(frob_norm(vec, 3) > thr)) {
+        if (!thr.gt(frob_sq(vec, 3))) {
             UNR for (int e = 0; e < 3; e++) red[9 + e] = red[9 + e] + fabs(vec[e]);
             return false;
         }
@@ -679,17 +742,17 @@ struct PolCrossPP {
             UNR for (int v = 0; v < 2; v++) {
                 const double ai = pick3(ind(x, A, v), ea[p]), bi = pick3(ind(x, B, v), fb[p]);
                 pi[v][p] = ai * bi + (r2 * bi + ai * r3);
-                if (frob1(red[p]) != 0) pi[v][p] = pi[v][p] + red[p];
+                if (frob1_sq(red[p]) != 0) pi[v][p] = pi[v][p] + red[p];
             }
         }
         double sred[3];
         UNR for (int e = 0; e < 3; e++) sred[e] = red[9 + e];
-        const bool sadd = frob_norm(sred, 3) != 0;
+        const bool sadd = frob_sq(sred, 3) != 0;
         UNR for (int e = 0; e < 3; e++) {
             cen(x, h)[e] = pc[2 * e] - pc[2 * e + 1];
             UNR for (int v = 0; v < 2; v++) {
                 double iv = pi[v][2 * e] + pi[v][2 * e + 1];
-                if (frob1(red[6 + e]) != 0) iv = iv + red[6 + e];
+                if (frob1_sq(red[6 + e]) != 0) iv = iv + red[6 + e];
                 if (sadd) iv = iv + sred[e];
                 ind(x, h, v)[e] = iv;
             }
@@ -697,6 +760,7 @@ struct PolCrossPP {
         }
     }
 };
+using PolCrossPP = PolCrossPPT<>;
 
 // deterministic reduction of the masked slots of an NR-block over the group
 AI void block_sum_mask(const Ctx& x, double* v, int nr, unsigned mask) {
@@ -945,7 +1009,8 @@ AI CrossC cross_const_table(int kind, const double* v) {
     return C;
 }
 // one source monomial m -> output row; red: [0,3) difference prunes, [3,6) stack prunes, [6,9) absum
-AI bool cross_const_mono(const CrossC& C, const double* m, double thr, double* out, double* red) {
+template <class D>
+AI bool cross_const_mono(const CrossC& C, const double* m, const D& thr, double* out, double* red) {
     double vec[3];
     bool any = false;
     UNR for (int e = 0; e < 3; e++) {
@@ -953,12 +1018,12 @@ AI bool cross_const_mono(const CrossC& C, const double* m, double thr, double* o
         const double xb = -(C.sB[e] * pick3(m, C.iB[e]));
         const double v = xa + xb;
         bool have = true;
-        if (!(frob1(v) > thr)) { red[e] = red[e] + fabs(v); have = false; }
+        if (!thr.gt(frob1_sq(v))) { red[e] = red[e] + fabs(v); have = false; }
         vec[e] = have ? v : 0.0;
         any = any || have;
     }
     if (!any) return false;
-    if (!(frob_norm(vec, 3) > thr)) {
+    if (!thr.gt(frob_sq(vec, 3))) {
         UNR for (int e = 0; e < 3; e++) red[3 + e] = red[3 + e] + fabs(vec[e]);
         return false;
     }
@@ -969,12 +1034,12 @@ AI bool cross_const_mono(const CrossC& C, const double* m, double thr, double* o
 AI void cross_const_finish(const Ctx& x, PZH& h, const PZH& A, const CrossC& C, const double* red) {
     double sred[3];
     UNR for (int e = 0; e < 3; e++) sred[e] = red[3 + e];
-    const bool sadd = frob_norm(sred, 3) != 0;
+    const bool sadd = frob_sq(sred, 3) != 0;
     UNR for (int e = 0; e < 3; e++) {
         cen(x, h)[e] = pick3(cen(x, A), C.iA[e]) * C.sA[e] - pick3(cen(x, A), C.iB[e]) * C.sB[e];
         UNR for (int v = 0; v < 2; v++) {
             double iv = pick3(ind(x, A, v), C.iA[e]) * fabs(C.sA[e]) + pick3(ind(x, A, v), C.iB[e]) * fabs(C.sB[e]);
-            if (frob1(red[e]) != 0) iv = iv + red[e];
+            if (frob1_sq(red[e]) != 0) iv = iv + red[e];
             if (sadd) iv = iv + sred[e];
             ind(x, h, v)[e] = iv;
         }
@@ -983,8 +1048,10 @@ AI void cross_const_finish(const Ctx& x, PZH& h, const PZH& A, const CrossC& C, 
 }
 
 // the whole op; the header of o (3x1) is initialised by the caller's thread 0; ends without barrier
+template <bool SQ>
 AI void cross_const(Ctx& x, int o, int a, const CrossC& C) {
     const Grp& g = x.g;
+    const Decide<SQ> thr{x.thr, x.thr_sq};
     const PZH& A = x.H[a];
     const int N = A.cnt;
     const Src S = src_of(x, A);
@@ -997,7 +1064,7 @@ AI void cross_const(Ctx& x, int o, int a, const CrossC& C) {
         bool keep = false;
         if (lane < N) {
             S.read(lane, false, m);
-            keep = cross_const_mono(C, m, x.thr, out, red);
+            keep = cross_const_mono(C, m, thr, out, red);
         }
         const unsigned long long km = __ballot(keep);
         const int K = __popcll(km);
@@ -1032,7 +1099,7 @@ AI void cross_const(Ctx& x, int o, int a, const CrossC& C) {
     }
     for (int k = g.tid; k < N; k += g.n) {
         S.read(k, false, m);
-        kp[k] = cross_const_mono(C, m, x.thr, out, red) ? 1 : 0;
+        kp[k] = cross_const_mono(C, m, thr, out, red) ? 1 : 0;
     }
     g.sync();
     const int K = block_scan(x, kp, N);
@@ -1049,7 +1116,7 @@ AI void cross_const(Ctx& x, int o, int a, const CrossC& C) {
             if (!keep) continue;
             S.read(k, false, m);
             UNR for (int e = 0; e < 9; e++) dummy[e] = 0.0;
-            cross_const_mono(C, m, x.thr, out, dummy);
+            cross_const_mono(C, m, thr, out, dummy);
             const long pos = kp[k];
             x.ah[hoff + pos] = S.h[k];
             double* dst = x.ac + coff + pos * 3;

@@ -216,7 +216,7 @@ T0FN void t0_make_raw(Ctx& x, int o, int R, int C, const double* center, int nc,
         UNR for (int e = 0; e < 9; e++) acc[m][e] = (m < nc && e < n) ? cf[m][e] : 0.0;
         UNR for (int m2 = m + 1; m2 < M; m2++)
             if (m2 < nc && h[m2] == h[m]) UNR for (int e = 0; e < 9; e++) if (e < n) acc[m][e] = acc[m][e] + cf[m2][e];
-        keep[m] = head[m] && !(frob_norm(acc[m], n) <= x.thr);
+        keep[m] = head[m] && sq_not_le(frob_sq(acc[m], n), x.thr, x.thr_sq, x.thr_valid);
     }
     int rk[M], pos[M], K = 0;
     UNR for (int m = 0; m < M; m++) {
@@ -238,7 +238,7 @@ T0FN void t0_make_raw(Ctx& x, int o, int R, int C, const double* center, int nc,
     PZH& hd = x.H[o];
     hdr_init(x, hd, R, C);
     for (int e = 0; e < n; e++) cen(x, hd)[e] = center[e];
-    if (frob_norm(red, n) != 0)
+    if (frob_sq(red, n) != 0)
         for (int e = 0; e < n; e++) { ind(x, hd, 0)[e] += red[e]; ind(x, hd, 1)[e] += red[e]; }
     UNR for (int e = 0; e < 9; e++) if (e < n) abs_(x, hd)[e] += ab[e];
     arena_alloc_t0(x, hd, K, n);
@@ -487,10 +487,24 @@ inline int* g_op_stats = nullptr;
 // host emulation: per op, the output handle's monomial hashes (structure studies)
 inline void (*g_hash_sink)(int pc, const uint64_t* h, int n) = nullptr;
 #endif
+// SQ: keep / prune decisions on squared norms (pz_engine.h SqThr; needs x.thr_valid), else with sqrt
+template <bool SQ = true>
 AI void run_program(Ctx& x, const RobotParams& rp, const Op* prog, int nops, int T, int t, const double* q0,
                     const double* qd0, const double* qdd0, const ReachOut& out, long j, JrsJoint* jrs,
                     double* scratch, unsigned long long* prof, double* dump = nullptr, const JrsJoint* jrs_in = nullptr) {
     const int tid = x.g.tid;
+#if !defined(__HIP_DEVICE_COMPILE__)
+    if (SQ) {
+        // the emulation: the same search with the host's sqrt
+        const SqThr q = sq_threshold(x.thr);
+        x.thr_sq = q.s;
+        x.thr_valid = q.valid;
+        if (!q.valid) {
+            run_program<false>(x, rp, prog, nops, T, t, q0, qd0, qdd0, out, j, jrs, scratch, prof, dump, jrs_in);
+            return;
+        }
+    }
+#endif
     double* rdist = scratch;
     double* ured = scratch + NF;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -563,7 +577,7 @@ AI void run_program(Ctx& x, const RobotParams& rp, const Op* prog, int nops, int
                 const double* v = op.b == VEC_TRANS ? &rp.trans[3 * op.c] : &rp.com[3 * op.c];
                 const CrossC C = cross_const_table(op.i, v);
                 if (tid == 0) hdr_init(x, x.H[op.o], 3, 1);
-                cross_const(x, op.o, op.a, C);
+                cross_const<SQ>(x, op.o, op.a, C);
                 break;
             }
             default: {
@@ -601,11 +615,12 @@ AI void run_program(Ctx& x, const RobotParams& rp, const Op* prog, int nops, int
 #if defined(__HIP_DEVICE_COMPILE__)
                 if (x.phase && tid == 0) x.phase[14] += (unsigned long long)(clock64() - ph0);
 #endif
-                PolBlock<1> p1{x.thr};
-                PolBlock<3> p3{x.thr};
-                PolBlock<9> p9{x.thr};
-                PolCrossPP pp;
-                pp.thr = x.thr;
+                const Decide<SQ> dec{x.thr, x.thr_sq};
+                PolBlock<1, Decide<SQ>> p1{dec};
+                PolBlock<3, Decide<SQ>> p3{dec};
+                PolBlock<9, Decide<SQ>> p9{dec};
+                PolCrossPPT<Decide<SQ>> pp;
+                pp.thr = dec;
                 pp.ac = cen(x, x.H[op.a]);
                 pp.bc = cen(x, x.H[op.b]);
                 pp.a = op.a;

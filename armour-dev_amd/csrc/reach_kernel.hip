@@ -106,6 +106,43 @@ __global__ void jrs_kernel(const RobotParams* __restrict__ rpp, int W, int T, co
     }
 }
 
+// simplify_threshold on squared norms, once per robot, with the sqrt the reach kernels would call
+__global__ void sq_threshold_kernel(RobotParams* rp) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const SqThr q = sq_threshold(rp->simplify_threshold);
+    rp->simplify_sq = q.s;
+    rp->simplify_sq_valid = q.valid;
+}
+
+// The squared threshold's self-check (armour_sq_selfcheck): every thread compares the decisions on
+// sqrt(S) and on S, in the three polarities the engines use, over the 2 * half + 1 doubles around
+// q.s and over n caller-supplied values; out[0] counts the mismatches
+__global__ void sq_selfcheck_kernel(SqThr q, long long half, const double* vals, long long n, unsigned long long* out) {
+    const Decide<true> a{q.thr, q.s};
+    const Decide<false> b{q.thr, q.s};
+    unsigned long long bad = 0;
+    unsigned long long sb;
+    __builtin_memcpy(&sb, &q.s, 8);
+    const long long total = (q.s >= 0 ? 2 * half + 1 : 0) + n;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        double S;
+        if (i < total - n) {
+            // the doubles within `half` ulps of q.s, clamped to [+0, +inf]
+            const long long d = i - half;
+            unsigned long long bits = sb;
+            if (d < 0) bits = sb >= (unsigned long long)(-d) ? sb + d : 0;
+            else bits = sb + (unsigned long long)d;
+            if (bits > 0x7ff0000000000000ull) bits = 0x7ff0000000000000ull;
+            __builtin_memcpy(&S, &bits, 8);
+        } else {
+            S = vals[i - (total - n)];
+        }
+        if (a.gt(S) != b.gt(S)) bad++;          // f > thr and !(f > thr)
+        if (!a.le(S) != !b.le(S)) bad++;        // !(f <= thr)
+    }
+    if (bad) atomicAdd(out, bad);
+}
+
 // ARMTD comparison planner (ACMP/Trajectory.cu:29-72): the offline JRS tables of cos / sin of the
 // relative joint angle rotated by q0, as the JRS scalars the reach program's MAKEROT reads (the
 // k-generator and the radius of the cos / sin 1-D PZs; radius x 5 as :43, :56). tables:
@@ -160,8 +197,9 @@ struct ReachArgs {
     double* dump;               // optional op-by-op state of job 0 (null: off)
 };
 
-// 2 waves per SIMD: 256 registers per lane (VGPR + AGPR); NT threads per job
-template <int NT>
+// 2 waves per SIMD: 256 registers per lane (VGPR + AGPR); NT threads per job. SQ: keep / prune on
+// squared norms (the robot's squared threshold is verified); false: with sqrt, the fallback
+template <int NT, bool SQ = true>
 __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_eu(REACH_CFG_WAVES_PER_SIMD, REACH_CFG_WAVES_PER_SIMD))) void reach_kernel(const RobotParams* __restrict__ rpp, ReachArgs a, ReachOut out) {
     __shared__ PZH H[MAX_SLOTS];
     __shared__ double pool[POOL_DOUBLES + 9];  // + 9: header reads of a full 3x3 past a small slot
@@ -201,6 +239,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
     x.iscan = iscan;
     x.err = &err;
     x.thr = rp.simplify_threshold;
+    x.thr_sq = rp.simplify_sq;
+    x.thr_valid = SQ ? 1 : 0;
     x.phase = a.phase ? phase_acc : nullptr;
     if (threadIdx.x < 16) phase_acc[threadIdx.x] = 0;
     x.mode = a.mode;
@@ -222,7 +262,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(NT, NT), amdgpu_waves_per_
             qdd0s[threadIdx.x] = a.qdd0[w * NF + threadIdx.x];
         }
         __syncthreads();
-        run_program(x, rp, a.prog, a.nops, a.T, t, q0s, qd0s, qdd0s, out, job, jrs, scratch, a.prof,
+        run_program<SQ>(x, rp, a.prog, a.nops, a.T, t, q0s, qd0s, qdd0s, out, job, jrs, scratch, a.prof,
                     job == 0 ? a.dump : nullptr, a.jrs + job * NF);
         if (threadIdx.x == 0) {
             if (err) atomicOr(&out.err[w], err);

@@ -269,6 +269,15 @@ int armour_get_reach_span(armour_planner* p, double* span_ms);
  * block size, centre[0..2], nominal ind[0], interval ind[0], sum|m|[0]] of the op's output, when
  * ARMOUR_DUMP_OPS was set at armour_create; returns the op count. */
 int armour_get_reach_dump(armour_planner* p, double* dump, int capacity);
+/* Self-check of the keep / prune decision on squared norms. The reach kernels
+ * decide sqrt(S) > thr as S > S*, with S* the largest double whose square root is <= thr, found and
+ * verified on the device when a planner is created. This runs the same search for `thr` on `device`
+ * and counts, on the device, how often the two forms decide differently (as f > thr and as
+ * !(f <= thr), one count each) over the doubles within half_width ulps of S* and over the n values
+ * (n may be 0). Writes S*, whether the device verified it (0: a planner with this threshold runs
+ * the sqrt kernels, as ARMOUR_SQ_THRESHOLD=0 forces) and the count, which is 0 on a sound device. */
+int armour_sq_selfcheck(int device, double thr, long long half_width, const double* values, long long n,
+                        double* s_star, int* valid, long long* mismatches);
 
 #ifdef __cplusplus
 }

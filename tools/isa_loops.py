@@ -20,12 +20,20 @@ the last round's stores; where no LDS read precedes the barrier, as in cross_con
 round's first load from memory), and the scratch accesses in the loop. Loops are taken from the
 compiler's block comments (Loop Header / in Loop / Parent Loop), since the layout may put a loop's
 latch blocks ahead of its header. A loop is named by its kernel and by the lines of SOURCE_FILE
-(default lane_engine.h) its instructions come from. It counts waits and nothing else."""
+(default lane_engine.h) its instructions come from. It counts waits and nothing else.
+
+    python tools/isa_loops.py --mix /tmp/lane.s [SOURCE_FILE]
+prints for the same loops (the compacting rounds) the instruction count by class: f64 VALU, other
+VALU, SALU, lane moves (v_readlane / v_writelane / v_readfirstlane / v_permlane), loads (global, flat,
+scratch, scalar), stores, LDS, waits (s_waitcnt, s_barrier) and nops, and the number of v_rsq_f64:
+each marks one expanded fp64 square root (none is left in a round once the keep / prune decisions
+compare squared norms). Whole bodies, inner loops included. It counts and classifies."""
 import collections
 import re
 import sys
 
-round_waits = sys.argv[1:2] == ["--round-waits"]
+mix = sys.argv[1:2] == ["--mix"]
+round_waits = mix or sys.argv[1:2] == ["--round-waits"]
 if round_waits:
     del sys.argv[1]
 lines = open(sys.argv[1]).read().split("\n")
@@ -58,6 +66,29 @@ def instr(j):
 
 def vm_wait(j):
     return instr(j).startswith("s_waitcnt") and "vmcnt" in instr(j)
+
+
+CLASSES = ("f64 VALU", "other VALU", "SALU", "lane moves", "loads", "stores", "LDS", "waits", "nops")
+
+
+def classify(op):
+    if re.match(r"v_(readlane|writelane|readfirstlane|permlane)", op):
+        return "lane moves"
+    if op.startswith("v_"):
+        return "f64 VALU" if "_f64" in op else "other VALU"
+    if op.startswith("ds_"):
+        return "LDS"
+    if re.match(r"(global|flat|scratch|buffer)_load|s_(buffer_)?load", op):
+        return "loads"
+    if re.match(r"(global|flat|scratch|buffer)_(store|atomic)", op):
+        return "stores"
+    if op.startswith("s_waitcnt") or op.startswith("s_barrier"):
+        return "waits"
+    if op.startswith("s_nop"):
+        return "nops"
+    if op.startswith("s_"):
+        return "SALU"
+    return None
 
 
 def loop_blocks():
@@ -121,12 +152,24 @@ if round_waits:
             kern = k[0]
             print(f"kernel {kern}")
         n += 1
+        if mix:
+            ops = [instr(j).split()[0] for j in body if instr(j) and re.match(r"[a-z]", instr(j))]
+            cnt = collections.Counter(c for c in map(classify, ops) if c)
+            rsq = sum(o.startswith("v_rsq_f64") for o in ops)
+            tot[0] += sum(cnt.values())
+            tot[1] += rsq
+            print(f"  loop {h} (depth {len(parents.get(h, [])) + 1}, {src}:{ln[0]}-{ln[-1]}): {sum(cnt.values())} instructions: "
+                  + ", ".join(f"{c} {cnt[c]}" for c in CLASSES) + f"; v_rsq_f64 {rsq}")
+            continue
         tot[0] += after
         tot[1] += before
         print(f"  loop {h} (depth {len(parents.get(h, [])) + 1}, {src}:{ln[0]}-{ln[-1]}, {len(body)} lines, {len(st)} stores to memory): "
               f"vmcnt waits after the first store {after}, before the first {what} {before}; "
               f"scratch loads {sl}, stores {ss}")
-    print(f"{n} round loops: vmcnt waits after the first store {tot[0]}, before the first read {tot[1]}")
+    if mix:
+        print(f"{n} round loops: {tot[0]} instructions, v_rsq_f64 {tot[1]}")
+    else:
+        print(f"{n} round loops: vmcnt waits after the first store {tot[0]}, before the first read {tot[1]}")
 elif len(sys.argv) > 3:
     src, last = sys.argv[2], int(sys.argv[3])
     for a, b in sorted(set(loops)):
