@@ -55,7 +55,8 @@ def link_spheres(robot: Robot, q: np.ndarray):
         p = p + R @ robot.trans[i]
         R = R @ _rpy(*robot.rots[i])
         if robot.axes[i] != 0 and i < len(q):
-            R = R @ _rot(abs(robot.axes[i]), q[i])
+            # axis code -a: the joint turns about -e_a, Rot(e_a, -q)
+            R = R @ _rot(abs(robot.axes[i]), q[i] if robot.axes[i] > 0 else -q[i])
         cs.append(p + R @ robot.link_c[i])
         rs.append(float(np.linalg.norm(robot.link_g[i])))
     return np.array(cs), np.array(rs)

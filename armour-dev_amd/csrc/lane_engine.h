@@ -1261,7 +1261,7 @@ DI void make_1d(const LCtx& x, int o, int i, int v) {
 
 DI void make_rot(const LCtx& x, int o, const RobotParams& rp, int i) {
     const JrsJoint& J = x.jrs[i];
-    const int ax = rp.axes[i];
+    const int ax = rp.axes[i] < 0 ? -rp.axes[i] : rp.axes[i];  // reversed: jrs_joint signs the sines
     double cn[9], cf[4][9];
     uint64_t hh[4];
 #pragma unroll

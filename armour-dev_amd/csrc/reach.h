@@ -32,7 +32,8 @@ struct ReachOut {
     int* err;              // [world]
 };
 
-// per-joint JRS scalars of one interval (KPR/Trajectory.cu:71-245)
+// per-joint JRS scalars of one interval (KPR/Trajectory.cu:71-245), of the joint's motion about the
+// positive axis e_a (a reversed joint: jrs_joint's last lines)
 struct JrsJoint {
     double cos_c, cos_k, cos_e;
     double sin_c, sin_k, sin_e;
@@ -162,6 +163,14 @@ __host__ __device__ __attribute__((noinline)) JrsJoint jrs_joint(const RobotPara
     J.qdd_c = (ki_lb + ki_ub) * 0.5;
     J.qdd_k = kdc;
     J.qdd_e = kdr + kir + rp.qddae;
+    // A reversed joint (axis code -a) turns by q about -e_a, that is by -q about e_a. The scalars
+    // describe the motion about e_a, which is what the program's ops are written for: the sine and
+    // the three rates change sign (every coefficient of their PZs, exactly), the cosine does not.
+    if (rp.axes[i] < 0) {
+        J.sin_c = -J.sin_c; J.sin_k = -J.sin_k; J.sin_e = -J.sin_e;
+        J.qd_c = -J.qd_c; J.qd_k = -J.qd_k; J.qd_e = -J.qd_e; J.qda_e = -J.qda_e;
+        J.qdd_c = -J.qdd_c; J.qdd_k = -J.qdd_k; J.qdd_e = -J.qdd_e;
+    }
     return J;
 }
 
@@ -322,8 +331,9 @@ T0FN void t0_make_1d(Ctx& x, int o, const JrsJoint& J, int i, int v) {
 }
 
 T0FN void t0_make_rot(Ctx& x, int o, const RobotParams& rp, const JrsJoint& J, int i) {
-    // rotation PZ about the joint axis (PZsparse.cu:179-205 + makeRotationMatrix :211-250)
-    const int ax = rp.axes[i];
+    // rotation PZ about the joint axis (PZsparse.cu:179-205 + makeRotationMatrix :211-250). A
+    // reversed joint (code -a) is Rot(e_a, -q): the matrix of axis a on jrs_joint's signed sines
+    const int ax = rp.axes[i] < 0 ? -rp.axes[i] : rp.axes[i];
     double cen[9], cf[4][9];
     uint64_t hh[4];
     for (int e = 0; e < 9; e++) cen[e] = (e % 4 == 0) ? 1.0 : 0.0;
@@ -890,6 +900,7 @@ struct ProgramBuilder {
                 W = w;
             }
             if (rp.axes[i] != 0) {
+                // a reversed joint's QD / QDA / QDD are its rates about +e_a (jrs_joint)
                 const int ax = (rp.axes[i] < 0 ? -rp.axes[i] : rp.axes[i]) - 1;
                 int w = add1d(W, QD[i], ax);
                 rel(W);
@@ -958,11 +969,15 @@ struct ProgramBuilder {
             rel({t5, FF});
             FF = ff;
             if (rp.axes[i] != 0 && i < NF) {
-                const int ax = (rp.axes[i] < 0 ? -rp.axes[i] : rp.axes[i]) - 1;
-                const int e = elem(NN, ax);
-                const int s1 = scaled(QDD[i], rp.armature[i]);
+                // u = n . axis + armature qdd + damping qd. For a reversed joint (code -a) the axis
+                // is -e_a and QDD / QD hold -qdd / -qd (jrs_joint): the same three views with the
+                // sign in their scale, so the op sequence does not depend on the joints' signs
+                const bool rev = rp.axes[i] < 0;
+                const int ax = (rev ? -rp.axes[i] : rp.axes[i]) - 1;
+                const int e = rev ? scaled_elem(NN, ax, -1.0) : elem(NN, ax);
+                const int s1 = scaled(QDD[i], rev ? -rp.armature[i] : rp.armature[i]);
                 const int u1 = add(e, s1);
-                const int s2 = scaled(QD[i], rp.damping[i]);
+                const int s2 = scaled(QD[i], rev ? -rp.damping[i] : rp.damping[i]);
                 us[i] = add(u1, s2);
                 rel({e, s1, u1, s2});
             }

@@ -91,7 +91,15 @@ void armour_destroy(armour_planner* p);
  * link i (the child of joint i) has mass, centre of mass, inertia (row-major 3x3) and a box
  * zonotope (centre, half extents: the STL bounding box of create_pz_bounding_boxes.m). The first
  * ARMOUR_NUM_FACTORS joints are the actuated ones. armour_amd/robot_tables.py builds these from a
- * URDF and its meshes. */
+ * URDF and its meshes.
+ * A reversed joint, code -a (URDF <axis> -e_a), turns by q about the unit vector -e_a: its rotation
+ * is R = Rot(e_a, -q), its angular velocity -qd e_a, and its generalised torque the moment about
+ * -e_a: u = -n[a] + armature qdd + damping qd. Its q, limits, speed and torque limits and trajectory
+ * parameter k are all counted about -e_a. The robot with joint j reversed, at the state with q0, qd0,
+ * qdd0 and q_des of joint j negated, is the same arm: same link sets, torques of joint j negated.
+ * The reach program of 8 or 9 joints needs more payload than the per-job reach engine holds; such
+ * robots run on the bundle engine at every batch size, and armour_create_robot refuses them with
+ * ARMOUR_E_CAPACITY only where ARMOUR_ENGINE=job forces the per-job engine. */
 #define ARMOUR_MAX_JOINTS 9
 typedef struct armour_robot {
     int num_joints;                               /* NUM_JOINTS, 7..9 */

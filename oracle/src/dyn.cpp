@@ -65,17 +65,23 @@ void KinDyn::rnea(int t, const std::vector<PZ>& mass_arr, const std::vector<PZ>&
         // line 13
         w = mul(Rt, w, thr);
         if (r.axes[i] != 0) {
+            // axis code -a (not in the reference): the joint turns about -e_a, so its angular
+            // rates along e_a are -qd, -qda, -qdda
             const int ax = std::abs(r.axes[i]) - 1;
-            w.addOneDimPZ(traj->qd_des[i * T + t], ax, 0, thr);
+            const double sg = r.axes[i] < 0 ? -1.0 : 1.0;
+            const PZ zqd = sg < 0 ? scale(sg, traj->qd_des[i * T + t]) : traj->qd_des[i * T + t];
+            const PZ zqda = sg < 0 ? scale(sg, traj->qda_des[i * T + t]) : traj->qda_des[i * T + t];
+            const PZ zqdda = sg < 0 ? scale(sg, traj->qdda_des[i * T + t]) : traj->qdda_des[i * T + t];
+            w.addOneDimPZ(zqd, ax, 0, thr);
             // line 14
             w_aux = mul(Rt, w_aux, thr);
             // line 15
             wdot = mul(Rt, wdot, thr);
             PZ temp(3, 1);
-            temp.addOneDimPZ(traj->qd_des[i * T + t], ax, 0, thr);
+            temp.addOneDimPZ(zqd, ax, 0, thr);
             wdot = add(wdot, cross_pp(w_aux, temp, thr), thr);
-            wdot.addOneDimPZ(traj->qdda_des[i * T + t], ax, 0, thr);
-            w_aux.addOneDimPZ(traj->qda_des[i * T + t], ax, 0, thr);
+            wdot.addOneDimPZ(zqdda, ax, 0, thr);
+            w_aux.addOneDimPZ(zqda, ax, 0, thr);
         } else {
             w_aux = mul(Rt, w_aux, thr);
             wdot = mul(Rt, wdot, thr);
@@ -100,7 +106,9 @@ void KinDyn::rnea(int t, const std::vector<PZ>& mass_arr, const std::vector<PZ>&
         // line 28
         f = add(mul(R1, f, thr), F[i], thr);
         if (r.axes[i] != 0) {
+            // the generalised torque is the moment along the joint axis: -n[a] for axis code -a
             PZ ui = n.elem(std::abs(r.axes[i]) - 1, 0);
+            if (r.axes[i] < 0) ui = scale(-1.0, ui);
             ui = add(ui, scale(r.armature[i], traj->qdda_des[i * T + t]), thr);
             ui = add(ui, scale(r.damping[i], traj->qd_des[i * T + t]), thr);
             u[i * T + t] = ui;

@@ -120,9 +120,12 @@ PZ PZ::rpy(double roll, double pitch, double yaw) {
 }
 
 // PZsparse.cu:211-250
+// A negative axis code -a (not in the reference) is the joint about -e_a: Rot(e_a, -q), that is
+// cos(-q) = cos q in the cosine entries and sin(-q) = -sin q in the sine entries.
 static void makeRotationMatrix(double* R, double cosElt, double sinElt, int axis, bool startFromZero) {
     for (int e = 0; e < 9; e++) R[e] = 0.0;
     if (!startFromZero) { R[0] = 1.0; R[4] = 1.0; R[8] = 1.0; }
+    if (axis < 0) { axis = -axis; sinElt = -sinElt; }
     const double negSinElt = -1.0 * sinElt;
     switch (axis) {
         case 0: return;

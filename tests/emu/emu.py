@@ -30,6 +30,32 @@ def set_robot(robot_struct=None):
     NJ = int(robot_struct.num_joints) if robot_struct is not None else 7
 
 
+def program(robot_struct=None, fused=True):
+    """[nops, 6] int array (code, o, a, b, c, i) of the reach program ProgramBuilder builds for the
+    robot tables (None: the built-in Kinova Gen3)"""
+    r = ctypes.byref(robot_struct) if robot_struct is not None else None
+    n = lib().emu_program_robot(r, 0 if fused else 1, None, 0)
+    if n < 0:
+        raise ValueError("invalid robot tables")
+    out = np.zeros((n, 6), np.int32)
+    lib().emu_program_robot(r, 0 if fused else 1, _p(out), n)
+    return out
+
+
+MAX_SLOTS = 96       # pz_engine.h: handle slots of a reach program
+POOL_DOUBLES = 1024  # reach_kernel.hip: the per-job engine's LDS payload pool
+
+
+def program_size(robot_struct=None):
+    """(handle slots, payload doubles) the reach program of the robot tables needs; a planner is
+    refused above MAX_SLOTS, and on the per-job engine above POOL_DOUBLES (planner.hip)"""
+    r = ctypes.byref(robot_struct) if robot_struct is not None else None
+    ns, pool = ctypes.c_int(), ctypes.c_int()
+    if lib().emu_program_size(r, ctypes.byref(ns), ctypes.byref(pool)) != 0:
+        raise ValueError("invalid robot tables")
+    return ns.value, pool.value
+
+
 def reach_job(world, T, t, fused=True):
     """Outputs of job (world, t) as the kernel writes them (fused: the program's cross products
     as single ops, else composed from views / products / differences / stack)."""

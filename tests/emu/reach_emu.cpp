@@ -104,9 +104,38 @@ extern "C" int emu_reach(int T, int t, const double* q0, const double* qd0, cons
 }
 
 // the op program (code, o, a, b, c, i) of the fused (or composed) build, for analysis tools
+static int program_of(const RobotParams& rp, int unfused, int* out, int cap);
 extern "C" int emu_program(int unfused, int* out, int cap) {
     static RobotParams rp;
     kinova_gen3(rp);
+    return program_of(rp, unfused, out, cap);
+}
+// the same for robot tables (null: the built-in Kinova Gen3); -1: invalid tables
+extern "C" int emu_program_robot(const armour_robot* r, int unfused, int* out, int cap) {
+    static RobotParams rp;
+    if (r) {
+        if (!robot_from_tables(*r, rp)) return -1;
+    } else {
+        kinova_gen3(rp);
+    }
+    return program_of(rp, unfused, out, cap);
+}
+// what the program of the robot tables needs of the kernels' fixed capacities: handle slots
+// (MAX_SLOTS) and payload doubles (the per-job engine's LDS pool); -1: invalid tables
+extern "C" int emu_program_size(const armour_robot* r, int* nslots, int* pool_doubles) {
+    static RobotParams rp;
+    if (r) {
+        if (!robot_from_tables(*r, rp)) return -1;
+    } else {
+        kinova_gen3(rp);
+    }
+    ProgramBuilder pb;
+    pb.build(rp);
+    *nslots = pb.nslots;
+    pb.slot_offsets(pool_doubles);
+    return 0;
+}
+static int program_of(const RobotParams& rp, int unfused, int* out, int cap) {
     ProgramBuilder pb;
     pb.fused = !unfused;
     pb.build(rp);

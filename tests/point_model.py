@@ -55,14 +55,29 @@ def bezier(beta, t, duration=1.0):
 
 
 # ---- rotations ----------------------------------------------------------------------------------
+def axis_vector(axis):
+    """unit vector of a joint axis code: e_x / e_y / e_z for 1 / 2 / 3, -e_a for -a (a reversed
+    joint, URDF <axis xyz="0 0 -1"/>), zero for 0 (a fixed joint)"""
+    z = np.zeros(3)
+    if axis != 0:
+        z[abs(axis) - 1] = 1.0 if axis > 0 else -1.0
+    return z
+
+
 def rot_axis(axis, q):
-    """[N, 3, 3] rotation about x / y / z (axis 1 / 2 / 3; 0: identity, a fixed joint)"""
+    """[N, 3, 3] rotation by q about x / y / z (axis 1 / 2 / 3; 0: identity, a fixed joint). A
+    negative code -a is the rotation by q about the unit vector u = -e_a, by Rodrigues' formula
+    I + sin q [u]x + (1 - cos q) [u]x^2 (the definition, not Rot(e_a, -q) by substitution)"""
     q = np.asarray(q, dtype=np.float64)
     R = np.zeros(q.shape + (3, 3))
     R[...] = np.eye(3)
     if axis == 0:
         return R
-    a, b = [(1, 2), (2, 0), (0, 1)][abs(axis) - 1]
+    if axis < 0:
+        u = axis_vector(axis)
+        K = np.array([[0.0, -u[2], u[1]], [u[2], 0.0, -u[0]], [-u[1], u[0], 0.0]])
+        return R + np.sin(q)[..., None, None] * K + (1 - np.cos(q))[..., None, None] * (K @ K)
+    a, b = [(1, 2), (2, 0), (0, 1)][axis - 1]
     c, s = np.cos(q), np.sin(q)
     R[..., a, a] = c
     R[..., b, b] = c
@@ -138,8 +153,7 @@ def rnea(robot, q, qd, qda, qdda, mass=None, inertia=None):
         wd = np.einsum("nij,nj->ni", Rt, wd)
         ax = int(robot["axes"][i])
         if ax != 0:
-            z = np.zeros(3)
-            z[abs(ax) - 1] = 1.0
+            z = axis_vector(ax)   # the joint's angular rates lie along its (signed) axis
             w = w + qd[:, i, None] * z
             wd = wd + np.cross(wa, qd[:, i, None] * z) + qdda[:, i, None] * z
             wa = wa + qda[:, i, None] * z
@@ -157,7 +171,8 @@ def rnea(robot, q, qd, qda, qdda, mass=None, inertia=None):
         f = Rf + F[i]
         ax = int(robot["axes"][i])
         if ax != 0 and i < nq:
-            u[:, i] = n[:, abs(ax) - 1] + robot["armature"][i] * qdda[:, i] + robot["damping"][i] * qd[:, i]
+            # generalised torque: the moment along the (signed) joint axis
+            u[:, i] = n @ axis_vector(ax) + robot["armature"][i] * qdda[:, i] + robot["damping"][i] * qd[:, i]
     return u
 
 
