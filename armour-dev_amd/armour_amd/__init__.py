@@ -108,6 +108,10 @@ def lib():
                                                        ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = args
+        for name, args in (("armour_check_world", [ctypes.POINTER(World), ctypes.c_int]),
+                           ("armour_check_armtd_world", [ctypes.POINTER(ArmtdWorld), ctypes.c_int, ctypes.c_int])):
+            if hasattr(L, name):
+                getattr(L, name).argtypes = args
         L.armour_plan.argtypes = [ctypes.c_void_p, ctypes.POINTER(World), ctypes.POINTER(PlanOutput)]
         L.armour_eval_constraints.argtypes = [ctypes.c_void_p, ctypes.c_int, _dp, _dp, _dp]
         L.armour_get_reach_program.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
@@ -139,7 +143,7 @@ ABI_SYMBOLS = ["armour_copy_bandwidth", "armour_create", "armour_create_robot", 
                "armour_create_armtd", "armour_plan_armtd_batch", "armour_reach_armtd_batch",
                "armour_get_plane_cache_stats", "armour_plan", "armour_get_reach_span",
                "armour_plan_batch_mixed", "armour_reach_batch_mixed", "armour_world_num_obstacles",
-               "armour_eval_candidates", "armour_sq_selfcheck"]
+               "armour_eval_candidates", "armour_sq_selfcheck", "armour_check_world", "armour_check_armtd_world"]
 
 
 def default_batch(T: int, device: int = 0, waves: int = 2) -> int:
@@ -168,6 +172,37 @@ def sq_selfcheck(thr: float, half_width: int, values=None, device: int = 0):
     _check(lib().armour_sq_selfcheck(device, float(thr), int(half_width), _ptr(v) if v.size else None, v.size,
                                      ctypes.byref(s), ctypes.byref(ok), ctypes.byref(bad)))
     return s.value, bool(ok.value), int(bad.value)
+
+
+def check_world(world, max_obstacles=40):
+    """armour_check_world on (q0, qd0, qdd0, q_des, obstacles[O, 12]): None when the world lies inside
+    the input domain (include/armour_hip.h), else the library's message, which names the field. Runs
+    on the host; no device is touched."""
+    w = World()
+    for k, f in enumerate(("q0", "qd0", "qdd0", "q_des")):
+        getattr(w, f)[:] = [float(v) for v in world[k]]
+    obs = np.ascontiguousarray(np.asarray(world[4], dtype=np.float64).reshape(-1, 12))
+    w.num_obstacles = obs.shape[0]
+    w.obstacles = _ptr(obs) if obs.shape[0] else None
+    rc = lib().armour_check_world(ctypes.byref(w), int(max_obstacles))
+    return None if rc == 0 else lib().armour_last_error().decode()
+
+
+def check_armtd_world(world, T, max_obstacles=40):
+    """armour_check_armtd_world on (q0, qd0, q_des, jrs_tables[7, 6, T], k_range, obstacles[O, 12])"""
+    q0, qd0, q_des, tab, kr, obs = world
+    a = ArmtdWorld()
+    a.q0[:] = [float(v) for v in q0]
+    a.qd0[:] = [float(v) for v in qd0]
+    a.q_des[:] = [float(v) for v in q_des]
+    a.k_range[:] = [float(v) for v in kr]
+    t = np.ascontiguousarray(np.asarray(tab, dtype=np.float64).reshape(NF, 6, T))
+    o = np.ascontiguousarray(np.asarray(obs, dtype=np.float64).reshape(-1, 12))
+    a.jrs_tables = _ptr(t)
+    a.num_obstacles = o.shape[0]
+    a.obstacles = _ptr(o) if o.shape[0] else None
+    rc = lib().armour_check_armtd_world(ctypes.byref(a), int(max_obstacles), int(T))
+    return None if rc == 0 else lib().armour_last_error().decode()
 
 
 def _check(rc):
@@ -484,4 +519,4 @@ class ArmtdPlanner(Planner):
         return lib().armour_reach_armtd_batch(*a)
 
 
-__all__ = ["ArmtdPlanner", "Planner", "ArmourError", "ARMOUR_E_CAPACITY", "ARMOUR_E_INTERNAL", "copy_bandwidth", "default_batch", "make_world", "example_world", "csv_world", "straight_line_waypoint", "KINOVA", "LIB_PATH", "ABI_SYMBOLS", "candidates_array"]
+__all__ = ["ArmtdPlanner", "Planner", "ArmourError", "ARMOUR_E_CAPACITY", "ARMOUR_E_INTERNAL", "copy_bandwidth", "default_batch", "make_world", "example_world", "csv_world", "straight_line_waypoint", "KINOVA", "LIB_PATH", "ABI_SYMBOLS", "candidates_array", "check_world", "check_armtd_world"]

@@ -104,6 +104,7 @@ struct Lib {
     decltype(&armour_plan) plan;
     decltype(&armour_num_joints) num_joints;
     decltype(&armour_num_constraints) num_constraints;
+    decltype(&armour_check_world) check_world;
 
     bool load(std::string& why) {
         const char* env = std::getenv("ARMOUR_LIB");
@@ -124,6 +125,7 @@ struct Lib {
         sym(plan, "armour_plan");
         sym(num_joints, "armour_num_joints");
         sym(num_constraints, "armour_num_constraints");
+        sym(check_world, "armour_check_world");
         if (!ok) why = "libarmour_hip.so lacks an armour_* symbol";
         return ok;
     }
@@ -219,6 +221,14 @@ int plan_dir(const Lib& L, armour_planner* served, const std::string& dir, int c
         for (double& v : obs) is >> v;
     }
 
+    armour_world w;
+    for (int i = 0; i < NF; i++) { w.q0[i] = q0[i]; w.qd0[i] = qd0[i]; w.qdd0[i] = qdd0[i]; w.q_des[i] = qdes[i]; }
+    w.num_obstacles = O;
+    w.obstacles = O > 0 ? obs.data() : nullptr;
+    // a world outside the input domain (armour_hip.h: a value that is not finite, an angle beyond
+    // ARMOUR_MAX_ABS_ANGLE) is a failed replan like unreadable input, before any device is touched
+    if (L.check_world(&w, MAX_OBSTACLES) != 0) return fail(L.last_error());
+
     const int T = time_steps();
     armour_planner* p = served;
     if (!p) {
@@ -231,11 +241,6 @@ int plan_dir(const Lib& L, armour_planner* served, const std::string& dir, int c
         armour_planner* p;
         ~Owned() { if (p) L.destroy(p); }
     } owned{L, served ? nullptr : p};
-
-    armour_world w;
-    for (int i = 0; i < NF; i++) { w.q0[i] = q0[i]; w.qd0[i] = qd0[i]; w.qdd0[i] = qdd0[i]; w.q_des[i] = qdes[i]; }
-    w.num_obstacles = O;
-    w.obstacles = O > 0 ? obs.data() : nullptr;
 
     // one plan through the single-world entry (armour_plan): the result and the payloads of the
     // five .out files

@@ -26,13 +26,23 @@ __device__ inline double div_dn(double a, double b) {
     const double r = fma(-q, b, a);  // a - q*b exactly
     return (r != 0 && ((r < 0) != (b < 0))) ? nextafter(q, -__builtin_inf()) : q;
 }
+// The residual a - s*s is about a * 2^-53: below a = 2^-969 it would be subnormal and lose the bits
+// that decide the step. Such radicands are scaled by 4^100 first (exact, as is scaling the root back);
+// every other value goes through unscaled. (No recursion: these inline into the reach kernels.)
+constexpr double SQRT_TINY = 0x1p-900;
 __device__ inline double sqrt_dn(double a) {
-    const double s = sqrt(a);
-    return fma(-s, s, a) < 0 ? nextafter(s, -__builtin_inf()) : s;
+    const bool tiny = a > 0 && a < SQRT_TINY;
+    const double x = tiny ? a * 0x1p200 : a;
+    const double s = sqrt(x);
+    const double r = fma(-s, s, x) < 0 ? nextafter(s, -__builtin_inf()) : s;
+    return tiny ? r * 0x1p-100 : r;
 }
 __device__ inline double sqrt_up(double a) {
-    const double s = sqrt(a);
-    return fma(-s, s, a) > 0 ? nextafter(s, __builtin_inf()) : s;
+    const bool tiny = a > 0 && a < SQRT_TINY;
+    const double x = tiny ? a * 0x1p200 : a;
+    const double s = sqrt(x);
+    const double r = fma(-s, s, x) > 0 ? nextafter(s, __builtin_inf()) : s;
+    return tiny ? r * 0x1p-100 : r;
 }
 #else
 inline double rnd_op(int mode, int op, double a, double b) {

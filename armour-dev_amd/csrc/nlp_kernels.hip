@@ -340,10 +340,15 @@ __device__ double extremum_grad(int kind, int id, double e2, double e3) {
     const double r = id == 2 ? e2 : e3;
     return kind == 0 ? r * r * r * (6 * r * r - 15 * r + 10) : 30 * r * r * (r - 1) * (r - 1);
 }
+// one step per turn, as the reference (NLPclass.cu:6-15). Inside the input domain (|q_des| and |q|
+// within ARMOUR_MAX_ABS_ANGLE, which the entries check before a launch) the difference is below
+// 2e4 rad, under 3200 turns; WRAP_MAX_TURNS only ends the loop for a value that could never end it
+// (not finite, or so large that a step of 2 pi changes nothing)
+constexpr int WRAP_MAX_TURNS = 4096;
 __device__ double wrap_to_pi(double a) {
     double w = a;
-    while (w < -M_PI) w += 2 * M_PI;
-    while (w > M_PI) w -= 2 * M_PI;
+    for (int n = 0; n < WRAP_MAX_TURNS && w < -M_PI; n++) w += 2 * M_PI;
+    for (int n = 0; n < WRAP_MAX_TURNS && w > M_PI; n++) w -= 2 * M_PI;
     return w;
 }
 

@@ -8,6 +8,7 @@
 // the host only sequences launches and reads one flag word per line-search round.
 #include <hip/hip_runtime.h>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -581,8 +582,55 @@ static int planner_init(armour_planner* p, const armour_config* cfg, const armou
     return 0;
 }
 
+// The input domain of a world (include/armour_hip.h, armour_check_world): every value finite and the
+// angles within ARMOUR_MAX_ABS_ANGLE. Host-side, O(O) per world; every planning and reach entry runs it
+// on every world before anything is copied or launched (wrap_to_pi's loop in nlp_kernels.hip is
+// bounded only for such values).
+static int check_values(const char* field, const double* v, int n, double max_abs) {
+    for (int i = 0; i < n; i++) {
+        char buf[160];
+        if (!std::isfinite(v[i])) {
+            std::snprintf(buf, sizeof(buf), "%s[%d] is not finite", field, i);
+            return fail(ARMOUR_E_ARG, buf);
+        }
+        if (max_abs > 0 && std::fabs(v[i]) > max_abs) {
+            std::snprintf(buf, sizeof(buf), "%s[%d] = %g lies outside +-%g (ARMOUR_MAX_ABS_ANGLE)", field, i, v[i], max_abs);
+            return fail(ARMOUR_E_ARG, buf);
+        }
+    }
+    return 0;
+}
+static int check_obstacles(int n, const double* obstacles, int max_obstacles) {
+    if (n < 0 || n > max_obstacles) return fail(ARMOUR_E_ARG, "num_obstacles exceeds max_obstacles");
+    if (n > 0 && !obstacles) return fail(ARMOUR_E_ARG, "null obstacles");
+    return n > 0 ? check_values("obstacles", obstacles, n * ARMOUR_OBSTACLE_DOUBLES, 0.0) : 0;
+}
+static int check_world(const armour_world* w, int max_obstacles) {
+    if (!w) return fail(ARMOUR_E_ARG, "null world");
+    int rc;
+    if ((rc = check_values("q0", w->q0, NF, ARMOUR_MAX_ABS_ANGLE))) return rc;
+    if ((rc = check_values("qd0", w->qd0, NF, 0.0))) return rc;
+    if ((rc = check_values("qdd0", w->qdd0, NF, 0.0))) return rc;
+    if ((rc = check_values("q_des", w->q_des, NF, ARMOUR_MAX_ABS_ANGLE))) return rc;
+    return check_obstacles(w->num_obstacles, w->obstacles, max_obstacles);
+}
+static int check_armtd_world(const armour_armtd_world* w, int max_obstacles, int T) {
+    if (!w) return fail(ARMOUR_E_ARG, "null world");
+    if (T <= 0) return fail(ARMOUR_E_ARG, "num_time_steps must be positive");
+    if (!w->jrs_tables) return fail(ARMOUR_E_ARG, "null jrs_tables");
+    int rc;
+    if ((rc = check_values("q0", w->q0, NF, ARMOUR_MAX_ABS_ANGLE))) return rc;
+    if ((rc = check_values("qd0", w->qd0, NF, 0.0))) return rc;
+    if ((rc = check_values("q_des", w->q_des, NF, ARMOUR_MAX_ABS_ANGLE))) return rc;
+    if ((rc = check_values("k_range", w->k_range, NF, 0.0))) return rc;
+    if ((rc = check_values("jrs_tables", w->jrs_tables, NF * 6 * T, 0.0))) return rc;
+    return check_obstacles(w->num_obstacles, w->obstacles, max_obstacles);
+}
+
 static int upload_worlds(armour_planner* p, int W, const armour_world* worlds) {
     if (W <= 0 || W > p->Wmax || !worlds) return fail(ARMOUR_E_ARG, "num_worlds out of range");
+    for (int w = 0; w < W; w++)
+        if (const int rc = check_world(&worlds[w], p->Omax)) return rc;
     const int O = worlds[0].num_obstacles;
     if (O < 0 || O > p->Omax) return fail(ARMOUR_E_ARG, "num_obstacles exceeds max_obstacles");
     std::vector<double> a(4 * (size_t)W * NF), ob((size_t)W * (O > 0 ? O : 1) * 12, 0.0);
@@ -626,6 +674,8 @@ static int upload_worlds_mixed(armour_planner* p, int W, const armour_world* wor
     if (p->armtd) return fail(ARMOUR_E_ARG, "mixed batches are not available on an ARMTD planner");
     if (p->eval_f32) return fail(ARMOUR_E_ARG, "mixed batches are not available with the fp32 study (ARMOUR_EVAL_F32)");
     if (W <= 0 || W > p->Wmax || !worlds) return fail(ARMOUR_E_ARG, "num_worlds out of range");
+    for (int w = 0; w < W; w++)
+        if (const int rc = check_world(&worlds[w], p->Omax)) return rc;
     int O = 0;
     for (int w = 0; w < W; w++) {
         const int n = worlds[w].num_obstacles;
@@ -672,6 +722,8 @@ static int upload_worlds_mixed(armour_planner* p, int W, const armour_world* wor
 static int upload_armtd(armour_planner* p, int W, const armour_armtd_world* worlds) {
     if (!p->armtd) return fail(ARMOUR_E_ARG, "not an ARMTD planner (armour_create_armtd)");
     if (W <= 0 || W > p->Wmax || !worlds) return fail(ARMOUR_E_ARG, "num_worlds out of range");
+    for (int w = 0; w < W; w++)
+        if (const int rc = check_armtd_world(&worlds[w], p->Omax, p->T)) return rc;
     std::vector<armour_world> base(W);
     const size_t ntab = (size_t)NF * 6 * p->T;
     std::vector<double> tab((size_t)W * ntab), kr((size_t)W * NF);
@@ -1518,6 +1570,11 @@ int armour_plan(armour_planner* p, const armour_world* world, armour_plan_output
     if (out->link_generators && (rc = armour_get_link_generators(p, 0, out->link_generators))) return rc;
     if (out->torque_radius && (rc = armour_get_torque_radius(p, 0, out->torque_radius))) return rc;
     return 0;
+}
+
+int armour_check_world(const armour_world* world, int max_obstacles) { return check_world(world, max_obstacles); }
+int armour_check_armtd_world(const armour_armtd_world* world, int max_obstacles, int num_time_steps) {
+    return check_armtd_world(world, max_obstacles, num_time_steps);
 }
 
 int armour_num_constraints(const armour_planner* p, int O) { return p ? p->d.nt + p->T * p->NJ * O + NF * 4 : ARMOUR_E_ARG; }

@@ -93,14 +93,18 @@ __host__ __device__ __attribute__((noinline)) JrsJoint jrs_joint(const RobotPara
     const double s_lb = s_ind * ds, s_ub = (s_ind + 1) * ds;
     const double kr = rp.k_range[i];
     JrsJoint J;
+    // The rates do not depend on q0, but their Bernstein differences round q0 + ..., an error that
+    // grows with |q0|. Beyond one turn (outside [-pi, pi], where continuous joints used to start) they
+    // are taken about q0 = 0; inside, as before, so those results keep their bits.
+    const double qr = fabs(q0) > M_PI ? 0.0 : q0;
     // k-independent extrema (Trajectory.cu:36-58)
     double qe1, qe2, qde1, qde2, qdde1, qdde2;
     q_roots(Tqd0, TTqdd0, 0.0, &qe1, &qe2);
     qd_roots(Tqd0, TTqdd0, 0.0, &qde1, &qde2);
     qdd_roots_k0(Tqd0, TTqdd0, &qdde1, &qdde2);
     const double qv1 = bz_q(q0, Tqd0, TTqdd0, 0.0, qe1), qv2 = bz_q(q0, Tqd0, TTqdd0, 0.0, qe2);
-    const double qdv1 = bz_qd(q0, Tqd0, TTqdd0, 0.0, qde1) / D, qdv2 = bz_qd(q0, Tqd0, TTqdd0, 0.0, qde2) / D;
-    const double qddv1 = bz_qdd(q0, Tqd0, TTqdd0, 0.0, qdde1) / (D * D), qddv2 = bz_qdd(q0, Tqd0, TTqdd0, 0.0, qdde2) / (D * D);
+    const double qdv1 = bz_qd(qr, Tqd0, TTqdd0, 0.0, qde1) / D, qdv2 = bz_qd(qr, Tqd0, TTqdd0, 0.0, qde2) / D;
+    const double qddv1 = bz_qdd(qr, Tqd0, TTqdd0, 0.0, qdde1) / (D * D), qddv2 = bz_qdd(qr, Tqd0, TTqdd0, 0.0, qdde2) / (D * D);
 
     // Part 1: q_des
     double kc_lb = s_lb * s_lb * s_lb * (6 * s_lb * s_lb - 15 * s_lb + 10);
@@ -141,7 +145,7 @@ __host__ __device__ __attribute__((noinline)) JrsJoint jrs_joint(const RobotPara
     if (kc_ub < kc_lb) { const double t = kc_lb; kc_lb = kc_ub; kc_ub = t; }
     kdc = (kc_ub + kc_lb) * 0.5 * kr;
     kdr = (kc_ub - kc_lb) * 0.5 * kr;
-    bound_k_indep(bz_qd(q0, Tqd0, TTqdd0, 0.0, s_lb) / D, bz_qd(q0, Tqd0, TTqdd0, 0.0, s_ub) / D, s_lb, s_ub, qde1, qdv1, qde2, qdv2, &ki_lb, &ki_ub);
+    bound_k_indep(bz_qd(qr, Tqd0, TTqdd0, 0.0, s_lb) / D, bz_qd(qr, Tqd0, TTqdd0, 0.0, s_ub) / D, s_lb, s_ub, qde1, qdv1, qde2, qdv2, &ki_lb, &ki_ub);
     kir = (ki_ub - ki_lb) * 0.5;
     J.qd_c = (ki_lb + ki_ub) * 0.5;
     J.qd_k = kdc;
@@ -158,7 +162,7 @@ __host__ __device__ __attribute__((noinline)) JrsJoint jrs_joint(const RobotPara
     else { kc_lb = tl; kc_ub = tu; }
     kdc = (kc_ub + kc_lb) * 0.5 * kr;
     kdr = (kc_ub - kc_lb) * 0.5 * kr;
-    bound_k_indep(bz_qdd(q0, Tqd0, TTqdd0, 0.0, s_lb) / (D * D), bz_qdd(q0, Tqd0, TTqdd0, 0.0, s_ub) / (D * D), s_lb, s_ub, qdde1, qddv1, qdde2, qddv2, &ki_lb, &ki_ub);
+    bound_k_indep(bz_qdd(qr, Tqd0, TTqdd0, 0.0, s_lb) / (D * D), bz_qdd(qr, Tqd0, TTqdd0, 0.0, s_ub) / (D * D), s_lb, s_ub, qdde1, qddv1, qdde2, qddv2, &ki_lb, &ki_ub);
     kir = (ki_ub - ki_lb) * 0.5;
     J.qdd_c = (ki_lb + ki_ub) * 0.5;
     J.qdd_k = kdc;

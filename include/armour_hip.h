@@ -138,6 +138,20 @@ const char* armour_last_error(void);
  * planners NJ*T*O + 28 (ACMP/NLPclass.cu:45-46) */
 int armour_num_constraints(const armour_planner* p, int num_obstacles);
 
+/* The input domain. Every entry that takes worlds (armour_plan, armour_plan_batch, armour_reach_batch,
+ * their _mixed forms and the two ARMTD entries) checks every world with armour_check_world /
+ * armour_check_armtd_world before it copies or launches anything, and returns ARMOUR_E_ARG with a
+ * message that names the field otherwise. A world is inside the domain when
+ *   - every q0, qd0, qdd0, q_des and obstacle entry is finite (ARMTD: q0, qd0, q_des, k_range and
+ *     every entry of jrs_tables [7][6][num_time_steps] and of the obstacles),
+ *   - every |q0| and |q_des| is at most ARMOUR_MAX_ABS_ANGLE (continuous joints carry +-1000 rad
+ *     bounds, so nothing beyond is feasible; the cost's wrap to [-pi, pi] of a continuous joint takes
+ *     one step per turn and is bounded for such values),
+ *   - 0 <= num_obstacles <= max_obstacles, with a non-null obstacles pointer when it is positive.
+ * Both checks run on the host and touch no device. */
+#define ARMOUR_MAX_ABS_ANGLE 1e4
+int armour_check_world(const armour_world* world, int max_obstacles);
+
 /* Plan a batch (all worlds must carry the same number of obstacles). Replaces
  * armour_main.cu:87-316 for each world. */
 int armour_plan_batch(armour_planner* p, int num_worlds, const armour_world* worlds, armour_result* results,
@@ -188,6 +202,9 @@ typedef struct armour_armtd_world {
     int num_obstacles;
     const double* obstacles;   /* [num_obstacles][12] */
 } armour_armtd_world;
+
+/* armour_check_world for an ARMTD world of a planner with num_time_steps intervals */
+int armour_check_armtd_world(const armour_armtd_world* world, int max_obstacles, int num_time_steps);
 
 /* an ARMTD planner (the reference's NUM_TIME_STEPS is 100, ACMP/Parameters.h:17; solver tolerance
  * 1e-7, :42); armour_num_constraints gives 7*T*O + 28, the getters work as for armour_create */

@@ -143,8 +143,10 @@ void Planner::bounds(double* g_l, double* g_u) const {
 
 static double wrap_to_pi(double a) {  // NLPclass.cu:6-15
     double w = a;
-    while (w < -M_PI) w += 2 * M_PI;
-    while (w > M_PI) w -= 2 * M_PI;
+    // one step per turn as the reference; bounded so that a value outside the input domain
+    // (include/armour_hip.h: not finite, or beyond any angle a step of 2 pi changes) ends it
+    for (int n = 0; n < 4096 && w < -M_PI; n++) w += 2 * M_PI;
+    for (int n = 0; n < 4096 && w > M_PI; n++) w -= 2 * M_PI;
     return w;
 }
 

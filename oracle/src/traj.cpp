@@ -95,8 +95,11 @@ double qd_des_extrema3_k_derivative(double q0, double Tqd0, double TTqdd0, doubl
 }
 
 double q_des_k_indep(double q0, double Tqd0, double TTqdd0, double s) { return q_des_func(q0, Tqd0, TTqdd0, 0.0, s); }
-double qd_des_k_indep(double q0, double Tqd0, double TTqdd0, double s, double D) { return qd_des_func(q0, Tqd0, TTqdd0, 0.0, s) / D; }
-double qdd_des_k_indep(double q0, double Tqd0, double TTqdd0, double s, double D) { return qdd_des_func(q0, Tqd0, TTqdd0, 0.0, s) / (D * D); }
+// the rates do not depend on q0; beyond [-pi, pi] they are taken about q0 = 0, so that the rounding of
+// q0 + ... in the Bernstein differences does not grow with |q0| (inside: as before, bit for bit)
+static inline double rate_origin(double q0) { return std::fabs(q0) > M_PI ? 0.0 : q0; }
+double qd_des_k_indep(double q0, double Tqd0, double TTqdd0, double s, double D) { return qd_des_func(rate_origin(q0), Tqd0, TTqdd0, 0.0, s) / D; }
+double qdd_des_k_indep(double q0, double Tqd0, double TTqdd0, double s, double D) { return qdd_des_func(rate_origin(q0), Tqd0, TTqdd0, 0.0, s) / (D * D); }
 
 // Trajectory.cu:15-61
 Bezier::Bezier(const Robot& r, const Params& p, const double* q0_, const double* qd0_, const double* qdd0_)
