@@ -65,6 +65,23 @@ class Timing(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class EpisodeConfig(ctypes.Structure):
+    """armour_episode_config (include/armour_hip.h)"""
+    _fields_ = [("lookahead", ctypes.c_double), ("goal_radius", ctypes.c_double), ("check_samples", ctypes.c_int)]
+
+
+class EpisodeState(ctypes.Structure):
+    """armour_episode_state (include/armour_hip.h)"""
+    _fields_ = [("q", ctypes.c_double * NF), ("qd", ctypes.c_double * NF), ("qdd", ctypes.c_double * NF),
+                ("q_des", ctypes.c_double * NF), ("status", ctypes.c_int), ("mode", ctypes.c_int),
+                ("steps", ctypes.c_int), ("failed_plans", ctypes.c_int), ("failed_streak", ctypes.c_int),
+                ("clearance", ctypes.c_double), ("clearance_at", ctypes.c_int * 3), ("goal_distance", ctypes.c_double)]
+
+
+T_PLAN = 0.5  # ARMOUR_T_PLAN
+EPISODE_STATUS = ("running", "goal reached", "collided", "no fail-safe", "left the input domain")
+
+
 class PlanOutput(ctypes.Structure):
     """armour_plan_output (include/armour_hip.h): the single-world entry's result and the caller's
     output arrays (null: skipped)"""
@@ -108,6 +125,16 @@ def lib():
                                                        ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = args
+        ip = ctypes.POINTER(ctypes.c_int)
+        for name, args in (("armour_check_motion", [ctypes.c_void_p, _dp, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                                    _dp, ip]),
+                           ("armour_episode_begin", [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(World), _dp,
+                                                     ctypes.POINTER(EpisodeConfig)]),
+                           ("armour_episode_step", [ctypes.c_void_p, ip, ctypes.POINTER(Result), ctypes.POINTER(Timing),
+                                                    _dp]),
+                           ("armour_episode_get", [ctypes.c_void_p, ctypes.POINTER(EpisodeState)])):
+            if hasattr(L, name):
+                getattr(L, name).argtypes = args
         for name, args in (("armour_check_world", [ctypes.POINTER(World), ctypes.c_int]),
                            ("armour_check_armtd_world", [ctypes.POINTER(ArmtdWorld), ctypes.c_int, ctypes.c_int])):
             if hasattr(L, name):
@@ -143,7 +170,8 @@ ABI_SYMBOLS = ["armour_copy_bandwidth", "armour_create", "armour_create_robot", 
                "armour_create_armtd", "armour_plan_armtd_batch", "armour_reach_armtd_batch",
                "armour_get_plane_cache_stats", "armour_plan", "armour_get_reach_span",
                "armour_plan_batch_mixed", "armour_reach_batch_mixed", "armour_world_num_obstacles",
-               "armour_eval_candidates", "armour_sq_selfcheck", "armour_check_world", "armour_check_armtd_world"]
+               "armour_eval_candidates", "armour_sq_selfcheck", "armour_check_world", "armour_check_armtd_world",
+               "armour_check_motion", "armour_episode_begin", "armour_episode_step", "armour_episode_get"]
 
 
 def default_batch(T: int, device: int = 0, waves: int = 2) -> int:
@@ -393,6 +421,66 @@ class Planner:
                                             best.ctypes.data_as(ip)))
         return dict(cost=cost, violation=viol, feasible=feas.astype(bool), best=best)
 
+    def check_motion(self, traj, t0=0.0, t1=1.0, samples=11):
+        """armour_check_motion: the smallest sampled separation between the arm and the obstacles of each
+        world of the last batch. traj [W, 4, 7]: q0, qd0, qdd0 and k (normalised) per world; the
+        trajectory is sampled at `samples` evenly spaced times in [t0, t1]. Returns (clearance [W],
+        where [W, 3]: sample, link, obstacle of the first minimiser; +inf and -1 without obstacles)."""
+        traj = np.ascontiguousarray(np.asarray(traj, dtype=np.float64))
+        if traj.ndim != 3 or traj.shape[1:] != (4, NF) or traj.shape[0] != self._W:
+            raise ValueError(f"check_motion: traj must have shape [W, 4, {NF}] (W = {self._W}), got {traj.shape}")
+        clear = np.zeros(self._W)
+        where = np.zeros((self._W, 3), dtype=np.int32)
+        _check(lib().armour_check_motion(self.h, _ptr(traj), float(t0), float(t1), int(samples), _ptr(clear),
+                                         where.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return clear, where
+
+    def episode_begin(self, worlds, goals, lookahead=0.1, goal_radius=np.pi / 30, check_samples=11):
+        """armour_episode_begin: start receding-horizon episodes of `worlds` (their q_des is ignored) toward
+        `goals` [W, 7]; returns the initial states (episode_states)"""
+        arr = self._worlds(worlds)
+        goals = np.ascontiguousarray(np.asarray(goals, dtype=np.float64))
+        if goals.shape != (len(worlds), NF):
+            raise ValueError(f"episode_begin: goals must have shape [{len(worlds)}, {NF}], got {goals.shape}")
+        cfg = EpisodeConfig(float(lookahead), float(goal_radius), int(check_samples))
+        _check(lib().armour_episode_begin(self.h, len(worlds), arr, _ptr(goals), ctypes.byref(cfg)))
+        return self.episode_states()
+
+    def episode_step(self, reject=None):
+        """armour_episode_step: plan every world from its pending state, execute, check and advance.
+        reject [W] (optional): worlds whose new plan the caller vetoes. Returns (running worlds,
+        results, timing) with results as plan_mixed's and timing's check_ms / advance_ms added."""
+        rj = None
+        if reject is not None:
+            rj = np.ascontiguousarray(np.asarray(reject).astype(np.int32))
+            if rj.shape != (self._W,):
+                raise ValueError(f"episode_step: reject must have shape [{self._W}], got {rj.shape}")
+        res = (Result * max(self._W, 1))()
+        tm = Timing()
+        ems = np.zeros(2)
+        n = lib().armour_episode_step(self.h, rj.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if rj is not None else None,
+                                      res, ctypes.byref(tm), _ptr(ems))
+        if n < 0:
+            _check(n)
+        t = self._span(tm.as_dict())
+        t["check_ms"], t["advance_ms"] = float(ems[0]), float(ems[1])
+        return n, self._results(res)[:self._W], t
+
+    def episode_states(self):
+        """armour_episode_get: dict of arrays over the worlds (q, qd, qdd, q_des [W, 7], status, mode, steps,
+        failed_plans, failed_streak [W], clearance [W], clearance_at [W, 3], goal_distance [W])"""
+        st = (EpisodeState * max(self._W, 1))()
+        _check(lib().armour_episode_get(self.h, st))
+        st = st[:self._W]
+        out = {k: np.array([getattr(s, k)[:] for s in st], dtype=np.float64).reshape(len(st), NF)
+               for k in ("q", "qd", "qdd", "q_des")}
+        for k in ("status", "mode", "steps", "failed_plans", "failed_streak"):
+            out[k] = np.array([getattr(s, k) for s in st], dtype=np.int64)
+        out["clearance"] = np.array([s.clearance for s in st], dtype=np.float64)
+        out["clearance_at"] = np.array([s.clearance_at[:] for s in st], dtype=np.int64).reshape(len(st), 3)
+        out["goal_distance"] = np.array([s.goal_distance for s in st], dtype=np.float64)
+        return out
+
     def constraints(self, w):
         g = np.zeros(self._m(w))
         _check(lib().armour_get_constraints(self.h, w, _ptr(g)))
@@ -482,6 +570,20 @@ class Planner:
         return r
 
 
+def run_episodes(planner, worlds, goals, max_steps, **config):
+    """Drive `worlds` toward `goals` [W, 7] with receding-horizon episodes on `planner` (episode_begin,
+    then episode_step until no world runs or max_steps steps were taken; config: lookahead,
+    goal_radius, check_samples). Returns dict(status, steps, clearance: [W] each)."""
+    st = planner.episode_begin(worlds, goals, **config)
+    running = int(np.sum(st["status"] == 0))
+    for _ in range(int(max_steps)):
+        if running == 0:
+            break
+        running, _, _ = planner.episode_step()
+    st = planner.episode_states()
+    return dict(status=st["status"], steps=st["steps"], clearance=st["clearance"])
+
+
 class ArmtdPlanner(Planner):
     """The ARMTD comparison planner (armour_create_armtd). A world is the content of one armtd.in:
     (q0, qd0, q_des, jrs_tables[7, 6, T], k_range[7], obstacles[O, 12]) with the tables per joint
@@ -519,4 +621,4 @@ class ArmtdPlanner(Planner):
         return lib().armour_reach_armtd_batch(*a)
 
 
-__all__ = ["ArmtdPlanner", "Planner", "ArmourError", "ARMOUR_E_CAPACITY", "ARMOUR_E_INTERNAL", "copy_bandwidth", "default_batch", "make_world", "example_world", "csv_world", "straight_line_waypoint", "KINOVA", "LIB_PATH", "ABI_SYMBOLS", "candidates_array", "check_world", "check_armtd_world"]
+__all__ = ["ArmtdPlanner", "Planner", "ArmourError", "ARMOUR_E_CAPACITY", "ARMOUR_E_INTERNAL", "copy_bandwidth", "default_batch", "make_world", "example_world", "csv_world", "straight_line_waypoint", "KINOVA", "LIB_PATH", "ABI_SYMBOLS", "candidates_array", "check_world", "check_armtd_world", "run_episodes", "EpisodeConfig", "EpisodeState", "T_PLAN", "EPISODE_STATUS"]

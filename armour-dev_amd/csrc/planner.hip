@@ -21,6 +21,7 @@
 #include "nlp_kernels.hip"
 #include "reach_kernel.hip"
 #include "lane_kernel.hip"
+#include "motion_kernels.hip"
 #include "robots.h"
 
 using namespace armour;
@@ -148,6 +149,19 @@ struct armour_planner {
     // first use, regrown when a call brings more candidates per world)
     CandDev cd{};
     int cand_cap = 0;
+    // armour_check_motion and the episodes (motion_kernels.hip): per-sample minima for max_worlds x
+    // motion_cap samples (allocated on first use, regrown for more samples), the caller's
+    // trajectories and the per-world results; the episode's own arrays, allocated by the first begin
+    double* mo_pval = nullptr;
+    int* mo_pidx = nullptr;
+    int motion_cap = 0;
+    double *mo_traj = nullptr, *mo_clear = nullptr;
+    int* mo_where = nullptr;
+    bool episode = false;      // an episode is running (armour_episode_begin .. any other reach / plan entry)
+    EpisodeDev ep{};
+    int* ep_accept = nullptr;
+    hipEvent_t ep_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    std::vector<armour_episode_state> ep_host;  // the states after the last begin / step
     std::vector<void*> allocs;
 
     template <class T>
@@ -1540,6 +1554,10 @@ void armour_destroy(armour_planner* p) {
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     for (void* a : p->allocs) (void)hipFree(a);
     cand_free(p->cd);
+    if (p->mo_pval) (void)hipFree(p->mo_pval);
+    if (p->mo_pidx) (void)hipFree(p->mo_pidx);
+    for (hipEvent_t e : p->ep_ev)
+        if (e) (void)hipEventDestroy(e);
     if (p->h_flags) (void)hipHostFree(p->h_flags);
     if (p->h_sum) (void)hipHostFree(p->h_sum);
     if (p->h_ws) (void)hipHostFree(p->h_ws);
@@ -1601,7 +1619,7 @@ int armour_reach_batch(armour_planner* p, int W, const armour_world* worlds, arm
     DeviceScope device_scope(p);
     if (!p) return fail(ARMOUR_E_ARG, "null planner");
     if (p->armtd) return fail(ARMOUR_E_ARG, "an ARMTD planner takes armour_armtd_world (armour_reach_armtd_batch)");
-    p->reached = p->planned = p->evaluated = false;
+    p->reached = p->planned = p->evaluated = p->episode = false;
     auto t0 = std::chrono::steady_clock::now();
     const int rc = upload_worlds(p, W, worlds);
     return rc ? rc : reach_uploaded(p, timing, t0);
@@ -1610,7 +1628,7 @@ int armour_reach_batch(armour_planner* p, int W, const armour_world* worlds, arm
 int armour_reach_armtd_batch(armour_planner* p, int W, const armour_armtd_world* worlds, armour_timing* timing) {
     DeviceScope device_scope(p);
     if (!p) return fail(ARMOUR_E_ARG, "null planner");
-    p->reached = p->planned = p->evaluated = false;
+    p->reached = p->planned = p->evaluated = p->episode = false;
     auto t0 = std::chrono::steady_clock::now();
     const int rc = upload_armtd(p, W, worlds);
     return rc ? rc : reach_uploaded(p, timing, t0);
@@ -1620,7 +1638,7 @@ int armour_plan_armtd_batch(armour_planner* p, int W, const armour_armtd_world* 
                             armour_timing* timing) {
     DeviceScope device_scope(p);
     if (!p || !results) return fail(ARMOUR_E_ARG, "null planner / results");
-    p->reached = p->planned = p->evaluated = false;
+    p->reached = p->planned = p->evaluated = p->episode = false;
     auto t0 = std::chrono::steady_clock::now();
     const int rc = upload_armtd(p, W, worlds);
     return rc ? rc : plan_uploaded(p, results, timing, t0);
@@ -1629,7 +1647,7 @@ int armour_plan_armtd_batch(armour_planner* p, int W, const armour_armtd_world* 
 int armour_reach_batch_mixed(armour_planner* p, int W, const armour_world* worlds, armour_timing* timing) {
     DeviceScope device_scope(p);
     if (!p) return fail(ARMOUR_E_ARG, "null planner");
-    p->reached = p->planned = p->evaluated = false;
+    p->reached = p->planned = p->evaluated = p->episode = false;
     auto t0 = std::chrono::steady_clock::now();
     const int rc = upload_worlds_mixed(p, W, worlds);
     return rc ? rc : reach_uploaded(p, timing, t0);
@@ -1639,7 +1657,7 @@ int armour_plan_batch_mixed(armour_planner* p, int W, const armour_world* worlds
                             armour_timing* timing) {
     DeviceScope device_scope(p);
     if (!p || !results) return fail(ARMOUR_E_ARG, "null planner / results");
-    p->reached = p->planned = p->evaluated = false;
+    p->reached = p->planned = p->evaluated = p->episode = false;
     auto t0 = std::chrono::steady_clock::now();
     const int rc = upload_worlds_mixed(p, W, worlds);
     return rc ? rc : plan_uploaded(p, results, timing, t0);
@@ -1674,7 +1692,7 @@ int armour_plan_batch(armour_planner* p, int W, const armour_world* worlds, armo
     DeviceScope device_scope(p);
     if (!p || !results) return fail(ARMOUR_E_ARG, "null planner / results");
     if (p->armtd) return fail(ARMOUR_E_ARG, "an ARMTD planner takes armour_armtd_world (armour_plan_armtd_batch)");
-    p->reached = p->planned = p->evaluated = false;
+    p->reached = p->planned = p->evaluated = p->episode = false;
     auto t0 = std::chrono::steady_clock::now();
     const int rc = upload_worlds(p, W, worlds);
     return rc ? rc : plan_uploaded(p, results, timing, t0);
@@ -1821,6 +1839,185 @@ int armour_eval_candidates(armour_planner* p, int N, const double* x, double* co
     if (feasible) HIPCK(hipMemcpyAsync(feasible, c.feas, sizeof(int) * n, hipMemcpyDeviceToHost, p->stream));
     if (best) HIPCK(hipMemcpyAsync(best, c.best, sizeof(int) * W, hipMemcpyDeviceToHost, p->stream));
     HIPCK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+// buffers of the execution check for S samples per world
+static int motion_reserve(armour_planner* p, int S) {
+    int rc = 0;
+    if (!p->mo_traj && ((rc = p->alloc(&p->mo_traj, (size_t)p->Wmax * TRAJ_DOUBLES)) ||
+                        (rc = p->alloc(&p->mo_clear, (size_t)p->Wmax)) || (rc = p->alloc(&p->mo_where, 3 * (size_t)p->Wmax))))
+        return rc;
+    if (S <= p->motion_cap) return 0;
+    HIPCK(hipStreamSynchronize(p->stream));
+    if (p->mo_pval) (void)hipFree(p->mo_pval);
+    if (p->mo_pidx) (void)hipFree(p->mo_pidx);
+    p->mo_pval = nullptr;
+    p->mo_pidx = nullptr;
+    p->motion_cap = 0;
+    if (dalloc(&p->mo_pval, (size_t)p->Wmax * S) != hipSuccess || dalloc(&p->mo_pidx, (size_t)p->Wmax * S) != hipSuccess)
+        return fail(ARMOUR_E_HIP, "hipMalloc failed for the execution check's buffers (max_worlds x samples)");
+    p->motion_cap = S;
+    return 0;
+}
+
+// the execution check of the resident batch over S samples of `traj` (device, [W][4][7]): per-world
+// windows `win` (device, [W][2]) or [t0, t1] for every world; results in mo_clear / mo_where
+static void launch_motion(armour_planner* p, const double* traj, const double* win, double t0, double t1, int S) {
+    MotionArgs a{};
+    a.rp = p->d_rp;
+    a.W = p->W;
+    a.S = S;
+    a.O = p->d.O;
+    a.Ow = p->d.Ow;
+    a.obs = p->obs;
+    a.traj = traj;
+    a.win = win;
+    a.t0 = t0;
+    a.t1 = t1;
+    a.pval = p->mo_pval;
+    a.pidx = p->mo_pidx;
+    hipLaunchKernelGGL(motion_check_kernel, dim3(S, p->W), dim3(MOTION_THREADS), 0, p->stream, a);
+    hipLaunchKernelGGL(motion_finish_kernel, dim3(p->W), dim3(64), 0, p->stream, a, p->mo_clear, p->mo_where);
+}
+
+int armour_check_motion(armour_planner* p, const double* traj, double t0, double t1, int samples, double* clearance,
+                        int* where) {
+    DeviceScope device_scope(p);
+    if (!p || !traj) return fail(ARMOUR_E_ARG, "null planner / traj");
+    if (p->armtd) return fail(ARMOUR_E_ARG, "the execution check is not available on an ARMTD planner");
+    if (p->eval_f32) return fail(ARMOUR_E_ARG, "the execution check is not available with the fp32 study (ARMOUR_EVAL_F32)");
+    if (samples < 1 || samples > 65535) return fail(ARMOUR_E_ARG, "samples must lie in 1 .. 65535");
+    if (!(t0 >= 0.0 && t1 <= 1.0 && t0 <= t1)) return fail(ARMOUR_E_ARG, "the window must satisfy 0 <= t0 <= t1 <= 1");
+    if (!p->reached) return fail(ARMOUR_E_STATE, "no batch: call a reach or plan entry first");
+    const int W = p->W;
+    for (int w = 0; w < W; w++) {
+        const double* t = traj + (size_t)w * TRAJ_DOUBLES;
+        for (int i = 0; i < TRAJ_DOUBLES; i++)
+            if (!std::isfinite(t[i])) return fail(ARMOUR_E_ARG, "traj holds a value that is not finite");
+        for (int i = 0; i < NF; i++)
+            if (!(std::fabs(t[3 * NF + i]) <= 1.0)) return fail(ARMOUR_E_ARG, "every k must lie inside [-1, 1]");
+    }
+    if (int rc = motion_reserve(p, samples)) return rc;
+    HIPCK(hipMemcpyAsync(p->mo_traj, traj, sizeof(double) * W * TRAJ_DOUBLES, hipMemcpyHostToDevice, p->stream));
+    launch_motion(p, p->mo_traj, nullptr, t0, t1, samples);
+    HIPCK(hipGetLastError());
+    if (clearance) HIPCK(hipMemcpyAsync(clearance, p->mo_clear, sizeof(double) * W, hipMemcpyDeviceToHost, p->stream));
+    if (where) HIPCK(hipMemcpyAsync(where, p->mo_where, sizeof(int) * 3 * W, hipMemcpyDeviceToHost, p->stream));
+    HIPCK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+static int episode_read(armour_planner* p) {
+    p->ep_host.resize(p->W);
+    HIPCK(hipMemcpyAsync(p->ep_host.data(), p->ep.st, sizeof(armour_episode_state) * p->W, hipMemcpyDeviceToHost, p->stream));
+    HIPCK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int armour_episode_begin(armour_planner* p, int W, const armour_world* worlds, const double* goals,
+                         const armour_episode_config* cfg) {
+    DeviceScope device_scope(p);
+    if (!p || !worlds || !goals || !cfg) return fail(ARMOUR_E_ARG, "null argument");
+    if (p->armtd) return fail(ARMOUR_E_ARG, "episodes are not available on an ARMTD planner");
+    if (p->eval_f32) return fail(ARMOUR_E_ARG, "episodes are not available with the fp32 study (ARMOUR_EVAL_F32)");
+    if (!(cfg->lookahead > 0.0) || !std::isfinite(cfg->lookahead) || !(cfg->goal_radius >= 0.0) ||
+        !std::isfinite(cfg->goal_radius) || cfg->check_samples < 2 || cfg->check_samples > 65535)
+        return fail(ARMOUR_E_ARG, "episode config: lookahead > 0, goal_radius >= 0, 2 <= check_samples <= 65535");
+    if (W <= 0 || W > p->Wmax) return fail(ARMOUR_E_ARG, "num_worlds out of range");
+    p->reached = p->planned = p->evaluated = p->episode = false;
+    int rc = 0;
+    if ((rc = check_values("goals", goals, W * NF, ARMOUR_MAX_ABS_ANGLE))) return rc;
+    // the worlds' q_des is ignored: the waypoints are written on the device
+    std::vector<armour_world> ws(worlds, worlds + W);
+    for (armour_world& w : ws) std::memcpy(w.q_des, w.q0, sizeof(w.q_des));
+    if ((rc = upload_worlds_mixed(p, W, ws.data()))) return rc;
+    if ((rc = motion_reserve(p, cfg->check_samples))) return rc;
+    EpisodeDev& e = p->ep;
+    if (!e.st) {
+        double* goal = nullptr;
+        int* accept = nullptr;
+        const size_t Wm = (size_t)p->Wmax;
+        if ((rc = p->alloc(&e.st, Wm)) || (rc = p->alloc(&goal, Wm * NF)) || (rc = p->alloc(&e.pend, Wm * TRAJ_DOUBLES)) ||
+            (rc = p->alloc(&e.has_pend, Wm)) || (rc = p->alloc(&e.kind, Wm)) || (rc = p->alloc(&e.exec, Wm * TRAJ_DOUBLES)) ||
+            (rc = p->alloc(&e.win, 2 * Wm)) || (rc = p->alloc(&accept, Wm)))
+            return rc;
+        e.goal = goal;
+        p->ep_accept = accept;
+        e.accept = accept;
+        for (hipEvent_t& ev : p->ep_ev) HIPCK(hipEventCreate(&ev));
+    }
+    e.rp = p->d_rp;
+    e.W = W;
+    e.S = cfg->check_samples;
+    e.lookahead = cfg->lookahead;
+    e.goal_radius = cfg->goal_radius;
+    e.clearance = p->mo_clear;
+    e.where = p->mo_where;
+    HIPCK(hipMemcpyAsync(const_cast<double*>(e.goal), goals, sizeof(double) * W * NF, hipMemcpyHostToDevice, p->stream));
+    hipLaunchKernelGGL(episode_begin_kernel, dim3((W + 63) / 64), dim3(64), 0, p->stream, e, p->q0, p->qd0, p->qdd0);
+    HIPCK(hipGetLastError());
+    if ((rc = episode_read(p))) return rc;  // (also: `goals` is the caller's, its copy has finished)
+    p->episode = true;
+    return 0;
+}
+
+int armour_episode_step(armour_planner* p, const int* reject, armour_result* results, armour_timing* timing,
+                        double* episode_ms) {
+    DeviceScope device_scope(p);
+    if (!p) return fail(ARMOUR_E_ARG, "null planner");
+    if (!p->episode) return fail(ARMOUR_E_STATE, "no episode: call armour_episode_begin first (any other reach or plan entry ends one)");
+    const int W = p->W;
+    const EpisodeDev& e = p->ep;
+    int rc = 0;
+    auto t0 = std::chrono::steady_clock::now();
+    // (a) the pending state becomes the batch input; reach and solve on the resident arrays
+    hipLaunchKernelGGL(episode_swap_kernel, dim3((W * NF + 255) / 256), dim3(256), 0, p->stream, e, p->q0, p->qd0, p->qdd0,
+                       p->qdes);
+    HIPCK(hipGetLastError());
+    if (p->rstream != p->stream) HIPCK(hipStreamSynchronize(p->stream));  // the reach stream reads q0 / qd0 / qdd0
+    p->reached = p->planned = p->evaluated = false;
+    std::vector<armour_result> own;
+    if (!results) {
+        own.resize(W);
+        results = own.data();
+    }
+    if ((rc = plan_uploaded(p, results, timing, t0))) {
+        p->episode = false;
+        return rc;
+    }
+    // (b) what each running world executes; (c) check, advance
+    std::vector<int> accept(W);
+    for (int w = 0; w < W; w++) accept[w] = results[w].feasible && !(reject && reject[w]) ? 1 : 0;
+    HIPCK(hipMemcpyAsync(p->ep_accept, accept.data(), sizeof(int) * W, hipMemcpyHostToDevice, p->stream));
+    const dim3 wg((W + 63) / 64), wb(64);
+    HIPCK(hipEventRecord(p->ep_ev[0], p->stream));
+    hipLaunchKernelGGL(episode_choose_kernel, wg, wb, 0, p->stream, e, (const double*)p->d.ws,
+                       (long)(sizeof(WorldState) / sizeof(double)), p->q0, p->qd0, p->qdd0);
+    HIPCK(hipEventRecord(p->ep_ev[1], p->stream));
+    launch_motion(p, e.exec, e.win, 0.0, 0.0, e.S);
+    HIPCK(hipEventRecord(p->ep_ev[2], p->stream));
+    hipLaunchKernelGGL(episode_advance_kernel, wg, wb, 0, p->stream, e);
+    HIPCK(hipEventRecord(p->ep_ev[3], p->stream));
+    HIPCK(hipGetLastError());
+    if ((rc = episode_read(p))) return rc;  // (ends in a synchronisation: `accept` outlives its copy)
+    if (episode_ms) {
+        float a = 0, b = 0, c = 0;
+        (void)hipEventElapsedTime(&a, p->ep_ev[0], p->ep_ev[1]);
+        (void)hipEventElapsedTime(&b, p->ep_ev[1], p->ep_ev[2]);
+        (void)hipEventElapsedTime(&c, p->ep_ev[2], p->ep_ev[3]);
+        episode_ms[0] = b;
+        episode_ms[1] = (double)a + c;
+    }
+    int running = 0;
+    for (const armour_episode_state& s : p->ep_host) running += s.status == 0;
+    return running;
+}
+
+int armour_episode_get(armour_planner* p, armour_episode_state* states) {
+    if (!p || !states) return fail(ARMOUR_E_ARG, "null argument");
+    if (!p->episode) return fail(ARMOUR_E_STATE, "no episode: call armour_episode_begin first (any other reach or plan entry ends one)");
+    std::memcpy(states, p->ep_host.data(), sizeof(armour_episode_state) * p->ep_host.size());
     return 0;
 }
 

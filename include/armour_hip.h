@@ -245,6 +245,104 @@ int armour_eval_constraints(armour_planner* p, int w, const double* x, double* g
 int armour_eval_candidates(armour_planner* p, int num_candidates, const double* x, double* cost, double* violation,
                            int* feasible, int* best);
 
+/* Execution check: the smallest sampled separation between the arm on a trajectory and the obstacles
+ * of each world of the last batch (uniform or mixed; after any reach or plan entry; the obstacles
+ * resident on the device and the planner's robot tables). No reach set is read: this is the check
+ * that an executed plan misses the obstacles, independent of the sets that produced it.
+ *   traj  [W][4][7]: q0, qd0, qdd0 and k (normalised, |k| <= 1) of each world's trajectory, the
+ *         degree-5 Bezier curve of KPR/Trajectory.cu:542-599 with end point q0 + k * k_range
+ *         (k_range = pi/48) and duration 1.
+ *   It is evaluated at `samples` evenly spaced times in [t0, t1], a window inside [0, 1], ends included
+ *   (sample s at t0 + s * ((t1 - t0) / (samples - 1)), the last at t1; samples = 1: t0 alone).
+ *   At each sampled q the link boxes come from point forward kinematics (KPR/Dynamics.cu:69-81 at a
+ *   point): p += R trans_i, R = R (RPY_i Rot_axis_i(q_i)); link i's box has centre p + R link_center_i
+ *   and the three generators R diag(link_generators_i).
+ *   Each link box is tested against each obstacle zonotope on the 15 axes that are the normalised
+ *   cross products of all pairs among the 6 generators (obstacle 3, then link 3); a pair whose cross
+ *   product has norm exactly 0 is skipped (KPR/CollisionChecking.cu:261-282). The separation is
+ *       max_n (|n . (c - c_obs)| - sum_j |n . G_j|)
+ *   (-1e8 when every pair was skipped). A positive value means the two sets are disjoint at that
+ *   sample and is a lower bound of their distance; a value <= 0 means they intersect (for two
+ *   3-generator zonotopes the 15 axes hold every facet normal of their sum).
+ *   clearance [W]     the minimum over samples, links and the world's own obstacles (optional)
+ *   where     [W][3]  its first minimiser in the order (sample, link, obstacle) (optional)
+ *   A world without obstacles gets +infinity and -1, -1, -1.
+ * ARMOUR_E_ARG for a null p or traj, a non-finite value, |k| > 1, samples < 1 (or > 65535), t0 > t1
+ * or a window outside [0, 1], an ARMTD planner, or the fp32 study (ARMOUR_EVAL_F32); ARMOUR_E_STATE
+ * before any batch. It touches no plan state (as armour_eval_candidates): the getters return what
+ * they returned before and the next plan is the one it would have been. */
+int armour_check_motion(armour_planner* p, const double* traj, double t0, double t1, int samples, double* clearance,
+                        int* where);
+
+/* Receding-horizon episodes: the loop of SCR/kinova_run_100_worlds.m with its state on the device.
+ * Each step takes the straight-line waypoint (robot_arm_straight_line_HLP.m:45-57), plans, follows
+ * the new trajectory for ARMOUR_T_PLAN of its duration 1 (KSI/uarmtd_planner.m:56-62) or, when the
+ * plan failed, brakes along the second half of the previous trajectory (uarmtd_planner.m:922-932),
+ * and stops on collision or inside the goal radius (kinova_world_static.m:417-425). The state
+ * advances on the desired trajectory (no tracking error or dynamics simulation).
+ *
+ * armour_episode_begin checks every world with armour_check_world (its q_des is ignored; goals must be
+ * finite and within ARMOUR_MAX_ABS_ANGLE; lookahead > 0, goal_radius >= 0, 2 <= check_samples <=
+ * 65535), uploads the worlds as armour_plan_batch_mixed does (any mix of obstacle counts, zero
+ * included) and writes each world's first waypoint on the device. A world already inside the goal
+ * radius starts with status 1; a world with a non-zero qd0 or qdd0 starts in mode 1 with nothing
+ * pending. Not available on an ARMTD planner or with the fp32 study: ARMOUR_E_ARG. No batch has been
+ * planned yet: the getters and armour_check_motion return ARMOUR_E_STATE until the first step.
+ *
+ * armour_episode_step, in order:
+ *  (a) The pending state becomes the batch input and the batch is planned with the code of
+ *      armour_plan_batch_mixed on the resident arrays (no world upload): results [W] and timing are
+ *      exactly what armour_plan_batch_mixed returns for the states armour_episode_get showed before the
+ *      step. Every world is planned, frozen ones included.
+ *  (b) Each running world (status 0) executes
+ *        its new plan on [0, ARMOUR_T_PLAN]            if the plan is feasible and reject[w] == 0
+ *                                                      (failed_streak = 0);
+ *        else (failed_plans and failed_streak count up)
+ *        the pending trajectory on [ARMOUR_T_PLAN, 1]  if mode == 1 and a plan is pending: the world
+ *                                                      then sits at rest at q0' + k' k_range with
+ *                                                      qd = qdd = 0 exactly, mode 0;
+ *        nothing (it stays at rest)                    if mode == 0;
+ *        and gets status 3                             if mode == 1 with nothing pending (a first plan
+ *                                                      from a moving start failed).
+ *      reject (optional, [W]) is the caller's veto: a missed deadline, or a check of its own.
+ *  (c) armour_check_motion's kernel runs over the executed segment with check_samples samples. The
+ *      running clearance keeps the smallest value and its first (step, link, obstacle). The next
+ *      state is the segment's end and the next q_des = q + lookahead * d / ||d||, d = goal - q
+ *      angle-wrapped to [-pi, pi) on continuous joints (state_lb <= -1000; d = 0: q_des = q). A
+ *      clearance <= 0 gives status 2; otherwise a sample within goal_radius of the goal gives status 1
+ *      (every sampled state of the segment is tested, as the reference tests every state). A next
+ *      state that is not finite or lies beyond ARMOUR_MAX_ABS_ANGLE gives status 4 and keeps the old
+ *      state. steps counts the steps a world executed (staying at rest included).
+ * A world whose status is not 0 is frozen: still planned, never advanced, checked or counted.
+ * Returns the number of worlds still running (>= 0), or a negative code. episode_ms (optional):
+ * [0] check kernels, [1] choose + advance kernels, device milliseconds.
+ *
+ * The advanced state lives in arrays of its own until the next step's (a): between steps every
+ * getter, armour_eval_constraints, armour_eval_candidates and armour_check_motion see the batch that
+ * was planned. Any other reach or plan entry ends the episode: step and get then return
+ * ARMOUR_E_STATE (as they do before a begin). */
+#define ARMOUR_T_PLAN 0.5
+typedef struct armour_episode_config {
+    double lookahead;     /* 0.1 (kinova_run_100_worlds.m:57) */
+    double goal_radius;   /* pi/30 */
+    int check_samples;    /* >= 2 */
+} armour_episode_config;
+typedef struct armour_episode_state {
+    double q[ARMOUR_NUM_FACTORS], qd[ARMOUR_NUM_FACTORS], qdd[ARMOUR_NUM_FACTORS];
+    double q_des[ARMOUR_NUM_FACTORS]; /* what the next plan starts from, and its waypoint */
+    int status;        /* 0 running, 1 goal reached, 2 collided, 3 no fail-safe, 4 left the input domain */
+    int mode;          /* 0 at rest, 1 moving: the braking half of the last accepted plan is pending */
+    int steps, failed_plans, failed_streak;
+    double clearance;  /* smallest over every executed sample so far (+infinity: none yet) */
+    int clearance_at[3];              /* its step, link, obstacle (-1: none yet) */
+    double goal_distance;             /* ||angdiff(q, goal)||_2 over all 7 joints */
+} armour_episode_state;
+int armour_episode_begin(armour_planner* p, int num_worlds, const armour_world* worlds, const double* goals,
+                         const armour_episode_config* cfg);
+int armour_episode_step(armour_planner* p, const int* reject, armour_result* results, armour_timing* timing,
+                        double* episode_ms);
+int armour_episode_get(armour_planner* p, armour_episode_state* states);
+
 /* Outputs of world w of the last batch (the armour_*.out payloads, armour_main.cu:340-398) */
 int armour_get_constraints(armour_planner* p, int w, double* g);              /* m values at k_opt (m_w of world w) */
 int armour_get_link_centers(armour_planner* p, int w, double* centers);       /* [T][NJ][3] sliced at the
