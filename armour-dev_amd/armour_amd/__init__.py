@@ -82,6 +82,16 @@ T_PLAN = 0.5  # ARMOUR_T_PLAN
 EPISODE_STATUS = ("running", "goal reached", "collided", "no fail-safe", "left the input domain")
 
 
+class TrackOutput(ctypes.Structure):
+    """armour_track_output (include/armour_hip.h): the caller's output arrays (null: skipped) and the
+    device time of the rollouts"""
+    _fields_ = [("max_pos_err", _dp), ("max_vel_err", _dp), ("max_torque", _dp), ("max_V", _dp), ("max_robust", _dp),
+                ("end_state", _dp), ("status", ctypes.POINTER(ctypes.c_int)), ("track_ms", ctypes.c_double)]
+
+
+TRACK_MAX_STEPS = 100000  # ARMOUR_TRACK_MAX_STEPS
+
+
 class PlanOutput(ctypes.Structure):
     """armour_plan_output (include/armour_hip.h): the single-world entry's result and the caller's
     output arrays (null: skipped)"""
@@ -132,7 +142,9 @@ def lib():
                                                      ctypes.POINTER(EpisodeConfig)]),
                            ("armour_episode_step", [ctypes.c_void_p, ip, ctypes.POINTER(Result), ctypes.POINTER(Timing),
                                                     _dp]),
-                           ("armour_episode_get", [ctypes.c_void_p, ctypes.POINTER(EpisodeState)])):
+                           ("armour_episode_get", [ctypes.c_void_p, ctypes.POINTER(EpisodeState)]),
+                           ("armour_track", [ctypes.c_void_p, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp, ctypes.c_double,
+                                             ctypes.c_double, ctypes.c_int, ctypes.POINTER(TrackOutput)])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = args
         for name, args in (("armour_check_world", [ctypes.POINTER(World), ctypes.c_int]),
@@ -171,7 +183,8 @@ ABI_SYMBOLS = ["armour_copy_bandwidth", "armour_create", "armour_create_robot", 
                "armour_get_plane_cache_stats", "armour_plan", "armour_get_reach_span",
                "armour_plan_batch_mixed", "armour_reach_batch_mixed", "armour_world_num_obstacles",
                "armour_eval_candidates", "armour_sq_selfcheck", "armour_check_world", "armour_check_armtd_world",
-               "armour_check_motion", "armour_episode_begin", "armour_episode_step", "armour_episode_get"]
+               "armour_check_motion", "armour_episode_begin", "armour_episode_step", "armour_episode_get",
+               "armour_track"]
 
 
 def default_batch(T: int, device: int = 0, waves: int = 2) -> int:
@@ -258,6 +271,24 @@ def candidates_array(x, W):
     if np.abs(x).max() > 1.0:
         raise ValueError("eval_candidates: every candidate must lie in [-1, 1]")
     return np.ascontiguousarray(x)
+
+
+def uncertainty_samples(tables, S, seed=0):
+    """[S, 2, num_joints] mass and inertia scales for armour_track within the tables' stated uncertainty
+    d = (mass_uncertainty, inertia_uncertainty): sample 0 nominal, sample 1 every link at 1 + d, sample 2
+    every link at 1 - d, the rest uniform in [1 - d, 1 + d] per link (numpy default_rng(seed))"""
+    S = int(S)
+    if S < 1:
+        raise ValueError("uncertainty_samples: S must be at least 1")
+    nj = int(tables["num_joints"])
+    d = np.array([float(tables["mass_uncertainty"]), float(tables["inertia_uncertainty"])])[None, :, None]
+    u = np.random.default_rng(seed).uniform(-1.0, 1.0, (S, 2, nj))
+    u[0] = 0.0
+    if S > 1:
+        u[1] = 1.0
+    if S > 2:
+        u[2] = -1.0
+    return 1.0 + d * u
 
 
 class Planner:
@@ -434,6 +465,53 @@ class Planner:
         _check(lib().armour_check_motion(self.h, _ptr(traj), float(t0), float(t1), int(samples), _ptr(clear),
                                          where.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return clear, where
+
+    def track(self, traj, scale=None, err0=None, t0=0.0, t1=0.5, steps=250):
+        """armour_track: the true arm under the robust controller along traj [N, 4, 7] (q0, qd0, qdd0, k
+        normalised), for S parameter samples per trajectory: scale [N, S, 2, num_joints] (mass and inertia
+        scales; [S, 2, num_joints] is used for every trajectory; None: nominal) and err0 [N, S, 2, 7] (the
+        start's offset from the desired state; None: zero), classical RK4 with `steps` steps over [t0, t1].
+        Needs no batch. Returns a dict: max_pos_err, max_vel_err, max_torque [N, S, 7], max_V, max_robust
+        [N, S], end_state [N, S, 2, 7], status [N, S] (1: the rollout stopped being finite), track_ms, and
+        the ultimate bounds qe, qde of the planner's tables the errors are read against."""
+        traj = np.ascontiguousarray(np.asarray(traj, dtype=np.float64))
+        if traj.ndim != 3 or traj.shape[1:] != (4, NF) or traj.shape[0] < 1:
+            raise ValueError(f"track: traj must have shape [N, 4, {NF}], got {traj.shape}")
+        N = traj.shape[0]
+        S = None
+        if scale is not None:
+            scale = np.asarray(scale, dtype=np.float64)
+            if scale.ndim == 3:
+                scale = np.broadcast_to(scale, (N,) + scale.shape)
+            if scale.ndim != 4 or scale.shape[0] != N or scale.shape[1] < 1 or scale.shape[2:] != (2, self.NJ):
+                raise ValueError(f"track: scale must have shape [N, S, 2, {self.NJ}] or [S, 2, {self.NJ}] (N = {N}), "
+                                 f"got {scale.shape}")
+            scale = np.ascontiguousarray(scale)
+            S = scale.shape[1]
+        if err0 is not None:
+            err0 = np.ascontiguousarray(np.asarray(err0, dtype=np.float64))
+            if err0.ndim != 4 or err0.shape[0] != N or err0.shape[1] < 1 or err0.shape[2:] != (2, NF) or \
+                    (S is not None and err0.shape[1] != S):
+                raise ValueError(f"track: err0 must have shape [N, S, 2, {NF}] (N = {N}, S = {S}), got {err0.shape}")
+            S = err0.shape[1]
+        S = 1 if S is None else S
+        out = dict(max_pos_err=np.zeros((N, S, NF)), max_vel_err=np.zeros((N, S, NF)), max_torque=np.zeros((N, S, NF)),
+                   max_V=np.zeros((N, S)), max_robust=np.zeros((N, S)), end_state=np.zeros((N, S, 2, NF)))
+        status = np.zeros((N, S), dtype=np.int32)
+        o = TrackOutput(*[_ptr(out[k]) for k in ("max_pos_err", "max_vel_err", "max_torque", "max_V", "max_robust",
+                                                  "end_state")], status.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), 0.0)
+        _check(lib().armour_track(self.h, N, _ptr(traj), S, _ptr(scale), _ptr(err0), float(t0), float(t1), int(steps),
+                                  ctypes.byref(o)))
+        out["status"] = status
+        out["track_ms"] = float(o.track_ms)
+        r = getattr(self, "_robot", None)   # the tables' ultimate bound, as the library derives it
+        if r is None:
+            from .robot_tables import ArmourRobot
+            r = ArmourRobot()
+            _check(lib().armour_robot_builtin(0, ctypes.byref(r)))
+        eps = float(np.sqrt(2 * r.V_m / r.M_min))
+        out["qe"], out["qde"] = eps / r.K, 2 * eps
+        return out
 
     def episode_begin(self, worlds, goals, lookahead=0.1, goal_radius=np.pi / 30, check_samples=11):
         """armour_episode_begin: start receding-horizon episodes of `worlds` (their q_des is ignored) toward

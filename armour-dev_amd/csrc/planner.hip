@@ -22,6 +22,7 @@
 #include "reach_kernel.hip"
 #include "lane_kernel.hip"
 #include "motion_kernels.hip"
+#include "track_kernels.hip"
 #include "robots.h"
 
 using namespace armour;
@@ -162,6 +163,12 @@ struct armour_planner {
     int* ep_accept = nullptr;
     hipEvent_t ep_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     std::vector<armour_episode_state> ep_host;  // the states after the last begin / step
+    // armour_track (track_kernels.hip): inputs and per-rollout outputs for track_cap rollouts,
+    // allocated on first use and regrown on demand
+    double *tr_traj = nullptr, *tr_scale = nullptr, *tr_err0 = nullptr, *tr_out = nullptr;
+    int* tr_status = nullptr;
+    long track_cap = 0;
+    hipEvent_t tr_ev[2] = {nullptr, nullptr};
     std::vector<void*> allocs;
 
     template <class T>
@@ -1378,6 +1385,32 @@ static int run_solver(armour_planner* p) {
     return 0;
 }
 
+static void track_free(armour_planner* p) {
+    for (void* a : {(void*)p->tr_traj, (void*)p->tr_scale, (void*)p->tr_err0, (void*)p->tr_out, (void*)p->tr_status})
+        if (a) (void)hipFree(a);
+    p->tr_traj = p->tr_scale = p->tr_err0 = p->tr_out = nullptr;
+    p->tr_status = nullptr;
+    p->track_cap = 0;
+}
+
+// buffers of armour_track for NR rollouts
+static int track_reserve(armour_planner* p, long NR) {
+    if (!p->tr_ev[0])
+        for (int i = 0; i < 2; i++) HIPCK(hipEventCreate(&p->tr_ev[i]));
+    if (NR <= p->track_cap) return 0;
+    HIPCK(hipStreamSynchronize(p->stream));
+    track_free(p);
+    const size_t n = (size_t)NR;
+    if (dalloc(&p->tr_traj, n * TRAJ_DOUBLES) != hipSuccess || dalloc(&p->tr_scale, n * 2 * MAX_J) != hipSuccess ||
+        dalloc(&p->tr_err0, n * 2 * NF) != hipSuccess || dalloc(&p->tr_out, n * TRACK_OUT_DOUBLES) != hipSuccess ||
+        dalloc(&p->tr_status, n) != hipSuccess) {
+        track_free(p);
+        return fail(ARMOUR_E_HIP, "hipMalloc failed for the tracking rollouts' buffers (num_traj x num_samples)");
+    }
+    p->track_cap = NR;
+    return 0;
+}
+
 // Every entry point runs on its planner's device, whatever the calling thread's current device is
 // (handles may be driven from other host threads); the caller's device is restored.
 struct DeviceScope {
@@ -1557,6 +1590,9 @@ void armour_destroy(armour_planner* p) {
     if (p->mo_pval) (void)hipFree(p->mo_pval);
     if (p->mo_pidx) (void)hipFree(p->mo_pidx);
     for (hipEvent_t e : p->ep_ev)
+        if (e) (void)hipEventDestroy(e);
+    track_free(p);
+    for (hipEvent_t e : p->tr_ev)
         if (e) (void)hipEventDestroy(e);
     if (p->h_flags) (void)hipHostFree(p->h_flags);
     if (p->h_sum) (void)hipHostFree(p->h_sum);
@@ -1905,6 +1941,79 @@ int armour_check_motion(armour_planner* p, const double* traj, double t0, double
     if (clearance) HIPCK(hipMemcpyAsync(clearance, p->mo_clear, sizeof(double) * W, hipMemcpyDeviceToHost, p->stream));
     if (where) HIPCK(hipMemcpyAsync(where, p->mo_where, sizeof(int) * 3 * W, hipMemcpyDeviceToHost, p->stream));
     HIPCK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int armour_track(armour_planner* p, int N, const double* traj, int S, const double* scale, const double* err0, double t0,
+                 double t1, int steps, armour_track_output* out) {
+    DeviceScope device_scope(p);
+    if (!p || !traj || !out) return fail(ARMOUR_E_ARG, "null planner / traj / out");
+    if (p->armtd) return fail(ARMOUR_E_ARG, "tracking rollouts are not available on an ARMTD planner");
+    if (p->eval_f32) return fail(ARMOUR_E_ARG, "tracking rollouts are not available with the fp32 study (ARMOUR_EVAL_F32)");
+    if (N < 1 || S < 1) return fail(ARMOUR_E_ARG, "num_traj and num_samples must be at least 1");
+    if ((long)N * S > ARMOUR_TRACK_MAX_ROLLOUTS) return fail(ARMOUR_E_ARG, "num_traj x num_samples exceeds ARMOUR_TRACK_MAX_ROLLOUTS");
+    if (steps < 1 || steps > ARMOUR_TRACK_MAX_STEPS) return fail(ARMOUR_E_ARG, "steps must lie in 1 .. ARMOUR_TRACK_MAX_STEPS");
+    if (!(t0 >= 0.0 && t0 < t1 && t1 <= 1.0)) return fail(ARMOUR_E_ARG, "the window must satisfy 0 <= t0 < t1 <= 1");
+    const long NR = (long)N * S;
+    const int NJ = p->NJ;
+    for (int n = 0; n < N; n++) {
+        const double* t = traj + (size_t)n * TRAJ_DOUBLES;
+        for (int i = 0; i < TRAJ_DOUBLES; i++)
+            if (!std::isfinite(t[i])) return fail(ARMOUR_E_ARG, "traj holds a value that is not finite");
+        for (int i = 0; i < NF; i++) {
+            if (!(std::fabs(t[i]) <= ARMOUR_MAX_ABS_ANGLE)) return fail(ARMOUR_E_ARG, "traj: every |q0| must be at most ARMOUR_MAX_ABS_ANGLE");
+            if (!(std::fabs(t[3 * NF + i]) <= 1.0)) return fail(ARMOUR_E_ARG, "traj: every k must lie inside [-1, 1]");
+        }
+    }
+    if (scale)
+        for (size_t i = 0; i < (size_t)NR * 2 * NJ; i++) {
+            if (!std::isfinite(scale[i])) return fail(ARMOUR_E_ARG, "scale holds a value that is not finite");
+            if (!(scale[i] > 0)) return fail(ARMOUR_E_ARG, "every scale must be positive");
+        }
+    if (err0)
+        for (size_t i = 0; i < (size_t)NR * 2 * NF; i++)
+            if (!std::isfinite(err0[i])) return fail(ARMOUR_E_ARG, "err0 holds a value that is not finite");
+    if (int rc = track_reserve(p, NR)) return rc;
+    HIPCK(hipMemcpyAsync(p->tr_traj, traj, sizeof(double) * N * TRAJ_DOUBLES, hipMemcpyHostToDevice, p->stream));
+    if (scale) HIPCK(hipMemcpyAsync(p->tr_scale, scale, sizeof(double) * NR * 2 * NJ, hipMemcpyHostToDevice, p->stream));
+    if (err0) HIPCK(hipMemcpyAsync(p->tr_err0, err0, sizeof(double) * NR * 2 * NF, hipMemcpyHostToDevice, p->stream));
+    TrackArgs a{};
+    a.rp = p->d_rp;
+    a.N = N;
+    a.S = S;
+    a.traj = p->tr_traj;
+    a.scale = scale ? p->tr_scale : nullptr;
+    a.err0 = err0 ? p->tr_err0 : nullptr;
+    a.t0 = t0;
+    a.t1 = t1;
+    a.steps = steps;
+    a.out = p->tr_out;
+    a.status = p->tr_status;
+    // the row form is the default (DESIGN.md section 4 has the measurement); ARMOUR_TRACK_KERNEL=serial
+    // selects the serial form, which computes the same bits
+    const char* kv = std::getenv("ARMOUR_TRACK_KERNEL");
+    const bool serial = kv && !std::strcmp(kv, "serial");
+    HIPCK(hipEventRecord(p->tr_ev[0], p->stream));
+    if (serial)
+        hipLaunchKernelGGL(track_serial_kernel, dim3((unsigned)((NR + TRACK_THREADS - 1) / TRACK_THREADS)), dim3(TRACK_THREADS), 0,
+                           p->stream, a);
+    else
+        hipLaunchKernelGGL(track_row_kernel, dim3((unsigned)((NR + TRACK_ROWS - 1) / TRACK_ROWS)), dim3(TRACK_THREADS), 0,
+                           p->stream, a);
+    HIPCK(hipGetLastError());
+    HIPCK(hipEventRecord(p->tr_ev[1], p->stream));
+    const size_t n = (size_t)NR;
+    struct { double* dst; size_t off, len; } parts[] = {
+        {out->max_pos_err, 0, n * NF},       {out->max_vel_err, n * NF, n * NF}, {out->max_torque, 2 * n * NF, n * NF},
+        {out->max_V, 21 * n, n},             {out->max_robust, 22 * n, n},       {out->end_state, 23 * n, n * 2 * NF}};
+    for (const auto& part : parts)
+        if (part.dst)
+            HIPCK(hipMemcpyAsync(part.dst, p->tr_out + part.off, sizeof(double) * part.len, hipMemcpyDeviceToHost, p->stream));
+    if (out->status) HIPCK(hipMemcpyAsync(out->status, p->tr_status, sizeof(int) * n, hipMemcpyDeviceToHost, p->stream));
+    HIPCK(hipStreamSynchronize(p->stream));
+    float ms = 0.f;
+    HIPCK(hipEventElapsedTime(&ms, p->tr_ev[0], p->tr_ev[1]));
+    out->track_ms = ms;
     return 0;
 }
 

@@ -279,7 +279,8 @@ int armour_check_motion(armour_planner* p, const double* traj, double t0, double
  * the new trajectory for ARMOUR_T_PLAN of its duration 1 (KSI/uarmtd_planner.m:56-62) or, when the
  * plan failed, brakes along the second half of the previous trajectory (uarmtd_planner.m:922-932),
  * and stops on collision or inside the goal radius (kinova_world_static.m:417-425). The state
- * advances on the desired trajectory (no tracking error or dynamics simulation).
+ * advances on the desired trajectory (no tracking error or dynamics simulation; armour_track below is
+ * that simulation, for given trajectories).
  *
  * armour_episode_begin checks every world with armour_check_world (its q_des is ignored; goals must be
  * finite and within ARMOUR_MAX_ABS_ANGLE; lookahead > 0, goal_radius >= 0, 2 <= check_samples <=
@@ -342,6 +343,75 @@ int armour_episode_begin(armour_planner* p, int num_worlds, const armour_world* 
 int armour_episode_step(armour_planner* p, const int* reject, armour_result* results, armour_timing* timing,
                         double* episode_ms);
 int armour_episode_get(armour_planner* p, armour_episode_state* states);
+
+/* Tracking rollouts: the other half of ARMOUR's guarantee. The planner bounds every trajectory whose
+ * tracking error stays inside the ultimate bound (qe = eps / K, qde = 2 eps, eps = sqrt(2 V_m / M_min));
+ * armour_track integrates the true arm under the reference's robust passivity controller along given
+ * trajectories, for num_samples parameter samples per trajectory, on the device, and reports how far the
+ * arm strayed and what torque it took. It reads only the planner's robot tables: it needs no batch,
+ * touches no batch, plan or episode state (the getters return what they returned before and the next
+ * plan is the one it would have been), and runs on the planner's stream.
+ *
+ * Inputs. Trajectory n is traj[n] = q0, qd0, qdd0, k (k normalised, |k| <= 1), the curve
+ *   armour_check_motion uses (duration 1). Sample s of trajectory n has the true parameters
+ *   mass_i * scale[n][s][0][i] and inertia_i * scale[n][s][1][i] per link i < num_joints
+ *   (scale [N][S][2][num_joints]; null: all 1). The start is q(t0) = q_des(t0) + err0[n][s][0],
+ *   qd(t0) = qd_des(t0) + err0[n][s][1] (err0 [N][S][2][7]; null: zero).
+ * Point RNEA R(q, qd, qa, qdda; params, gravity on/off, damping on/off): the recursion of
+ *   KPR/Dynamics.cu:83-181 at a point. Reversed axes and fixed joints (axis 0) as in the robot tables
+ *   above. The generalised torque is the moment along the signed axis, plus armature * qdda, plus
+ *   damping * qd. friction[] is not modelled, as in the planner's RNEA.
+ * Its radius for mass in m (1 +- dm) and every inertia entry in I_jk (1 +- dI), dm = mass_uncertainty,
+ *   dI = inertia_uncertainty: the midpoint-radius form of the reference's interval RNEA (rnea.cpp
+ *   passRNEA_Int, robot_models.cpp:222-232) with point kinematics. With |a| (x) |b| the "absolute
+ *   cross" (|a_y||b_z| + |a_z||b_y|, ...):
+ *     rad F_i = dm |m_i| |a_ci|,   rad N_i = dI (|I_i||wd| + |wa| (x) (|I_i||w|)),
+ *     backward: rad f_i = |R_{i+1}| rad f_{i+1} + rad F_i,
+ *               rad n_i = rad N_i + |R_{i+1}| rad n_{i+1} + |c_i| (x) rad F_i + |p_{i+1}| (x) (|R_{i+1}| rad f_{i+1}),
+ *     rho_i = rad n_i . |axis_i|.   Armature and damping carry no uncertainty.
+ * Controller at (t, q, qd) (robust_controller.cpp:63-168, ARMOUR method, r_norm_threshold = 0):
+ *   e = q_des - q, wrapped to [-pi, pi) on continuous joints (state_lb <= -1000) by one remainder;
+ *   de = qd_des - qd; qa_d = qd_des + K e; qa_dd = qdd_des + K de; r = de + K e;
+ *   tau = R(q, qd, qa_d, qa_dd; nominal) with radius rho;
+ *   Mr = R(q, 0, 0, r; nominal, no gravity, no damping) with radius rMr;
+ *   V_sup = 0.5 (r . Mr + |r| . rMr); h = V_m - V_sup;
+ *   if ||r|| > 0: lambda = max(0, -alpha h / ||r|| + ||rho||) and u = tau + lambda r / ||r||; otherwise
+ *   u = tau. Norms are sums in index order.
+ * Plant. Column j of M is R(q, 0, 0, e_j; true, no gravity, no damping) (with the armature, as the
+ *   reference's agent adds its transmission inertia); b = R(q, qd, qd, 0; true);
+ *   qdd = M^-1 (u - b) by an unpivoted Cholesky in a fixed order; the true V = 0.5 r' M r.
+ * Integration. Classical RK4 with `steps` equal steps h = (t1 - t0) / steps, step s starting at
+ *   t0 + s h. The trip count is fixed; no loop's length depends on data.
+ * Recording, at the first stage of every step and once more at t1 (steps + 1 samples): per joint
+ *   max |q - q_des|, max |qd - qd_des|, max |u|; per rollout max V (true) and max lambda; and the end
+ *   state q(t1), qd(t1).
+ * Status. 0 for a clean rollout; 1 when a state or a pivot stopped being finite or positive: from then
+ *   on the rollout only carries its last finite values, and nothing is stored out of range.
+ *
+ * The scheme is fixed-step and the robust term has the gain lambda / ||r||: an arm with little or no
+ * armature (the Fetch tables) needs many more steps than the Kinova; max_robust
+ * and status are how a caller sees that a rollout chattered.
+ *
+ * ARMOUR_E_ARG, naming the field and before any device work, for a null p, traj or out; num_traj < 1
+ * or num_samples < 1 (or more than ARMOUR_TRACK_MAX_ROLLOUTS rollouts); a value that is not finite;
+ * |k| > 1; |q0| > ARMOUR_MAX_ABS_ANGLE; a scale <= 0; steps < 1 or > ARMOUR_TRACK_MAX_STEPS;
+ * !(0 <= t0 < t1 <= 1); an ARMTD planner, or the fp32 study (ARMOUR_EVAL_F32). Device buffers are
+ * sized by num_traj * num_samples and grown on demand on the handle. Two kernels compute the same
+ * bits: one rollout per 16 lanes (the default) and one per thread (ARMOUR_TRACK_KERNEL=serial). */
+#define ARMOUR_TRACK_MAX_STEPS 100000
+#define ARMOUR_TRACK_MAX_ROLLOUTS 16777216
+typedef struct armour_track_output {   /* every pointer optional (null: skipped) */
+    double* max_pos_err;  /* [N][S][7] */
+    double* max_vel_err;  /* [N][S][7] */
+    double* max_torque;   /* [N][S][7] */
+    double* max_V;        /* [N][S] */
+    double* max_robust;   /* [N][S] largest lambda */
+    double* end_state;    /* [N][S][2][7] q(t1), qd(t1): err0 of a following window is end_state - desired */
+    int* status;          /* [N][S] */
+    double track_ms;      /* device time of the rollouts */
+} armour_track_output;
+int armour_track(armour_planner* p, int num_traj, const double* traj, int num_samples, const double* scale,
+                 const double* err0, double t0, double t1, int steps, armour_track_output* out);
 
 /* Outputs of world w of the last batch (the armour_*.out payloads, armour_main.cu:340-398) */
 int armour_get_constraints(armour_planner* p, int w, double* g);              /* m values at k_opt (m_w of world w) */
