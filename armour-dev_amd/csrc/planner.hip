@@ -45,21 +45,157 @@ template <class T>
 hipError_t dalloc(T** p, size_t n) {
     return hipMalloc((void**)p, sizeof(T) * (n > 0 ? n : 1));
 }
-// the buffers of armour_eval_candidates (CandDev, nlp_kernels.hip)
-void cand_free(CandDev& c) {
-    for (const void* a : {(const void*)c.x, (const void*)c.ptq, (const void*)c.pcol, (const void*)c.pbad, (const void*)c.cost,
-                          (const void*)c.viol, (const void*)c.feas, (const void*)c.best})
-        if (a) (void)hipFree(const_cast<void*>(a));
-    c = CandDev{};
-}
 }  // namespace
+
+// A set of device buffers allocated on first use and regrown when a call needs more (the candidate,
+// execution-check and tracking buffers). The pointers live where their users read them (planner
+// fields); the set knows which they are, so there is one way to grow and one to free.
+struct GrowSet {
+    struct Buf {
+        void** ptr;
+        size_t bytes;
+    };
+    template <class T>
+    static Buf buf(T*& p, size_t n) { return {(void**)&p, sizeof(T) * n}; }
+
+    long cap = 0;  // what the buffers hold, in the caller's unit (candidates, samples, rollouts)
+    std::vector<void**> held;
+
+    void release() {
+        for (void** h : held) {
+            if (*h) (void)hipFree(*h);
+            *h = nullptr;
+        }
+        held.clear();
+        cap = 0;
+    }
+    // Room for `need`: nothing to do within the capacity; otherwise the old set is freed once the
+    // stream's work on it has finished, and the new set is allocated whole or not at all.
+    int reserve(hipStream_t stream, long need, std::initializer_list<Buf> bufs, const char* failure) {
+        if (need <= cap) return 0;
+        HIPCK(hipStreamSynchronize(stream));
+        release();
+        for (const Buf& b : bufs) {
+            *b.ptr = nullptr;
+            held.push_back(b.ptr);
+            if (hipMalloc(b.ptr, b.bytes) != hipSuccess) {
+                release();
+                return fail(ARMOUR_E_HIP, failure);
+            }
+        }
+        cap = need;
+        return 0;
+    }
+};
 
 // planners alive per device (armour_create / armour_destroy): the bundle kernel's shape depends on
 // whether the GPU is shared (lane_shape_for)
 static std::atomic<int> g_planners[64];
 
+// capacity retry: a quarter of the workgroups, each with four workgroups' buffers
+constexpr int RETRY_SCALE = 4;
+
+// largest batch (jobs = worlds x T) that runs on the per-job engine; measured crossover, DESIGN.md §4
+constexpr long JOB_ENGINE_JOBS = 5120;
+
+// Every environment variable a planner reads when it is created, parsed once (INTEGRATION.md has the
+// table). A planner keeps its settings for life; only three test hooks are read per call, at their
+// call sites: ARMOUR_TRACK_KERNEL (armour_track), ARMOUR_DUMP_LANE (armour_get_reach_dump) and
+// ARMOUR_PC_GROW_FAIL (ensure_plane_cache).
+struct Settings {
+    // g_planners sees this process's planners only; planners of other processes on the same GPU
+    // (torchrun ranks folded onto one device, several armour_main servers) are declared with
+    // ARMOUR_DEVICE_SHARED=1 (DESIGN.md §4: it only chooses the bundle kernel's shape)
+    bool device_shared = false;
+    // Concurrent planners share the GPU. The bundle reach kernel holds every CU it runs on for
+    // its whole launch (persistent, 2 workgroups x 78 KB LDS per CU), so another planner's solver
+    // kernels wait for it. ARMOUR_REACH_CU_RESERVE=k keeps k CUs out of the reach stream's CU mask
+    // for them; ARMOUR_SOLVER_PRIORITY=1 gives the solver stream the highest queue priority.
+    bool solver_priority = false;
+    int cu_reserve = 0;
+    int tail_worlds = 16;     // sync-free tail below this many running worlds (ARMOUR_TAIL_WORLDS, 0: off)
+    int tail_search = 1;      // its line search (ARMOUR_TAIL_SEARCH): 0 rounds only, 1 adaptive, 2 always one round
+    bool da_lds = true;       // wide grids take ipm_rows_DA_lds (ARMOUR_DA_REGS set: the register form)
+    bool sq_off = false;      // ARMOUR_SQ_THRESHOLD=0: the sqrt reach kernels even where the squared threshold is verified
+    // Engine choice per batch: batches of at most job_engine_jobs jobs take the per-job engine
+    // (ARMOUR_JOB_ENGINE_JOBS); ARMOUR_ENGINE=job|lane forces one engine (0: by size, 1: job, 2: lane)
+    int engine = 0;
+    long job_engine_jobs = JOB_ENGINE_JOBS;
+    bool job_narrow = false;  // ARMOUR_REACH_WIDE=0 (diagnostics): small batches on the 128-thread kernel too
+    int reach_wg_per_cu = 0;  // ARMOUR_REACH_WG_PER_CU (diagnostics): fewer resident workgroups per CU than fit
+    int engine_mode = 0;      // ARMOUR_ENGINE_MODE: per-job engine mode experiments (ReachArgs::mode)
+    // ARMOUR_PROFILE_OPS set: the profile buffer exists; =1: per-op cycles/terms; =2: phase totals
+    // (each distorts the other); =3: no op profiling; [start, end] wall clock (100 MHz) of every
+    // bundle of the last launch after the op tables (bundle-engine load balance)
+    bool profile = false;
+    int profile_mode = 0;
+    bool dump_ops = false;    // ARMOUR_DUMP_OPS set: op-by-op state of job 0 (bundle engine: of bundle 0)
+    int lane_shape = -1;      // ARMOUR_LANE_SHAPE: 0 wide, 1 dense, -1 chosen per launch
+    long lane_hcap = 1L << 16, lane_ccap = 1L << 17;  // ARMOUR_LANE_HCAP / _CCAP: bundle arena capacities
+    bool eval_f32 = false;    // ARMOUR_EVAL_F32: fp32 constraint evaluation (tolerance study only)
+    bool eval_full = false;   // ARMOUR_EVAL_FULL: always the full-capacity evaluation kernels
+    int eval_skip = 0;        // ARMOUR_EVAL_SKIP: skips slicing (1) / collision rows (2), for part timings (NlpDev::diag)
+    int mu_strategy = -1;     // ARMOUR_MU_STRATEGY: 0 monotone, 1 any other value (adaptive), -1 unset: IpmOptions' default
+    int resto_max = -1;       // ARMOUR_RESTORATION: restoration phases per solve (0: none), -1 unset: the default
+    bool plane_cache = true;  // ARMOUR_PLANE_CACHE=0: every evaluation on the full 36-plane scan
+    int pc_k = PC_K;          // ARMOUR_PC_K (1..36): plane cache pool records per (link, obstacle) pair
+    bool no_spec = false;     // ARMOUR_NO_SPEC set: sequential line-search rounds only
+    bool resto_rounds = false;     // ARMOUR_RESTO_ROUNDS set: the restoration phase searches round by round
+    bool resto_inline = true;      // ARMOUR_RESTO_INLINE=0: restoration phases after the interior-point loop
+    bool resto_concurrent = true;  // ARMOUR_RESTO_CONCURRENT=0: inline phases on the solver stream
+    // rows per block of the IPM row passes (ARMOUR_ROW_CHUNK overrides for diagnostics, a multiple of
+    // 256). Measured at 327 worlds (tools/chunk_sweep.sh): 2048 rows 34.8 ms of NLP, 1024 34.2 ms, 512
+    // 36.5 ms, 256 43.1 ms: shorter per-thread row loops help the latency-bound tail iterations until
+    // the per-block reductions dominate. Fixed at creation: the partial-sum buffers are sized by it.
+    int row_chunk = 1024;
+
+    static Settings from_env() {
+        auto num = [](const char* e, int dflt) { return e ? std::atoi(e) : dflt; };
+        auto lnum = [](const char* e, long dflt) { return e ? std::atol(e) : dflt; };
+        auto is = [](const char* e, const char* v) { return e && std::strcmp(e, v) == 0; };
+        auto on = [&](const char* e) { return num(e, 0) != 0; };   // set to a non-zero number
+        auto off = [&](const char* e) { return e && std::atoi(e) == 0; };  // set to 0 (or to no number)
+        Settings s;
+        s.device_shared = on(std::getenv("ARMOUR_DEVICE_SHARED"));
+        s.solver_priority = on(std::getenv("ARMOUR_SOLVER_PRIORITY"));
+        s.cu_reserve = num(std::getenv("ARMOUR_REACH_CU_RESERVE"), 0);
+        s.tail_worlds = num(std::getenv("ARMOUR_TAIL_WORLDS"), 16);
+        if (const char* e = std::getenv("ARMOUR_TAIL_SEARCH")) s.tail_search = is(e, "rounds") ? 0 : is(e, "one") ? 2 : 1;
+        s.da_lds = !std::getenv("ARMOUR_DA_REGS");
+        s.sq_off = off(std::getenv("ARMOUR_SQ_THRESHOLD"));
+        const char* eng = std::getenv("ARMOUR_ENGINE");
+        s.engine = is(eng, "job") ? 1 : is(eng, "lane") ? 2 : 0;
+        s.job_engine_jobs = lnum(std::getenv("ARMOUR_JOB_ENGINE_JOBS"), JOB_ENGINE_JOBS);
+        s.job_narrow = off(std::getenv("ARMOUR_REACH_WIDE"));
+        s.reach_wg_per_cu = num(std::getenv("ARMOUR_REACH_WG_PER_CU"), 0);
+        s.engine_mode = num(std::getenv("ARMOUR_ENGINE_MODE"), 0);
+        s.profile = std::getenv("ARMOUR_PROFILE_OPS") != nullptr;
+        s.profile_mode = num(std::getenv("ARMOUR_PROFILE_OPS"), 0);
+        s.dump_ops = std::getenv("ARMOUR_DUMP_OPS") != nullptr;
+        const char* sh = std::getenv("ARMOUR_LANE_SHAPE");
+        s.lane_shape = is(sh, "wide") ? 0 : is(sh, "dense") ? 1 : -1;
+        s.lane_hcap = lnum(std::getenv("ARMOUR_LANE_HCAP"), 1L << 16);
+        s.lane_ccap = lnum(std::getenv("ARMOUR_LANE_CCAP"), 1L << 17);
+        s.eval_f32 = on(std::getenv("ARMOUR_EVAL_F32"));
+        s.eval_full = on(std::getenv("ARMOUR_EVAL_FULL"));
+        s.eval_skip = num(std::getenv("ARMOUR_EVAL_SKIP"), 0);
+        if (const char* e = std::getenv("ARMOUR_MU_STRATEGY")) s.mu_strategy = is(e, "monotone") ? 0 : 1;
+        if (const char* e = std::getenv("ARMOUR_RESTORATION")) s.resto_max = std::max(std::atoi(e), 0);
+        s.plane_cache = !off(std::getenv("ARMOUR_PLANE_CACHE"));
+        s.pc_k = num(std::getenv("ARMOUR_PC_K"), PC_K);
+        s.no_spec = std::getenv("ARMOUR_NO_SPEC") != nullptr;
+        s.resto_rounds = std::getenv("ARMOUR_RESTO_ROUNDS") != nullptr;
+        s.resto_inline = !off(std::getenv("ARMOUR_RESTO_INLINE"));
+        s.resto_concurrent = !off(std::getenv("ARMOUR_RESTO_CONCURRENT"));
+        const int c = num(std::getenv("ARMOUR_ROW_CHUNK"), 1024);
+        s.row_chunk = (c >= 256 && c % 256 == 0) ? c : 1024;
+        return s;
+    }
+};
+
 struct armour_planner {
     armour_config cfg;
+    Settings set;
     int T = 0, NJ = 0, Omax = 0, Wmax = 0, ncu = 0, reach_grid = 0;
     RobotParams rp;
     RobotParams* d_rp = nullptr;
@@ -68,15 +204,14 @@ struct armour_planner {
     int reach_cus = 0;               // CUs the reach stream may use
     hipEvent_t ev[6];
     hipEvent_t tev[2];        // sync-free solver tail: end of iteration it (parity it & 1)
-    int tail_worlds = 16;     // sync-free tail below this many running worlds (ARMOUR_TAIL_WORLDS, 0: off)
     // reach program (ProgramBuilder::ops) on the device
     Op* d_prog = nullptr;
     int* d_slot_off = nullptr;
     JrsJoint* d_jrs = nullptr;
     int nops = 0, nslots = 0;
     unsigned long long* d_bytes = nullptr;
-    unsigned long long* d_prof = nullptr;  // per-op [cycles, terms] when ARMOUR_PROFILE_OPS is set
-    double* d_dump = nullptr;              // op-by-op state of job 0 when ARMOUR_DUMP_OPS is set
+    unsigned long long* d_prof = nullptr;  // per-op [cycles, terms] (Settings::profile)
+    double* d_dump = nullptr;              // op-by-op state of job 0 (Settings::dump_ops)
     double last_kernel_ms = 0, last_bytes = 0;
     double last_span_ms = -1;  // device-clock execution span of the last reach launch (armour_get_reach_span)
     int wall_khz = 0;          // hipDeviceAttributeWallClockRate
@@ -100,21 +235,16 @@ struct armour_planner {
     double* d_tables = nullptr;  // ARMTD: offline JRS tables [W][NF][6][T]
     long job_max = 0;         // batches of at most this many jobs (W x T) run on the per-job engine
     bool job_fits = true;     // the reach program's payload pool fits the per-job engine's LDS
-    bool job_narrow = false;  // ARMOUR_REACH_WIDE=0 (diagnostics): small batches on the 128-thread kernel too
-    bool eval_f32 = false;    // ARMOUR_EVAL_F32: fp32 constraint evaluation (tolerance study only)
-    bool eval_full = false;   // ARMOUR_EVAL_FULL: always the full-capacity evaluation kernels
     // largest link / torque k-monomial counts of the last reach (both engines record them in
     // occ[3], occ[4], published with the error flags), and the first launch's occupancy
     unsigned long long h_occ[8] = {};
     int mono_max[2] = {CAP_LM, CAP_UM};
     int lane_grid = 0;        // workgroups with an arena: the larger (dense) shape's resident set
     int lane_slots[2] = {0, 0};  // resident bundle workgroups of the wide / dense kernel shape
-    int lane_shape = -1;      // ARMOUR_LANE_SHAPE: 0 wide, 1 dense, -1 chosen per launch
     bool sq = true;           // reach kernels decide keep / prune on squared norms (rp.simplify_sq_valid)
     int last_shape = 0;       // shape of the last first launch (a capacity retry uses it too)
     int dev = 0;              // the planner's device
     bool counted = false;     // counted in g_planners[dev]
-    bool device_shared = false;  // ARMOUR_DEVICE_SHARED=1: other processes plan on this GPU too
     lane::LaneArgs la;
 
     // nlp
@@ -126,7 +256,6 @@ struct armour_planner {
     bool spec_all = true;     // the sync-free tail's one-round line search (eval_trials_all, ipm_world_Cs_all)
     bool resto_spec = false;  // the restoration phase's one-round search (eval_trials_all, resto_world_Vs)
     bool resto_inline = true; // restoration phases inside the interior-point loop (ARMOUR_RESTO_INLINE=0: after it)
-    bool da_lds = true;       // wide grids take ipm_rows_DA_lds (ARMOUR_DA_REGS=1: the register form)
     // In the sync-free tail the inline restoration phase runs on a second stream, concurrently with
     // the next interior-point iteration (ARMOUR_RESTO_CONCURRENT=0: on the solver stream): its worlds
     // are others than the interior point's, and its speculative rows start after the tail's
@@ -136,7 +265,6 @@ struct armour_planner {
     hipStream_t rstream2 = nullptr;
     hipEvent_t ev_ip = nullptr, ev_pub = nullptr, ev_rend = nullptr;
     size_t resto_soff = 0;
-    int tail_search = 1;      // its use (ARMOUR_TAIL_SEARCH): 0 rounds only, 1 adaptive, 2 always
     WorldState* h_ws = nullptr;
     double* h_f = nullptr;
     int* h_feas = nullptr;
@@ -146,16 +274,16 @@ struct armour_planner {
     std::vector<int> Ow;       // obstacle count of each world of the last batch
     int* d_Ow = nullptr;       // [max_worlds] device copy of a mixed batch's counts (NlpDev::Ow)
     bool reached = false, planned = false, evaluated = false;  // evaluated: slot 0 holds armour_eval_constraints' point
-    // armour_eval_candidates: buffers of its own for max_worlds x cand_cap candidates (allocated on
+    // armour_eval_candidates: buffers of its own for max_worlds x cand.cap candidates (allocated on
     // first use, regrown when a call brings more candidates per world)
     CandDev cd{};
-    int cand_cap = 0;
+    GrowSet cand;
     // armour_check_motion and the episodes (motion_kernels.hip): per-sample minima for max_worlds x
-    // motion_cap samples (allocated on first use, regrown for more samples), the caller's
+    // motion.cap samples (allocated on first use, regrown for more samples), the caller's
     // trajectories and the per-world results; the episode's own arrays, allocated by the first begin
     double* mo_pval = nullptr;
     int* mo_pidx = nullptr;
-    int motion_cap = 0;
+    GrowSet motion;
     double *mo_traj = nullptr, *mo_clear = nullptr;
     int* mo_where = nullptr;
     bool episode = false;      // an episode is running (armour_episode_begin .. any other reach / plan entry)
@@ -163,11 +291,11 @@ struct armour_planner {
     int* ep_accept = nullptr;
     hipEvent_t ep_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     std::vector<armour_episode_state> ep_host;  // the states after the last begin / step
-    // armour_track (track_kernels.hip): inputs and per-rollout outputs for track_cap rollouts,
+    // armour_track (track_kernels.hip): inputs and per-rollout outputs for track.cap rollouts,
     // allocated on first use and regrown on demand
     double *tr_traj = nullptr, *tr_scale = nullptr, *tr_err0 = nullptr, *tr_out = nullptr;
     int* tr_status = nullptr;
-    long track_cap = 0;
+    GrowSet track;
     hipEvent_t tr_ev[2] = {nullptr, nullptr};
     std::vector<void*> allocs;
 
@@ -180,40 +308,15 @@ struct armour_planner {
     }
 };
 
-// rows per block of the IPM row passes (ARMOUR_ROW_CHUNK overrides for diagnostics, a multiple of
-// 256). Measured at 327 worlds (tools/chunk_sweep.sh): 2048 rows 34.8 ms of NLP, 1024 34.2 ms, 512
-// 36.5 ms, 256 43.1 ms: shorter per-thread row loops help the latency-bound tail iterations until
-// the per-block reductions dominate.
-static int row_chunk() {
-    const char* e = std::getenv("ARMOUR_ROW_CHUNK");
-    const int c = e ? std::atoi(e) : 1024;
-    return (c >= 256 && c % 256 == 0) ? c : 1024;
-}
-
-// capacity retry: a quarter of the workgroups, each with four workgroups' buffers
-constexpr int RETRY_SCALE = 4;
-
-// largest batch (jobs = worlds x T) that runs on the per-job engine; measured crossover, DESIGN.md §4
-constexpr long JOB_ENGINE_JOBS = 5120;
-
-static int planner_init(armour_planner* p, const armour_config* cfg, const armour_robot* robot, bool armtd = false) {
-    p->cfg = *cfg;
-    p->armtd = armtd;
-    if (!robot && cfg->robot != 0) return fail(ARMOUR_E_ARG, "unknown robot id");
-    if (cfg->num_time_steps <= 0 || (cfg->num_time_steps % 2) != 0)
-        return fail(ARMOUR_E_ARG, "num_time_steps must be a positive even number (KPR/Parameters.h:16)");
-    if (cfg->max_obstacles < 0 || cfg->max_obstacles > MAX_OBS || cfg->max_worlds <= 0)
-        return fail(ARMOUR_E_ARG, "bad max_obstacles (0..40, MAX_OBSTACLE_NUM) / max_worlds");
+// planner_init, phase 1: the device, the robot, the streams and events
+static int init_device(armour_planner* p, const armour_robot* robot) {
+    const armour_config* cfg = &p->cfg;
     if (cfg->device >= 0) HIPCK(hipSetDevice(cfg->device));
     int dev = 0;
     HIPCK(hipGetDevice(&dev));
     p->dev = dev;
     g_planners[dev & 63]++;
     p->counted = true;
-    // g_planners sees this process's planners only; planners of other processes on the same GPU
-    // (torchrun ranks folded onto one device, several armour_main servers) are declared with
-    // ARMOUR_DEVICE_SHARED=1 (DESIGN.md §4: it only chooses the bundle kernel's shape)
-    if (const char* e = std::getenv("ARMOUR_DEVICE_SHARED")) p->device_shared = std::atoi(e) != 0;
     HIPCK(hipDeviceGetAttribute(&p->ncu, hipDeviceAttributeMultiprocessorCount, dev));
     if (hipDeviceGetAttribute(&p->wall_khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess) p->wall_khz = 0;
     if (robot) {
@@ -226,38 +329,33 @@ static int planner_init(armour_planner* p, const armour_config* cfg, const armou
     p->NJ = p->rp.num_joints;
     p->Omax = cfg->max_obstacles;
     p->Wmax = cfg->max_worlds;
-    {
-        // Concurrent planners share the GPU. The bundle reach kernel holds every CU it runs on for
-        // its whole launch (persistent, 2 workgroups x 78 KB LDS per CU), so another planner's solver
-        // kernels wait for it. ARMOUR_REACH_CU_RESERVE=k keeps k CUs out of the reach stream's CU mask
-        // for them; ARMOUR_SOLVER_PRIORITY=1 gives the solver stream the highest queue priority.
-        const char* pr = std::getenv("ARMOUR_SOLVER_PRIORITY");
-        int lo = 0, hi = 0;
-        HIPCK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        const int prio = (pr && std::atoi(pr) != 0) ? hi : 0;
-        HIPCK(hipStreamCreateWithPriority(&p->stream, hipStreamNonBlocking, prio));
-        const char* rv = std::getenv("ARMOUR_REACH_CU_RESERVE");
-        const int reserve = rv ? std::atoi(rv) : 0;
-        p->reach_cus = p->ncu;
-        if (reserve > 0 && reserve < p->ncu) {
-            std::vector<uint32_t> mask((p->ncu + 31) / 32, 0u);
-            for (int c = 0; c < p->ncu; c++) mask[c / 32] |= 1u << (c % 32);
-            for (int i = 0; i < reserve; i++) {
-                const int c = (int)((long)i * p->ncu / reserve);
-                mask[c / 32] &= ~(1u << (c % 32));
-            }
-            HIPCK(hipExtStreamCreateWithCUMask(&p->rstream, (uint32_t)mask.size(), mask.data()));
-            p->reach_cus = p->ncu - reserve;
-        } else {
-            p->rstream = p->stream;
+    int lo = 0, hi = 0;
+    HIPCK(hipDeviceGetStreamPriorityRange(&lo, &hi));
+    HIPCK(hipStreamCreateWithPriority(&p->stream, hipStreamNonBlocking, p->set.solver_priority ? hi : 0));
+    const int reserve = p->set.cu_reserve;
+    p->reach_cus = p->ncu;
+    if (reserve > 0 && reserve < p->ncu) {
+        std::vector<uint32_t> mask((p->ncu + 31) / 32, 0u);
+        for (int c = 0; c < p->ncu; c++) mask[c / 32] |= 1u << (c % 32);
+        for (int i = 0; i < reserve; i++) {
+            const int c = (int)((long)i * p->ncu / reserve);
+            mask[c / 32] &= ~(1u << (c % 32));
         }
+        HIPCK(hipExtStreamCreateWithCUMask(&p->rstream, (uint32_t)mask.size(), mask.data()));
+        p->reach_cus = p->ncu - reserve;
+    } else {
+        p->rstream = p->stream;
     }
     for (int i = 0; i < 6; i++) HIPCK(hipEventCreate(&p->ev[i]));
     for (int i = 0; i < 2; i++) HIPCK(hipEventCreateWithFlags(&p->tev[i], hipEventDisableTiming));
-    if (const char* e = std::getenv("ARMOUR_TAIL_WORLDS")) p->tail_worlds = std::atoi(e);
-    p->da_lds = !std::getenv("ARMOUR_DA_REGS");
-    if (const char* e = std::getenv("ARMOUR_TAIL_SEARCH"))
-        p->tail_search = !std::strcmp(e, "rounds") ? 0 : !std::strcmp(e, "one") ? 2 : 1;
+    return 0;
+}
+
+// planner_init, phase 2: the robot and input arrays, the reach outputs and program, and the
+// workspaces of the engines this planner can need
+static int init_reach(armour_planner* p) {
+    const Settings& set = p->set;
+    const int dev = p->dev;
     const int T = p->T, NJ = p->NJ, Om = p->Omax > 0 ? p->Omax : 1, Wm = p->Wmax;
     int rc = 0;
     if ((rc = p->alloc(&p->d_rp, 1))) return rc;
@@ -268,8 +366,7 @@ static int planner_init(armour_planner* p, const armour_config* cfg, const armou
         hipLaunchKernelGGL(sq_threshold_kernel, dim3(1), dim3(1), 0, nullptr, p->d_rp);
         HIPCK(hipGetLastError());
         HIPCK(hipMemcpy(&p->rp, p->d_rp, sizeof(RobotParams), hipMemcpyDeviceToHost));
-        const char* e = std::getenv("ARMOUR_SQ_THRESHOLD");
-        if (e && std::atoi(e) == 0 && p->rp.simplify_sq_valid) {
+        if (set.sq_off && p->rp.simplify_sq_valid) {
             p->rp.simplify_sq_valid = 0;
             HIPCK(hipMemcpy(p->d_rp, &p->rp, sizeof(RobotParams), hipMemcpyHostToDevice));
         }
@@ -293,45 +390,35 @@ static int planner_init(armour_planner* p, const armour_config* cfg, const armou
         (rc = p->alloc(&ro.err, (size_t)Wm)))
         return rc;
     // reach program
-    {
-        ProgramBuilder pb;
-        pb.build(p->rp, p->armtd);
-        int pool = 0;
-        const std::vector<int> off = pb.slot_offsets(&pool);
-        {
-            const char* eng = std::getenv("ARMOUR_ENGINE");
-            const bool job_engine = eng && std::strcmp(eng, "job") == 0;
-            // the bundle engine's payload pool lives in HBM, sized below; the per-job engine's in LDS
-            // (POOL_DOUBLES): a robot whose program does not fit it (Fetch: 8 links) runs on the
-            // bundle engine only
-            p->job_fits = pool <= POOL_DOUBLES;
-            if (pb.nslots > MAX_SLOTS || (job_engine && pool > POOL_DOUBLES)) {
-                char buf[200];
-                std::snprintf(buf, sizeof(buf), "reach program needs %d handle slots (kernel: %d) and %d payload doubles (per-job engine: %d)",
-                              pb.nslots, MAX_SLOTS, pool, POOL_DOUBLES);
-                return fail(ARMOUR_E_CAPACITY, buf);
-            }
-        }
-        p->nops = (int)pb.ops.size();
-        p->nslots = pb.nslots;
-        if ((rc = p->alloc(&p->d_prog, pb.ops.size())) || (rc = p->alloc(&p->d_bytes, 1)) ||
-            (rc = p->alloc(&p->d_slot_off, off.size())))
-            return rc;
-        HIPCK(hipMemcpy(p->d_prog, pb.ops.data(), sizeof(Op) * pb.ops.size(), hipMemcpyHostToDevice));
-        HIPCK(hipMemcpy(p->d_slot_off, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice));
-        if (std::getenv("ARMOUR_PROFILE_OPS")) {
-            // =3: no op profiling; [start, end] wall clock (100 MHz) of every bundle of the last launch
-            // after the op tables (bundle-engine load balance)
-            const size_t nbt = 2 * (((size_t)p->Wmax * p->T + lane::LG - 1) / lane::LG);
-            const size_t n = 2 * pb.ops.size() + 16 + 8 * OP_NCODES + nbt;
-            if ((rc = p->alloc(&p->d_prof, n))) return rc;
-            HIPCK(hipMemset(p->d_prof, 0, sizeof(unsigned long long) * n));
-        }
+    ProgramBuilder pb;
+    pb.build(p->rp, p->armtd);
+    int pool = 0;
+    const std::vector<int> off = pb.slot_offsets(&pool);
+    // the bundle engine's payload pool lives in HBM, sized below; the per-job engine's in LDS
+    // (POOL_DOUBLES): a robot whose program does not fit it (Fetch: 8 links) runs on the
+    // bundle engine only
+    p->job_fits = pool <= POOL_DOUBLES;
+    if (pb.nslots > MAX_SLOTS || (set.engine == 1 && pool > POOL_DOUBLES)) {
+        char buf[200];
+        std::snprintf(buf, sizeof(buf), "reach program needs %d handle slots (kernel: %d) and %d payload doubles (per-job engine: %d)",
+                      pb.nslots, MAX_SLOTS, pool, POOL_DOUBLES);
+        return fail(ARMOUR_E_CAPACITY, buf);
+    }
+    p->nops = (int)pb.ops.size();
+    p->nslots = pb.nslots;
+    if ((rc = p->alloc(&p->d_prog, pb.ops.size())) || (rc = p->alloc(&p->d_bytes, 1)) ||
+        (rc = p->alloc(&p->d_slot_off, off.size())))
+        return rc;
+    HIPCK(hipMemcpy(p->d_prog, pb.ops.data(), sizeof(Op) * pb.ops.size(), hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(p->d_slot_off, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice));
+    if (set.profile) {
+        const size_t nbt = 2 * (((size_t)p->Wmax * p->T + lane::LG - 1) / lane::LG);
+        const size_t n = 2 * pb.ops.size() + 16 + 8 * OP_NCODES + nbt;
+        if ((rc = p->alloc(&p->d_prof, n))) return rc;
+        HIPCK(hipMemset(p->d_prof, 0, sizeof(unsigned long long) * n));
     }
     // reach workspace: four resident workgroups per CU, each with a private arena
     {
-        // ARMOUR_REACH_WG_PER_CU (diagnostics): fewer resident workgroups per CU than the 4 that fit
-        const char* wg = std::getenv("ARMOUR_REACH_WG_PER_CU");
         int fit = REACH_WG_PER_CU;  // as many as the CU's LDS holds (a persistent grid larger than
         {                           // the resident set would run its last workgroups one job late)
             hipFuncAttributes fa{};
@@ -340,7 +427,7 @@ static int planner_init(armour_planner* p, const armour_config* cfg, const armou
             HIPCK(hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev));
             if (fa.sharedSizeBytes > 0) fit = std::max(1, std::min<int>(fit, (int)(lds_cu / fa.sharedSizeBytes)));
         }
-        const int per = wg ? std::atoi(wg) : fit;
+        const int per = set.reach_wg_per_cu;
         p->reach_grid = (per >= 1 && per <= fit ? per : fit) * p->ncu;
     }
     // Engine choice per batch. The bundle engine (lane_kernel.hip) runs 64 jobs per workgroup and
@@ -348,35 +435,22 @@ static int planner_init(armour_planner* p, const armour_config* cfg, const armou
     // per-job engine (reach_kernel.hip) runs one job per workgroup, ~4 ms per round of up to
     // 4 x CUs jobs. So small batches (the drop-in's single plan) take the per-job engine:
     // batches of at most job_max jobs (ARMOUR_JOB_ENGINE_JOBS; ARMOUR_ENGINE=job|lane forces one).
-    {
-        const char* eng = std::getenv("ARMOUR_ENGINE");
-        const char* jm = std::getenv("ARMOUR_JOB_ENGINE_JOBS");
-        p->job_max = jm ? std::atol(jm) : JOB_ENGINE_JOBS;
-        const char* wide = std::getenv("ARMOUR_REACH_WIDE");
-        p->job_narrow = wide && std::atoi(wide) == 0;
-        if (eng && std::strcmp(eng, "job") == 0) p->job_max = (long)Wm * T;
-        if ((eng && std::strcmp(eng, "lane") == 0) || !p->job_fits) p->job_max = 0;
-        p->has_job = p->job_max > 0;
-        p->has_lane = (long)Wm * T > p->job_max;
-        if (p->has_job) p->reach_grid = (int)std::min<long>(p->reach_grid, std::min<long>(p->job_max, (long)Wm * T));
-    }
+    p->job_max = set.job_engine_jobs;
+    if (set.engine == 1) p->job_max = (long)Wm * T;
+    if (set.engine == 2 || !p->job_fits) p->job_max = 0;
+    p->has_job = p->job_max > 0;
+    p->has_lane = (long)Wm * T > p->job_max;
+    if (p->has_job) p->reach_grid = (int)std::min<long>(p->reach_grid, std::min<long>(p->job_max, (long)Wm * T));
     ReachArgs& ra = p->ra;
     ra.prog = p->d_prog;
     ra.nops = p->nops;
     ra.slot_off = p->d_slot_off;
     ra.nslots = p->nslots;
     ra.bytes = p->d_bytes;
-    // ARMOUR_PROFILE_OPS=1: per-op cycles/terms; =2: phase totals (each distorts the other)
-    const char* pm = std::getenv("ARMOUR_PROFILE_OPS");
-    ra.prof = (pm && std::atoi(pm) == 2) ? nullptr : p->d_prof;
-    ra.phase = (pm && std::atoi(pm) == 2) ? p->d_prof + 2 * p->nops : nullptr;
-    ra.mode = std::getenv("ARMOUR_ENGINE_MODE") ? std::atoi(std::getenv("ARMOUR_ENGINE_MODE")) : 0;
+    ra.prof = set.profile_mode == 2 ? nullptr : p->d_prof;
+    ra.phase = set.profile_mode == 2 ? p->d_prof + 2 * p->nops : nullptr;
+    ra.mode = set.engine_mode;
     ra.dump = nullptr;
-    if (std::getenv("ARMOUR_DUMP_OPS")) {
-        if ((rc = p->alloc(&p->d_dump, (size_t)p->nops * DUMP_W))) return rc;
-        HIPCK(hipMemset(p->d_dump, 0, sizeof(double) * p->nops * DUMP_W));
-        ra.dump = p->d_dump;
-    }
     if ((rc = p->alloc(&p->d_jrs, jobs * NF)) || (rc = p->alloc(&p->d_occ, 8)) || (rc = p->alloc(&p->d_done, 1))) return rc;
     HIPCK(hipMemset(p->d_done, 0, sizeof(unsigned)));
     {
@@ -387,12 +461,6 @@ static int planner_init(armour_planner* p, const armour_config* cfg, const armou
         p->h_sum[RSUM_SEQ] = 0;
         ra.rc = p->rc;
         ra.ntq = p->armtd ? 0 : NF;
-    }
-    {
-        const char* f32 = std::getenv("ARMOUR_EVAL_F32");
-        p->eval_f32 = f32 && std::atoi(f32) != 0;
-        const char* ef = std::getenv("ARMOUR_EVAL_FULL");
-        p->eval_full = ef && std::atoi(ef) != 0;
     }
     if (p->has_job) {
         ra.arena_cap = 1 << 17;
@@ -423,23 +491,12 @@ static int planner_init(armour_planner* p, const armour_config* cfg, const armou
                 if (fa.sharedSizeBytes > 0) per_cu = std::max(1, std::min<int>(per_cu, (int)(lds_cu / fa.sharedSizeBytes)));
                 p->lane_slots[k] = p->reach_cus * per_cu;
             }
-            const char* sh = std::getenv("ARMOUR_LANE_SHAPE");
-            if (sh && std::strcmp(sh, "wide") == 0) p->lane_shape = 0;
-            if (sh && std::strcmp(sh, "dense") == 0) p->lane_shape = 1;
         }
         const long slots = std::max(p->lane_slots[0], p->lane_slots[1]);
         p->lane_grid = (int)(bundles < slots ? bundles : slots);
-        const char* hc = std::getenv("ARMOUR_LANE_HCAP");
-        const char* cc = std::getenv("ARMOUR_LANE_CCAP");
-        la.hcap = hc ? std::atol(hc) : (1L << 16);
-        la.ccap = cc ? std::atol(cc) : (1L << 17);
+        la.hcap = set.lane_hcap;
+        la.ccap = set.lane_ccap;
         la.gcap = 1 << 15;
-        int pool = 0;
-        {
-            ProgramBuilder pb;
-            pb.build(p->rp, p->armtd);
-            (void)pb.slot_offsets(&pool);
-        }
         la.pool_rows = pool + 9 + 2 * NF;  // + the torque-radius scratch rows (lane_kernel.hip)
         // buffers of at least RETRY_SCALE workgroups, so even a one-world batch has a capacity retry
         const size_t G = (size_t)std::max(p->lane_grid, RETRY_SCALE), LGs = lane::LG;
@@ -458,31 +515,36 @@ static int planner_init(armour_planner* p, const armour_config* cfg, const armou
         la.slot_off = p->d_slot_off;
         la.nslots = p->nslots;
         la.bytes = p->d_bytes;
-        const bool btimes = pm && std::atoi(pm) == 3;
+        const bool btimes = set.profile_mode == 3;
         la.prof = btimes ? nullptr : p->d_prof;
         la.btime = btimes ? p->d_prof + 2 * p->nops + 16 + 8 * OP_NCODES : nullptr;
         la.dump = nullptr;
-        if (p->d_dump) {
-            (void)hipFree(p->d_dump);
-            p->allocs.erase(std::find(p->allocs.begin(), p->allocs.end(), (void*)p->d_dump));
-            if ((rc = p->alloc(&p->d_dump, (size_t)p->nops * DUMP_W * lane::LG))) return rc;
-            HIPCK(hipMemset(p->d_dump, 0, sizeof(double) * p->nops * DUMP_W * lane::LG));
-            la.dump = p->d_dump;
-            ra.dump = nullptr;  // the op dump follows the bundle engine when it exists
-        }
     }
-    // NLP
+    if (set.dump_ops) {
+        // the op dump follows the bundle engine when it exists (one column per job of bundle 0)
+        const size_t n = (size_t)p->nops * DUMP_W * (p->has_lane ? lane::LG : 1);
+        if ((rc = p->alloc(&p->d_dump, n))) return rc;
+        HIPCK(hipMemset(p->d_dump, 0, sizeof(double) * n));
+        (p->has_lane ? p->la.dump : ra.dump) = p->d_dump;
+    }
+    return 0;
+}
+
+// planner_init, phase 3: the solver's arrays, its options and the loop variants it may take
+static int init_solver(armour_planner* p) {
+    const Settings& set = p->set;
+    const int T = p->T, NJ = p->NJ, Om = p->Omax > 0 ? p->Omax : 1, Wm = p->Wmax;
+    const size_t jobs = (size_t)Wm * T;
+    int rc = 0;
     NlpDev& d = p->d;
     d.rp = p->d_rp;
-    d.diag = std::getenv("ARMOUR_EVAL_SKIP") ? std::atoi(std::getenv("ARMOUR_EVAL_SKIP")) : 0;
+    d.diag = set.eval_skip;
     d.T = T;
     d.NJ = NJ;
-    d.ro = ro;
-    if (cfg->max_iter > 0) d.opt.max_iter = cfg->max_iter;
-    if (const char* ms = std::getenv("ARMOUR_MU_STRATEGY"))  // adaptive (default) or monotone
-        d.opt.mu_strategy = std::strcmp(ms, "monotone") == 0 ? 0 : 1;
-    if (const char* rs = std::getenv("ARMOUR_RESTORATION"))  // restoration phases per solve (0: none)
-        d.opt.resto_max = std::atoi(rs) < 0 ? 0 : std::atoi(rs);
+    d.ro = p->ro;
+    if (p->cfg.max_iter > 0) d.opt.max_iter = p->cfg.max_iter;
+    if (set.mu_strategy >= 0) d.opt.mu_strategy = set.mu_strategy;  // adaptive (default) or monotone
+    if (set.resto_max >= 0) d.opt.resto_max = set.resto_max;        // restoration phases per solve (0: none)
     d.resto = 0;
     d.armtd = p->armtd ? 1 : 0;
     d.nt = p->armtd ? 0 : NF * T;
@@ -506,7 +568,8 @@ static int planner_init(armour_planner* p, const armour_config* cfg, const armou
     double** rowbufs[] = {&d.slo, &d.shi, &d.zlo, &d.zhi, &d.dslo, &d.dshi};
     for (double** b : rowbufs)
         if ((rc = p->alloc(b, Wm * Rmax))) return rc;
-    const int nblk_max = (int)((Rmax + row_chunk() - 1) / row_chunk());
+    d.chunk = set.row_chunk;
+    const int nblk_max = (int)((Rmax + d.chunk - 1) / d.chunk);
     if ((rc = p->alloc(&d.partial, (size_t)Wm * nblk_max * KA)) || (rc = p->alloc(&d.partial2, (size_t)Wm * nblk_max * KA2)) ||
         (rc = p->alloc(&d.ws, (size_t)Wm)) ||
         (rc = p->alloc(&p->feas, (size_t)Wm)))
@@ -528,14 +591,9 @@ static int planner_init(armour_planner* p, const armour_config* cfg, const armou
     // (bitwise the same results, slower). Round 4 reserved all 36 per pair (42 MB per world at
     // T = 100, O = 20), which capped the batch a GPU can hold. The pool counter is 32-bit: a batch
     // whose 36 records per pair could exceed it does not use the cache.
-    d.pcache = !(std::getenv("ARMOUR_PLANE_CACHE") && std::atoi(std::getenv("ARMOUR_PLANE_CACHE")) == 0) &&
-               (double)COMB * NJ * std::max(Om, 1) * (double)jobs < 4294967295.0;
+    d.pcache = set.plane_cache && (double)COMB * NJ * std::max(Om, 1) * (double)jobs < 4294967295.0;
     d.pcready = 0;
-    {
-        const char* pk = std::getenv("ARMOUR_PC_K");
-        const int k = pk ? std::atoi(pk) : PC_K;
-        d.pc_pool = std::max(1L, (long)std::min(std::max(k, 1), COMB) * NJ * std::max(Om, 1) * (long)jobs);
-    }
+    d.pc_pool = std::max(1L, (long)std::min(std::max(set.pc_k, 1), COMB) * NJ * std::max(Om, 1) * (long)jobs);
     if (d.pcache && ((rc = p->alloc(&d.pc, 5 * (size_t)d.pc_pool)) || (rc = p->alloc(&d.pcp, (size_t)d.pc_pool)) ||
                      (rc = p->alloc(&d.pcoff, jobs * NJ * (size_t)Om)) || (rc = p->alloc(&d.pcok, jobs)) ||
                      (rc = p->alloc(&d.pcbase, jobs)) || (rc = p->alloc(&d.pcnext, 1))))
@@ -550,16 +608,15 @@ static int planner_init(armour_planner* p, const armour_config* cfg, const armou
     // speculative line-search slots (values only): every world x (max_ls - 1) trials. The speculative
     // round reads the plane cache (ARMOUR planner, fp64); otherwise the rounds run one by one.
     d.K = d.opt.max_ls - 1;
-    p->spec = !std::getenv("ARMOUR_NO_SPEC") && d.K > 0 && d.K <= EV_MAXK && d.pcache && !p->armtd && !p->eval_f32;
+    p->spec = !set.no_spec && d.K > 0 && d.K <= EV_MAXK && d.pcache && !p->armtd && !set.eval_f32;
     // The sync-free tail may search all max_ls trials of its (at most tail_worlds) running worlds in
     // one round (run_solver)
-    p->spec_all = p->spec && p->tail_search > 0 && (d.K + 1) * NJ * Om <= UB_FULL;
+    p->spec_all = p->spec && p->set.tail_search > 0 && (d.K + 1) * NJ * Om <= UB_FULL;
     // the restoration phase searches all max_ls trials of up to every world at once
     p->resto_spec = p->spec && d.opt.resto_max > 0 && d.opt.max_ls <= EV_MAXK + 1 && d.opt.max_ls * NJ * Om <= UB_FULL &&
-                    !std::getenv("ARMOUR_RESTO_ROUNDS");
-    p->resto_inline = p->resto_spec && !(std::getenv("ARMOUR_RESTO_INLINE") && std::atoi(std::getenv("ARMOUR_RESTO_INLINE")) == 0);
-    p->resto_conc = p->resto_inline && p->spec_all && p->tail_worlds > 0 &&
-                    !(std::getenv("ARMOUR_RESTO_CONCURRENT") && std::atoi(std::getenv("ARMOUR_RESTO_CONCURRENT")) == 0);
+                    !set.resto_rounds;
+    p->resto_inline = p->resto_spec && set.resto_inline;
+    p->resto_conc = p->resto_inline && p->spec_all && set.tail_worlds > 0 && set.resto_concurrent;
     if (p->resto_conc) {
         HIPCK(hipStreamCreateWithFlags(&p->rstream2, hipStreamNonBlocking));
         HIPCK(hipEventCreateWithFlags(&p->ev_ip, hipEventDisableTiming));
@@ -570,7 +627,7 @@ static int planner_init(armour_planner* p, const armour_config* cfg, const armou
         // rows of the speculative slots: the interior point's rounds use the first Wm x K (the
         // sync-free tail's one-round search the first nall); a restoration phase Wm x max_ls, after
         // the tail's rows when it runs concurrently with the tail (resto_soff)
-        const size_t nall = p->spec_all ? (size_t)std::min(Wm, std::max(p->tail_worlds, 0)) * (d.K + 1) : 0;
+        const size_t nall = p->spec_all ? (size_t)std::min(Wm, std::max(p->set.tail_worlds, 0)) * (d.K + 1) : 0;
         p->resto_soff = p->resto_conc ? nall : 0;
         const size_t nres = p->resto_spec ? (size_t)Wm * d.opt.max_ls + p->resto_soff : 0;
         const size_t ns = std::max(std::max((size_t)Wm * d.K, nall), nres);
@@ -599,7 +656,20 @@ static int planner_init(armour_planner* p, const armour_config* cfg, const armou
     d.qdes = p->qdes;
     d.obs = p->obs;
     d.Ow = nullptr;
-    if ((rc = p->alloc(&p->d_Ow, (size_t)Wm))) return rc;
+    return p->alloc(&p->d_Ow, (size_t)Wm);
+}
+
+static int planner_init(armour_planner* p, const armour_config* cfg, const armour_robot* robot, bool armtd) {
+    p->cfg = *cfg;
+    p->armtd = armtd;
+    p->set = Settings::from_env();
+    if (!robot && cfg->robot != 0) return fail(ARMOUR_E_ARG, "unknown robot id");
+    if (cfg->num_time_steps <= 0 || (cfg->num_time_steps % 2) != 0)
+        return fail(ARMOUR_E_ARG, "num_time_steps must be a positive even number (KPR/Parameters.h:16)");
+    if (cfg->max_obstacles < 0 || cfg->max_obstacles > MAX_OBS || cfg->max_worlds <= 0)
+        return fail(ARMOUR_E_ARG, "bad max_obstacles (0..40, MAX_OBSTACLE_NUM) / max_worlds");
+    int rc = 0;
+    if ((rc = init_device(p, robot)) || (rc = init_reach(p)) || (rc = init_solver(p))) return rc;
     return 0;
 }
 
@@ -648,65 +718,25 @@ static int check_armtd_world(const armour_armtd_world* w, int max_obstacles, int
     return check_obstacles(w->num_obstacles, w->obstacles, max_obstacles);
 }
 
-static int upload_worlds(armour_planner* p, int W, const armour_world* worlds) {
-    if (W <= 0 || W > p->Wmax || !worlds) return fail(ARMOUR_E_ARG, "num_worlds out of range");
-    for (int w = 0; w < W; w++)
-        if (const int rc = check_world(&worlds[w], p->Omax)) return rc;
-    const int O = worlds[0].num_obstacles;
-    if (O < 0 || O > p->Omax) return fail(ARMOUR_E_ARG, "num_obstacles exceeds max_obstacles");
-    std::vector<double> a(4 * (size_t)W * NF), ob((size_t)W * (O > 0 ? O : 1) * 12, 0.0);
-    for (int w = 0; w < W; w++) {
-        if (worlds[w].num_obstacles != O) return fail(ARMOUR_E_ARG, "all worlds of a batch must have the same num_obstacles");
-        if (O > 0 && !worlds[w].obstacles) return fail(ARMOUR_E_ARG, "null obstacles");
-        for (int i = 0; i < NF; i++) {
-            a[0 * (size_t)W * NF + w * NF + i] = worlds[w].q0[i];
-            a[1 * (size_t)W * NF + w * NF + i] = worlds[w].qd0[i];
-            a[2 * (size_t)W * NF + w * NF + i] = worlds[w].qdd0[i];
-            a[3 * (size_t)W * NF + w * NF + i] = worlds[w].q_des[i];
-        }
-        if (O > 0) std::memcpy(&ob[(size_t)w * O * 12], worlds[w].obstacles, sizeof(double) * O * 12);
-    }
-    const size_t bytes = sizeof(double) * W * NF;
-    HIPCK(hipMemcpyAsync(p->q0, &a[0], bytes, hipMemcpyHostToDevice, p->stream));
-    HIPCK(hipMemcpyAsync(p->qd0, &a[(size_t)W * NF], bytes, hipMemcpyHostToDevice, p->stream));
-    HIPCK(hipMemcpyAsync(p->qdd0, &a[2 * (size_t)W * NF], bytes, hipMemcpyHostToDevice, p->stream));
-    HIPCK(hipMemcpyAsync(p->qdes, &a[3 * (size_t)W * NF], bytes, hipMemcpyHostToDevice, p->stream));
-    if (O > 0) HIPCK(hipMemcpyAsync(p->obs, ob.data(), sizeof(double) * ob.size(), hipMemcpyHostToDevice, p->stream));
-    HIPCK(hipStreamSynchronize(p->stream));  // host staging vectors die at return
-    p->W = W;
-    p->O = O;
-    p->Ow.assign(W, O);
-    NlpDev& d = p->d;
-    d.W = W;
-    d.O = O;
-    d.Ow = nullptr;
-    d.pcready = 0;
-    d.m = d.nt + p->T * p->NJ * O + NF * 4;
-    d.R = d.m + NF;
-    d.chunk = row_chunk();
-    d.nblk = (d.R + d.chunk - 1) / d.chunk;
-    return 0;
-}
-
-// A mixed batch: every world with its own obstacle count, 0 .. max_obstacles. The obstacle array is
-// padded to the batch's largest count (the stride of every per-world slab, as O is for a uniform
-// batch) and the counts go to the device (NlpDev::Ow); the solver then runs the _mx kernels.
-static int upload_worlds_mixed(armour_planner* p, int W, const armour_world* worlds) {
-    if (p->armtd) return fail(ARMOUR_E_ARG, "mixed batches are not available on an ARMTD planner");
-    if (p->eval_f32) return fail(ARMOUR_E_ARG, "mixed batches are not available with the fp32 study (ARMOUR_EVAL_F32)");
+// The batch's worlds, checked (check_world) and copied to the device. A uniform batch: every world
+// with the same obstacle count O. A mixed batch: every world with its own count, 0 .. max_obstacles;
+// the obstacle array is padded to the batch's largest count (the stride of every per-world slab, as
+// O is for a uniform batch) and the counts go to the device (NlpDev::Ow); the solver then runs the
+// _mx kernels.
+static int upload_worlds(armour_planner* p, int W, const armour_world* worlds, bool mixed) {
+    if (mixed && p->armtd) return fail(ARMOUR_E_ARG, "mixed batches are not available on an ARMTD planner");
+    if (mixed && p->set.eval_f32)
+        return fail(ARMOUR_E_ARG, "mixed batches are not available with the fp32 study (ARMOUR_EVAL_F32)");
     if (W <= 0 || W > p->Wmax || !worlds) return fail(ARMOUR_E_ARG, "num_worlds out of range");
     for (int w = 0; w < W; w++)
         if (const int rc = check_world(&worlds[w], p->Omax)) return rc;
     int O = 0;
-    for (int w = 0; w < W; w++) {
-        const int n = worlds[w].num_obstacles;
-        if (n < 0 || n > p->Omax) return fail(ARMOUR_E_ARG, "num_obstacles exceeds max_obstacles");
-        if (n > 0 && !worlds[w].obstacles) return fail(ARMOUR_E_ARG, "null obstacles");
-        O = std::max(O, n);
-    }
+    for (int w = 0; w < W; w++) O = std::max(O, worlds[w].num_obstacles);
     std::vector<double> a(4 * (size_t)W * NF), ob((size_t)W * (O > 0 ? O : 1) * 12, 0.0);
     std::vector<int> ow(W);
     for (int w = 0; w < W; w++) {
+        if (!mixed && worlds[w].num_obstacles != worlds[0].num_obstacles)
+            return fail(ARMOUR_E_ARG, "all worlds of a batch must have the same num_obstacles");
         for (int i = 0; i < NF; i++) {
             a[0 * (size_t)W * NF + w * NF + i] = worlds[w].q0[i];
             a[1 * (size_t)W * NF + w * NF + i] = worlds[w].qd0[i];
@@ -722,7 +752,7 @@ static int upload_worlds_mixed(armour_planner* p, int W, const armour_world* wor
     HIPCK(hipMemcpyAsync(p->qdd0, &a[2 * (size_t)W * NF], bytes, hipMemcpyHostToDevice, p->stream));
     HIPCK(hipMemcpyAsync(p->qdes, &a[3 * (size_t)W * NF], bytes, hipMemcpyHostToDevice, p->stream));
     if (O > 0) HIPCK(hipMemcpyAsync(p->obs, ob.data(), sizeof(double) * ob.size(), hipMemcpyHostToDevice, p->stream));
-    HIPCK(hipMemcpyAsync(p->d_Ow, ow.data(), sizeof(int) * W, hipMemcpyHostToDevice, p->stream));
+    if (mixed) HIPCK(hipMemcpyAsync(p->d_Ow, ow.data(), sizeof(int) * W, hipMemcpyHostToDevice, p->stream));
     HIPCK(hipStreamSynchronize(p->stream));  // host staging vectors die at return
     p->W = W;
     p->O = O;
@@ -730,12 +760,11 @@ static int upload_worlds_mixed(armour_planner* p, int W, const armour_world* wor
     NlpDev& d = p->d;
     d.W = W;
     d.O = O;
-    d.Ow = p->d_Ow;
+    d.Ow = mixed ? p->d_Ow : nullptr;
     d.pcready = 0;
     d.m = d.nt + p->T * p->NJ * O + NF * 4;
     d.R = d.m + NF;
-    d.chunk = row_chunk();
-    d.nblk = (d.R + d.chunk - 1) / d.chunk;
+    d.nblk = (d.R + d.chunk - 1) / d.chunk;  // (d.chunk: Settings::row_chunk, the rows per block the buffers are sized for)
     return 0;
 }
 
@@ -749,7 +778,6 @@ static int upload_armtd(armour_planner* p, int W, const armour_armtd_world* worl
     const size_t ntab = (size_t)NF * 6 * p->T;
     std::vector<double> tab((size_t)W * ntab), kr((size_t)W * NF);
     for (int w = 0; w < W; w++) {
-        if (!worlds[w].jrs_tables) return fail(ARMOUR_E_ARG, "null jrs_tables");
         armour_world& b = base[w];
         for (int i = 0; i < NF; i++) {
             b.q0[i] = worlds[w].q0[i];
@@ -764,7 +792,7 @@ static int upload_armtd(armour_planner* p, int W, const armour_armtd_world* worl
     }
     HIPCK(hipMemcpyAsync(p->d_tables, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, p->stream));
     HIPCK(hipMemcpyAsync((double*)p->d.krange, kr.data(), sizeof(double) * kr.size(), hipMemcpyHostToDevice, p->stream));
-    return upload_worlds(p, W, base.data());  // ends in a synchronisation: tab / kr outlive the copies
+    return upload_worlds(p, W, base.data(), false);  // ends in a synchronisation: tab / kr outlive the copies
 }
 
 // Bundle kernel shape of a launch of `bundles` bundles (lane_kernel.hip): the dense shape (three
@@ -774,23 +802,18 @@ static int upload_armtd(armour_planner* p, int W, const armour_armtd_world* worl
 // Measured: three planners x 327 worlds dense 5324-5363 against 5187 plans/s;
 // three planners x 85 worlds (config 4's 256-world job) wide 63.5 against 72.1 ms.
 static int lane_shape_for(armour_planner* p, long bundles) {
-    int shape = p->lane_shape;
+    int shape = p->set.lane_shape;
     if (shape < 0)
         shape = (bundles > p->lane_slots[0] ||
-                 ((p->device_shared || g_planners[p->dev & 63].load() > 1) && bundles > p->reach_cus)) ? 1 : 0;
+                 ((p->set.device_shared || g_planners[p->dev & 63].load() > 1) && bundles > p->reach_cus)) ? 1 : 0;
     p->last_shape = shape;
     return shape;
 }
 static void launch_lane(int shape, bool sq, int grid, hipStream_t s, const RobotParams* rp, const lane::LaneArgs& la,
                         const ReachOut& ro) {
-    if (shape == 1 && sq)
-        hipLaunchKernelGGL(lane::lane_reach_kernel<lane::LaneDense>, dim3(grid), dim3(lane::LT), 0, s, rp, la, ro);
-    else if (shape == 1)
-        hipLaunchKernelGGL(lane::lane_reach_kernel<lane::LaneDenseSqrt>, dim3(grid), dim3(lane::LT), 0, s, rp, la, ro);
-    else if (sq)
-        hipLaunchKernelGGL(lane::lane_reach_kernel<lane::LaneWide>, dim3(grid), dim3(lane::LT), 0, s, rp, la, ro);
-    else
-        hipLaunchKernelGGL(lane::lane_reach_kernel<lane::LaneWideSqrt>, dim3(grid), dim3(lane::LT), 0, s, rp, la, ro);
+    auto k = shape == 1 ? (sq ? lane::lane_reach_kernel<lane::LaneDense> : lane::lane_reach_kernel<lane::LaneDenseSqrt>)
+                        : (sq ? lane::lane_reach_kernel<lane::LaneWide> : lane::lane_reach_kernel<lane::LaneWideSqrt>);
+    hipLaunchKernelGGL(k, dim3(grid), dim3(lane::LT), 0, s, rp, la, ro);
 }
 
 // reach set for the uploaded batch. The whole phase is three kernel launches on the reach stream
@@ -833,15 +856,10 @@ static int run_reach(armour_planner* p) {
         launch_lane(shape, p->sq, lg, rs, p->d_rp, la, p->ro);
     } else {
         // a batch that fits the chip in one round at two jobs per CU takes the wide kernel
-        const bool wide = jobs <= (long)REACH_WIDE_PER_CU * p->ncu && !p->job_narrow;
-        if (wide && p->sq)
-            hipLaunchKernelGGL((reach_kernel<REACH_WIDE_THREADS, true>), dim3(grid), dim3(REACH_WIDE_THREADS), 0, rs, p->d_rp, ra, p->ro);
-        else if (wide)
-            hipLaunchKernelGGL((reach_kernel<REACH_WIDE_THREADS, false>), dim3(grid), dim3(REACH_WIDE_THREADS), 0, rs, p->d_rp, ra, p->ro);
-        else if (p->sq)
-            hipLaunchKernelGGL((reach_kernel<REACH_THREADS, true>), dim3(grid), dim3(REACH_THREADS), 0, rs, p->d_rp, ra, p->ro);
-        else
-            hipLaunchKernelGGL((reach_kernel<REACH_THREADS, false>), dim3(grid), dim3(REACH_THREADS), 0, rs, p->d_rp, ra, p->ro);
+        const bool wide = jobs <= (long)REACH_WIDE_PER_CU * p->ncu && !p->set.job_narrow;
+        auto k = wide ? (p->sq ? reach_kernel<REACH_WIDE_THREADS, true> : reach_kernel<REACH_WIDE_THREADS, false>)
+                      : (p->sq ? reach_kernel<REACH_THREADS, true> : reach_kernel<REACH_THREADS, false>);
+        hipLaunchKernelGGL(k, dim3(grid), dim3(wide ? REACH_WIDE_THREADS : REACH_THREADS), 0, rs, p->d_rp, ra, p->ro);
     }
     HIPCK(hipGetLastError());
     HIPCK(hipEventRecord(p->ev[4], rs));
@@ -928,7 +946,7 @@ static int run_reach(armour_planner* p) {
 // the certified plane cache of the current reach sets and obstacles (plane_cache_kernel)
 static void ensure_plane_cache(armour_planner* p) {
     NlpDev& d = p->d;
-    if (!d.pcache || d.pcready || d.O == 0 || p->eval_f32) return;
+    if (!d.pcache || d.pcready || d.O == 0 || p->set.eval_f32) return;
     // The pool is sized at creation for ARMOUR_PC_K records per pair; a build whose blocks need
     // more (the count is known only on the device) is repeated on a pool of 1.25x what it needed,
     // so every block is cached. One host wait on the build, which the solver's first kernels wait
@@ -978,7 +996,7 @@ static int nside_count(const armour_planner* p) {
 // the small-capacity evaluation kernels (eval_kernel_small, eval_trials_small: a third of the LDS,
 // five blocks per CU) when the last reach's largest PZs and this batch's pair tables fit them
 static bool eval_small_fits(const armour_planner* p) {
-    return !p->eval_full && !p->armtd && !p->eval_f32 && p->mono_max[0] <= LM_S && p->mono_max[1] <= UM_S;
+    return !p->set.eval_full && !p->armtd && !p->set.eval_f32 && p->mono_max[0] <= LM_S && p->mono_max[1] <= UM_S;
 }
 static void launch_eval(armour_planner* p, dim3 grid, const NlpDev& d, int mode, bool cached = true, hipStream_t s = nullptr) {
     if (!s) s = p->stream;
@@ -987,11 +1005,11 @@ static void launch_eval(armour_planner* p, dim3 grid, const NlpDev& d, int mode,
         hipLaunchKernelGGL(KSEL(eval_kernel_small), grid, dim3(EVAL_THREADS), 0, s, d, mode);
         return;
     }
-    if (d.Ow) {  // a mixed batch (fp64 ARMOUR planner: upload_worlds_mixed)
+    if (d.Ow) {  // a mixed batch (fp64 ARMOUR planner: upload_worlds)
         hipLaunchKernelGGL(c ? eval_kernel_mx<true> : eval_kernel_mx<false>, grid, dim3(EVAL_THREADS), 0, s, d, mode);
         return;
     }
-    auto k = p->eval_f32 ? (d.armtd ? eval_kernel_t<float, true, false> : eval_kernel_t<float, false, false>)
+    auto k = p->set.eval_f32 ? (d.armtd ? eval_kernel_t<float, true, false> : eval_kernel_t<float, false, false>)
                          : c ? (d.armtd ? eval_kernel_t<double, true, true> : eval_kernel_t<double, false, true>)
                              : (d.armtd ? eval_kernel_t<double, true, false> : eval_kernel_t<double, false, false>);
     hipLaunchKernelGGL(k, grid, dim3(EVAL_THREADS), 0, s, d, mode);
@@ -1001,6 +1019,32 @@ static void launch_eval(armour_planner* p, dim3 grid, const NlpDev& d, int mode,
 static void launch_trials(armour_planner* p, int n, const NlpDev& d) {
     const bool small = eval_small_fits(p) && d.K * p->NJ * d.O <= UB_TS;
     hipLaunchKernelGGL(small ? KSEL(eval_trials_small) : KSEL(eval_trials_kernel), dim3(p->T, n), dim3(EVAL_THREADS), 0, p->stream, d);
+}
+
+// One speculative line-search round over n list entries: the values of ds.K trials of every listed
+// world, their row sums, the acceptance tests in trial order, then the chosen trial in full. `all`:
+// the sync-free tail's one-round form over all max_ls trials, round 0's included (eval_trials_all,
+// ipm_world_Cs_all with pass B's world step); else the K trials that remain after round 0.
+static void launch_spec_round(armour_planner* p, int n, const NlpDev& ds, bool all) {
+    if (all)
+        hipLaunchKernelGGL(KSEL(eval_trials_all), dim3(p->T, n), dim3(EVAL_THREADS), 0, p->stream, ds);
+    else
+        launch_trials(p, n, ds);
+    hipLaunchKernelGGL(KSEL(ipm_rows_Cs), dim3(ds.nblk, n * ds.K), dim3(ROW_THREADS), 0, p->stream, ds);
+    hipLaunchKernelGGL(all ? KSEL(ipm_world_Cs_all) : KSEL(ipm_world_Cs), dim3(n), dim3(64), 0, p->stream, ds);
+    launch_eval(p, dim3(p->T, n), ds, 5);
+}
+
+// One restoration-phase iteration in its one-round form, over nb list entries on stream s: the
+// Gauss-Newton pass and world step, the values of all dr.K = max_ls trials, their sums, the tests in
+// trial order (resto_world_Vs), then the chosen trial in full.
+static void launch_resto_round(armour_planner* p, hipStream_t s, int nb, const NlpDev& dr) {
+    hipLaunchKernelGGL(KSEL(resto_rows_G), dim3(dr.nblk, nb), dim3(ROW_THREADS), 0, s, dr);
+    hipLaunchKernelGGL(KSEL(resto_world_G), dim3(nb), dim3(64), 0, s, dr);
+    hipLaunchKernelGGL(KSEL(eval_trials_all), dim3(p->T, nb), dim3(EVAL_THREADS), 0, s, dr);
+    hipLaunchKernelGGL(KSEL(resto_rows_Vs), dim3(dr.nblk, nb * dr.K), dim3(ROW_THREADS), 0, s, dr);
+    hipLaunchKernelGGL(KSEL(resto_world_Vs), dim3(nb), dim3(64), 0, s, dr);
+    launch_eval(p, dim3(p->T, nb), dr, 5, true, s);
 }
 
 // The interior-point loop over the nrun worlds listed in the first iteration list (d_lists[0..]):
@@ -1082,12 +1126,7 @@ static int ipm_loop(armour_planner* p, int nrun) {
             dr.fs = d.fs + p->resto_soff;
             dr.partial_s = d.partial_s + p->resto_soff * (size_t)d.nblk * KA;
         }
-        hipLaunchKernelGGL(KSEL(resto_rows_G), dim3(d.nblk, nb), dim3(ROW_THREADS), 0, s, dr);
-        hipLaunchKernelGGL(KSEL(resto_world_G), dim3(nb), dim3(64), 0, s, dr);
-        hipLaunchKernelGGL(KSEL(eval_trials_all), dim3(p->T, nb), dim3(EVAL_THREADS), 0, s, dr);
-        hipLaunchKernelGGL(KSEL(resto_rows_Vs), dim3(d.nblk, nb * dr.K), dim3(ROW_THREADS), 0, s, dr);
-        hipLaunchKernelGGL(KSEL(resto_world_Vs), dim3(nb), dim3(64), 0, s, dr);
-        launch_eval(p, dim3(p->T, nb), dr, 5, true, s);
+        launch_resto_round(p, s, nb, dr);
         return 0;
     };
     // Launches cover the active worlds only (NlpDev::wl): every line-search round's ipm_world_C
@@ -1110,8 +1149,33 @@ static int ipm_loop(armour_planner* p, int nrun) {
     // values of every trial plus the chosen one's full evaluation; a backtracking world saves a
     // round. The choice changes launches only, never a world's arithmetic.
     int backtracked = nrun;
+    // The end of a sync-free iteration, after its speculative round: the phase iteration, the
+    // iteration's end event, then (from the second tail iteration on) iteration it - 1's lagged
+    // counts: its running count (the worlds iteration it was launched for, the next grid bound),
+    // its backtracking count and the list lengths. `done`: iteration it had nothing to do.
+    auto tail_end = [&](int it, bool& done) -> int {
+        ub = std::min(W0, ub + nrun);
+        if (int rc = resto_iter(it, pend_known > 0 || pub_known > 0 ? ub : 0, p->resto_conc)) return rc;
+        HIPCK(hipEventRecord(p->tev[it & 1], p->stream));
+        HIPCK(hipGetLastError());
+        cur = 1 - cur;
+        if (tail) {
+            HIPCK(hipEventSynchronize(p->tev[(it - 1) & 1]));
+            if (inl) pend_known = flr[6 + ((it - 1) & 1)];
+            pub_known = pub_launched[(it - 1) & 1] ? flr[8 + ((it - 1) & 1)] : 0;
+            const int prev = flr[2 + ((it - 1) & 1)];
+            backtracked = flr[4 + ((it - 1) & 1)];
+            if (prev == 0) {
+                done = true;
+                return 0;
+            }
+            nrun = prev < nrun ? prev : nrun;
+        }
+        tail = true;
+        return 0;
+    };
     for (int it = 0; it <= d.opt.max_iter && nrun > 0; it++) {
-        const bool tl = it > 0 && p->spec && d.pcready && nrun <= p->tail_worlds;
+        const bool tl = it > 0 && p->spec && d.pcready && nrun <= p->set.tail_worlds;
         // this iteration's failed line searches, and the list length its last world kernel reports
         d.rl_app = inl ? RL : nullptr;
         d.pend_flag = inl ? d.flags + 6 + (it & 1) : nullptr;
@@ -1125,11 +1189,11 @@ static int ipm_loop(armour_planner* p, int nrun) {
             hipLaunchKernelGGL(KSEL(ipm_world_A), dim3(nrun), dim3(64), 0, p->stream, di, ns);
         } else {
             // the LDS-accumulator form for grids of several blocks per CU (nlp_kernels.hip rows_DA_body)
-            const bool wide = p->da_lds && (long)d.nblk * nrun >= 4L * p->ncu;
+            const bool wide = p->set.da_lds && (long)d.nblk * nrun >= 4L * p->ncu;
             hipLaunchKernelGGL(wide ? KSEL(ipm_rows_DA_lds) : KSEL(ipm_rows_DA), dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, di);
             hipLaunchKernelGGL(KSEL(ipm_world_DA), dim3(nrun), dim3(64), 0, p->stream, di, ns);
         }
-        const bool one = tl && p->spec_all && (p->tail_search == 2 || backtracked > 0);
+        const bool one = tl && p->spec_all && (p->set.tail_search == 2 || backtracked > 0);
         hipLaunchKernelGGL(KSEL(ipm_rows_B), dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, di);
         if (!one) hipLaunchKernelGGL(KSEL(ipm_world_B), dim3(nrun), dim3(64), 0, p->stream, di);
         if (one) {
@@ -1148,25 +1212,10 @@ static int ipm_loop(armour_planner* p, int nrun) {
             ds.lrun_out = d.cnt + 8 + ((it + 1) & 1);
             ds.nrun_flag = d.flags + 2 + (it & 1);
             ds.bt_flag = d.flags + 4 + (it & 1);
-            hipLaunchKernelGGL(KSEL(eval_trials_all), dim3(p->T, nrun), dim3(EVAL_THREADS), 0, p->stream, ds);
-            hipLaunchKernelGGL(KSEL(ipm_rows_Cs), dim3(d.nblk, nrun * ds.K), dim3(ROW_THREADS), 0, p->stream, ds);
-            hipLaunchKernelGGL(KSEL(ipm_world_Cs_all), dim3(nrun), dim3(64), 0, p->stream, ds);
-            launch_eval(p, dim3(p->T, nrun), ds, 5);
-            ub = std::min(W0, ub + nrun);
-            if (int rc = resto_iter(it, pend_known > 0 || pub_known > 0 ? ub : 0, p->resto_conc)) return rc;
-            HIPCK(hipEventRecord(p->tev[it & 1], p->stream));
-            HIPCK(hipGetLastError());
-            cur = 1 - cur;
-            if (tail) {
-                HIPCK(hipEventSynchronize(p->tev[(it - 1) & 1]));
-                if (inl) pend_known = flr[6 + ((it - 1) & 1)];
-                pub_known = pub_launched[(it - 1) & 1] ? flr[8 + ((it - 1) & 1)] : 0;
-                const int prev = ((volatile int*)p->h_flags)[2 + ((it - 1) & 1)];
-                backtracked = ((volatile int*)p->h_flags)[4 + ((it - 1) & 1)];
-                if (prev == 0) break;
-                nrun = prev < nrun ? prev : nrun;
-            }
-            tail = true;
+            launch_spec_round(p, nrun, ds, true);
+            bool done = false;
+            if (int rc = tail_end(it, done)) return rc;
+            if (done) break;
             continue;
         }
         // Round 0 of the line search for every running world, then one host synchronisation. The
@@ -1204,26 +1253,10 @@ static int ipm_loop(armour_planner* p, int nrun) {
             NlpDev ds = d;
             ds.wl = Ls[1];
             ds.lcount = d.cnt + 5;
-            launch_trials(p, nrun, ds);
-            hipLaunchKernelGGL(KSEL(ipm_rows_Cs), dim3(d.nblk, nrun * d.K), dim3(ROW_THREADS), 0, p->stream, ds);
-            hipLaunchKernelGGL(KSEL(ipm_world_Cs), dim3(nrun), dim3(64), 0, p->stream, ds);
-            launch_eval(p, dim3(p->T, nrun), ds, 5);
-            ub = std::min(W0, ub + nrun);
-            if (int rc = resto_iter(it, pend_known > 0 || pub_known > 0 ? ub : 0, p->resto_conc)) return rc;
-            HIPCK(hipEventRecord(p->tev[it & 1], p->stream));
-            HIPCK(hipGetLastError());
-            cur = 1 - cur;
-            if (tail) {
-                // iteration it - 1's running count: the worlds iteration it was launched for
-                HIPCK(hipEventSynchronize(p->tev[(it - 1) & 1]));
-                if (inl) pend_known = flr[6 + ((it - 1) & 1)];
-                pub_known = pub_launched[(it - 1) & 1] ? flr[8 + ((it - 1) & 1)] : 0;
-                const int prev = ((volatile int*)p->h_flags)[2 + ((it - 1) & 1)];
-                backtracked = ((volatile int*)p->h_flags)[4 + ((it - 1) & 1)];
-                if (prev == 0) break;  // iteration it had nothing to do
-                nrun = prev < nrun ? prev : nrun;
-            }
-            tail = true;
+            launch_spec_round(p, nrun, ds, false);
+            bool done = false;
+            if (int rc = tail_end(it, done)) return rc;
+            if (done) break;
             continue;
         }
         if (nsearch > 0 && p->spec && d.pcready) {
@@ -1231,10 +1264,7 @@ static int ipm_loop(armour_planner* p, int nrun) {
             // tests in trial order, then the chosen trial in full
             NlpDev ds = d;
             ds.wl = Ls[1];
-            launch_trials(p, nsearch, ds);
-            hipLaunchKernelGGL(KSEL(ipm_rows_Cs), dim3(d.nblk, nsearch * d.K), dim3(ROW_THREADS), 0, p->stream, ds);
-            hipLaunchKernelGGL(KSEL(ipm_world_Cs), dim3(nsearch), dim3(64), 0, p->stream, ds);
-            launch_eval(p, dim3(p->T, nsearch), ds, 5);
+            launch_spec_round(p, nsearch, ds, false);
         } else if (nsearch > 0) {
             for (int ls = 1; ls < d.opt.max_ls; ls++) {
                 NlpDev dc = d;
@@ -1301,12 +1331,7 @@ static int run_resto(armour_planner* p, const int* list, int n) {
             di.lcount = k == 0 ? nullptr : p->d.cnt + 8 + (k & 1);
             di.lrun_out = p->d.cnt + 8 + ((k + 1) & 1);
             di.nrun_flag = p->d.flags + 2 + (k & 1);
-            hipLaunchKernelGGL(KSEL(resto_rows_G), dim3(dr.nblk, nb), dim3(ROW_THREADS), 0, p->stream, di);
-            hipLaunchKernelGGL(KSEL(resto_world_G), dim3(nb), dim3(64), 0, p->stream, di);
-            hipLaunchKernelGGL(KSEL(eval_trials_all), dim3(p->T, nb), dim3(EVAL_THREADS), 0, p->stream, di);
-            hipLaunchKernelGGL(KSEL(resto_rows_Vs), dim3(dr.nblk, nb * dr.K), dim3(ROW_THREADS), 0, p->stream, di);
-            hipLaunchKernelGGL(KSEL(resto_world_Vs), dim3(nb), dim3(64), 0, p->stream, di);
-            launch_eval(p, dim3(p->T, nb), di, 5);
+            launch_resto_round(p, p->stream, nb, di);
             HIPCK(hipEventRecord(p->tev[k & 1], p->stream));
             HIPCK(hipGetLastError());
             if (k > 0) {
@@ -1385,42 +1410,31 @@ static int run_solver(armour_planner* p) {
     return 0;
 }
 
-static void track_free(armour_planner* p) {
-    for (void* a : {(void*)p->tr_traj, (void*)p->tr_scale, (void*)p->tr_err0, (void*)p->tr_out, (void*)p->tr_status})
-        if (a) (void)hipFree(a);
-    p->tr_traj = p->tr_scale = p->tr_err0 = p->tr_out = nullptr;
-    p->tr_status = nullptr;
-    p->track_cap = 0;
-}
-
 // buffers of armour_track for NR rollouts
 static int track_reserve(armour_planner* p, long NR) {
     if (!p->tr_ev[0])
         for (int i = 0; i < 2; i++) HIPCK(hipEventCreate(&p->tr_ev[i]));
-    if (NR <= p->track_cap) return 0;
-    HIPCK(hipStreamSynchronize(p->stream));
-    track_free(p);
     const size_t n = (size_t)NR;
-    if (dalloc(&p->tr_traj, n * TRAJ_DOUBLES) != hipSuccess || dalloc(&p->tr_scale, n * 2 * MAX_J) != hipSuccess ||
-        dalloc(&p->tr_err0, n * 2 * NF) != hipSuccess || dalloc(&p->tr_out, n * TRACK_OUT_DOUBLES) != hipSuccess ||
-        dalloc(&p->tr_status, n) != hipSuccess) {
-        track_free(p);
-        return fail(ARMOUR_E_HIP, "hipMalloc failed for the tracking rollouts' buffers (num_traj x num_samples)");
-    }
-    p->track_cap = NR;
-    return 0;
+    return p->track.reserve(p->stream, NR,
+                            {GrowSet::buf(p->tr_traj, n * TRAJ_DOUBLES), GrowSet::buf(p->tr_scale, n * 2 * MAX_J),
+                             GrowSet::buf(p->tr_err0, n * 2 * NF), GrowSet::buf(p->tr_out, n * TRACK_OUT_DOUBLES),
+                             GrowSet::buf(p->tr_status, n)},
+                            "hipMalloc failed for the tracking rollouts' buffers (num_traj x num_samples)");
 }
 
 // Every entry point runs on its planner's device, whatever the calling thread's current device is
 // (handles may be driven from other host threads); the caller's device is restored.
+// The device-level entries (create, self-check, copy bandwidth) name their device themselves.
 struct DeviceScope {
     int prev = -1;
-    explicit DeviceScope(const armour_planner* p) {
+    bool ok = false;  // `device` is current now (a negative device: nothing was asked, the current one stays)
+    explicit DeviceScope(int device) {
         int cur = -1;
-        if (p && p->cfg.device >= 0 && hipGetDevice(&cur) == hipSuccess && cur != p->cfg.device &&
-            hipSetDevice(p->cfg.device) == hipSuccess)
-            prev = cur;
+        if (device < 0 || hipGetDevice(&cur) != hipSuccess) return;
+        ok = cur == device || hipSetDevice(device) == hipSuccess;
+        if (ok && cur != device) prev = cur;
     }
+    explicit DeviceScope(const armour_planner* p) : DeviceScope(p ? p->cfg.device : -1) {}
     ~DeviceScope() {
         if (prev >= 0) (void)hipSetDevice(prev);
     }
@@ -1459,15 +1473,10 @@ __global__ __launch_bounds__(256) void copy_kernel(const copy_v2d* __restrict__ 
 
 int armour_sq_selfcheck(int device, double thr, long long half_width, const double* values, long long n,
                         double* s_star, int* valid, long long* mismatches) {
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    struct Restore {
-        int d;
-        ~Restore() { if (d >= 0) (void)hipSetDevice(d); }
-    } restore{prev};
     if (half_width < 0 || n < 0 || (n > 0 && !values) || !s_star || !valid || !mismatches)
         return fail(ARMOUR_E_ARG, "half_width >= 0, n >= 0, values unless n = 0, and the three outputs");
-    if (hipSetDevice(device) != hipSuccess) return fail(ARMOUR_E_HIP, "hipSetDevice failed (no device?)");
+    DeviceScope device_scope(device);
+    if (!device_scope.ok) return fail(ARMOUR_E_HIP, "hipSetDevice failed (no device?)");
     RobotParams* rp = nullptr;
     double* dv = nullptr;
     unsigned long long* dbad = nullptr;
@@ -1504,14 +1513,9 @@ int armour_sq_selfcheck(int device, double thr, long long half_width, const doub
 }
 
 double armour_copy_bandwidth(int device, size_t bytes, int reps) {
-    int prev = -1;
-    (void)hipGetDevice(&prev);
-    struct Restore {
-        int d;
-        ~Restore() { if (d >= 0) (void)hipSetDevice(d); }
-    } restore{prev};
     if (reps <= 0 || bytes < 16) return fail(ARMOUR_E_ARG, "bytes >= 16 and reps > 0");
-    if (hipSetDevice(device) != hipSuccess) return fail(ARMOUR_E_HIP, "hipSetDevice failed (no device?)");
+    DeviceScope device_scope(device);
+    if (!device_scope.ok) return fail(ARMOUR_E_HIP, "hipSetDevice failed (no device?)");
     const long n = (long)(bytes / 16);
     copy_v2d *a = nullptr, *b = nullptr;
     hipEvent_t e0, e1;
@@ -1544,19 +1548,14 @@ int armour_robot_builtin(int robot_id, armour_robot* out) {
     return 0;
 }
 
-armour_planner* armour_create(const armour_config* cfg) { return armour_create_robot(cfg, nullptr); }
-
-armour_planner* armour_create_robot(const armour_config* cfg, const armour_robot* robot) {
+static armour_planner* create(const armour_config* cfg, const armour_robot* robot, bool armtd) {
     if (!cfg) { fail(ARMOUR_E_ARG, "null config"); return nullptr; }
-    // planner_init makes cfg->device current; the caller's current device is restored on return
-    struct Restore {
-        int dev = -1;
-        Restore() { if (hipGetDevice(&dev) != hipSuccess) dev = -1; }
-        ~Restore() { if (dev >= 0) (void)hipSetDevice(dev); }
-    } restore;
+    // planner_init runs on cfg->device (and reports a device it cannot select); the caller's
+    // current device is restored on return
+    DeviceScope device_scope(cfg->device);
     armour_planner* p = new armour_planner();
-    if (planner_init(p, cfg, robot) != 0) {
-        std::string keep = g_err;
+    if (planner_init(p, cfg, robot, armtd) != 0) {
+        std::string keep = g_err;  // the first error's message, not one of the teardown's
         armour_destroy(p);
         g_err = keep;
         return nullptr;
@@ -1564,34 +1563,18 @@ armour_planner* armour_create_robot(const armour_config* cfg, const armour_robot
     return p;
 }
 
-armour_planner* armour_create_armtd(const armour_config* cfg) {
-    if (!cfg) { fail(ARMOUR_E_ARG, "null config"); return nullptr; }
-    struct Restore {
-        int dev = -1;
-        Restore() { if (hipGetDevice(&dev) != hipSuccess) dev = -1; }
-        ~Restore() { if (dev >= 0) (void)hipSetDevice(dev); }
-    } restore;
-    armour_planner* p = new armour_planner();
-    if (planner_init(p, cfg, nullptr, true) != 0) {
-        std::string keep = g_err;
-        armour_destroy(p);
-        g_err = keep;
-        return nullptr;
-    }
-    return p;
-}
+armour_planner* armour_create(const armour_config* cfg) { return create(cfg, nullptr, false); }
+armour_planner* armour_create_robot(const armour_config* cfg, const armour_robot* robot) { return create(cfg, robot, false); }
+armour_planner* armour_create_armtd(const armour_config* cfg) { return create(cfg, nullptr, true); }
 
 void armour_destroy(armour_planner* p) {
     DeviceScope device_scope(p);
     if (!p) return;
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     for (void* a : p->allocs) (void)hipFree(a);
-    cand_free(p->cd);
-    if (p->mo_pval) (void)hipFree(p->mo_pval);
-    if (p->mo_pidx) (void)hipFree(p->mo_pidx);
+    for (GrowSet* g : {&p->cand, &p->motion, &p->track}) g->release();
     for (hipEvent_t e : p->ep_ev)
         if (e) (void)hipEventDestroy(e);
-    track_free(p);
     for (hipEvent_t e : p->tr_ev)
         if (e) (void)hipEventDestroy(e);
     if (p->h_flags) (void)hipHostFree(p->h_flags);
@@ -1651,52 +1634,42 @@ static int reach_uploaded(armour_planner* p, armour_timing* timing, std::chrono:
 static int plan_uploaded(armour_planner* p, armour_result* results, armour_timing* timing,
                          std::chrono::steady_clock::time_point t0);
 
+// The six batch entries: null checks, the batch state reset, the upload of the batch's kind (uniform,
+// mixed or ARMTD worlds), then the reach phase alone (`plan` false) or the reach phase and the solve.
+enum BatchKind { BATCH_UNIFORM, BATCH_MIXED, BATCH_ARMTD };
+static int run_batch(armour_planner* p, BatchKind kind, bool plan, int W, const void* worlds, armour_result* results,
+                     armour_timing* timing) {
+    DeviceScope device_scope(p);
+    if (!p || (plan && !results)) return fail(ARMOUR_E_ARG, plan ? "null planner / results" : "null planner");
+    if (kind == BATCH_UNIFORM && p->armtd)
+        return fail(ARMOUR_E_ARG, plan ? "an ARMTD planner takes armour_armtd_world (armour_plan_armtd_batch)"
+                                       : "an ARMTD planner takes armour_armtd_world (armour_reach_armtd_batch)");
+    p->reached = p->planned = p->evaluated = p->episode = false;
+    auto t0 = std::chrono::steady_clock::now();
+    const int rc = kind == BATCH_ARMTD ? upload_armtd(p, W, (const armour_armtd_world*)worlds)
+                                       : upload_worlds(p, W, (const armour_world*)worlds, kind == BATCH_MIXED);
+    return rc ? rc : plan ? plan_uploaded(p, results, timing, t0) : reach_uploaded(p, timing, t0);
+}
+
 int armour_reach_batch(armour_planner* p, int W, const armour_world* worlds, armour_timing* timing) {
-    DeviceScope device_scope(p);
-    if (!p) return fail(ARMOUR_E_ARG, "null planner");
-    if (p->armtd) return fail(ARMOUR_E_ARG, "an ARMTD planner takes armour_armtd_world (armour_reach_armtd_batch)");
-    p->reached = p->planned = p->evaluated = p->episode = false;
-    auto t0 = std::chrono::steady_clock::now();
-    const int rc = upload_worlds(p, W, worlds);
-    return rc ? rc : reach_uploaded(p, timing, t0);
+    return run_batch(p, BATCH_UNIFORM, false, W, worlds, nullptr, timing);
 }
-
-int armour_reach_armtd_batch(armour_planner* p, int W, const armour_armtd_world* worlds, armour_timing* timing) {
-    DeviceScope device_scope(p);
-    if (!p) return fail(ARMOUR_E_ARG, "null planner");
-    p->reached = p->planned = p->evaluated = p->episode = false;
-    auto t0 = std::chrono::steady_clock::now();
-    const int rc = upload_armtd(p, W, worlds);
-    return rc ? rc : reach_uploaded(p, timing, t0);
+int armour_plan_batch(armour_planner* p, int W, const armour_world* worlds, armour_result* results, armour_timing* timing) {
+    return run_batch(p, BATCH_UNIFORM, true, W, worlds, results, timing);
 }
-
-int armour_plan_armtd_batch(armour_planner* p, int W, const armour_armtd_world* worlds, armour_result* results,
-                            armour_timing* timing) {
-    DeviceScope device_scope(p);
-    if (!p || !results) return fail(ARMOUR_E_ARG, "null planner / results");
-    p->reached = p->planned = p->evaluated = p->episode = false;
-    auto t0 = std::chrono::steady_clock::now();
-    const int rc = upload_armtd(p, W, worlds);
-    return rc ? rc : plan_uploaded(p, results, timing, t0);
-}
-
 int armour_reach_batch_mixed(armour_planner* p, int W, const armour_world* worlds, armour_timing* timing) {
-    DeviceScope device_scope(p);
-    if (!p) return fail(ARMOUR_E_ARG, "null planner");
-    p->reached = p->planned = p->evaluated = p->episode = false;
-    auto t0 = std::chrono::steady_clock::now();
-    const int rc = upload_worlds_mixed(p, W, worlds);
-    return rc ? rc : reach_uploaded(p, timing, t0);
+    return run_batch(p, BATCH_MIXED, false, W, worlds, nullptr, timing);
 }
-
 int armour_plan_batch_mixed(armour_planner* p, int W, const armour_world* worlds, armour_result* results,
                             armour_timing* timing) {
-    DeviceScope device_scope(p);
-    if (!p || !results) return fail(ARMOUR_E_ARG, "null planner / results");
-    p->reached = p->planned = p->evaluated = p->episode = false;
-    auto t0 = std::chrono::steady_clock::now();
-    const int rc = upload_worlds_mixed(p, W, worlds);
-    return rc ? rc : plan_uploaded(p, results, timing, t0);
+    return run_batch(p, BATCH_MIXED, true, W, worlds, results, timing);
+}
+int armour_reach_armtd_batch(armour_planner* p, int W, const armour_armtd_world* worlds, armour_timing* timing) {
+    return run_batch(p, BATCH_ARMTD, false, W, worlds, nullptr, timing);
+}
+int armour_plan_armtd_batch(armour_planner* p, int W, const armour_armtd_world* worlds, armour_result* results,
+                            armour_timing* timing) {
+    return run_batch(p, BATCH_ARMTD, true, W, worlds, results, timing);
 }
 
 int armour_world_num_obstacles(const armour_planner* p, int w) {
@@ -1706,32 +1679,27 @@ int armour_world_num_obstacles(const armour_planner* p, int w) {
     return p->Ow[w];
 }
 
+// the phase times of the finished batch: reach ev[0] .. ev[1], and the solve ev[1] .. ev[2] when it ran
+static void fill_timing(armour_planner* p, armour_timing* timing, bool solved, std::chrono::steady_clock::time_point t0) {
+    if (!timing) return;
+    float a = 0, b = 0;
+    (void)hipEventElapsedTime(&a, p->ev[0], p->ev[1]);
+    if (solved) (void)hipEventElapsedTime(&b, p->ev[1], p->ev[2]);
+    timing->reach_ms = a;
+    timing->nlp_ms = b;
+    timing->reach_kernel_ms = p->last_kernel_ms;
+    timing->reach_bytes = p->last_bytes;
+    timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
 static int reach_uploaded(armour_planner* p, armour_timing* timing, std::chrono::steady_clock::time_point t0) {
     int rc = 0;
     HIPCK(hipEventRecord(p->ev[0], p->rstream));
     if ((rc = run_reach(p))) return rc;
     HIPCK(hipEventRecord(p->ev[1], p->rstream));
     HIPCK(hipEventSynchronize(p->ev[1]));
-    if (timing) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, p->ev[0], p->ev[1]);
-        timing->reach_ms = ms;
-        timing->nlp_ms = 0;
-        timing->reach_kernel_ms = p->last_kernel_ms;
-        timing->reach_bytes = p->last_bytes;
-        timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
+    fill_timing(p, timing, false, t0);
     return 0;
-}
-
-int armour_plan_batch(armour_planner* p, int W, const armour_world* worlds, armour_result* results, armour_timing* timing) {
-    DeviceScope device_scope(p);
-    if (!p || !results) return fail(ARMOUR_E_ARG, "null planner / results");
-    if (p->armtd) return fail(ARMOUR_E_ARG, "an ARMTD planner takes armour_armtd_world (armour_plan_armtd_batch)");
-    p->reached = p->planned = p->evaluated = p->episode = false;
-    auto t0 = std::chrono::steady_clock::now();
-    const int rc = upload_worlds(p, W, worlds);
-    return rc ? rc : plan_uploaded(p, results, timing, t0);
 }
 
 static int plan_uploaded(armour_planner* p, armour_result* results, armour_timing* timing,
@@ -1769,16 +1737,7 @@ static int plan_uploaded(armour_planner* p, armour_result* results, armour_timin
         }
     }
     p->planned = true;
-    if (timing) {
-        float a = 0, b = 0;
-        (void)hipEventElapsedTime(&a, p->ev[0], p->ev[1]);
-        (void)hipEventElapsedTime(&b, p->ev[1], p->ev[2]);
-        timing->reach_ms = a;
-        timing->nlp_ms = b;
-        timing->reach_kernel_ms = p->last_kernel_ms;
-        timing->reach_bytes = p->last_bytes;
-        timing->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
+    fill_timing(p, timing, true, t0);
     return 0;
 }
 
@@ -1817,23 +1776,13 @@ int armour_eval_constraints(armour_planner* p, int w, const double* x, double* g
 
 // buffers of armour_eval_candidates for N candidates per world
 static int cand_reserve(armour_planner* p, int N) {
-    if (N <= p->cand_cap) return 0;
     CandDev& c = p->cd;
-    HIPCK(hipStreamSynchronize(p->stream));
-    cand_free(c);
-    p->cand_cap = 0;
     const size_t n = (size_t)p->Wmax * N, nT = n * p->T;
-    double* x = nullptr;
-    if (dalloc(&x, n * NF) != hipSuccess || dalloc(&c.ptq, nT) != hipSuccess || dalloc(&c.pcol, nT) != hipSuccess ||
-        dalloc(&c.pbad, nT) != hipSuccess || dalloc(&c.cost, n) != hipSuccess || dalloc(&c.viol, n * 3) != hipSuccess ||
-        dalloc(&c.feas, n) != hipSuccess || dalloc(&c.best, (size_t)p->Wmax) != hipSuccess) {
-        c.x = x;
-        cand_free(c);
-        return fail(ARMOUR_E_HIP, "hipMalloc failed for the candidate buffers (max_worlds x num_candidates x T partials)");
-    }
-    c.x = x;
-    p->cand_cap = N;
-    return 0;
+    return p->cand.reserve(p->stream, N,
+                           {GrowSet::buf(c.x, n * NF), GrowSet::buf(c.ptq, nT), GrowSet::buf(c.pcol, nT), GrowSet::buf(c.pbad, nT),
+                            GrowSet::buf(c.cost, n), GrowSet::buf(c.viol, n * 3), GrowSet::buf(c.feas, n),
+                            GrowSet::buf(c.best, (size_t)p->Wmax)},
+                           "hipMalloc failed for the candidate buffers (max_worlds x num_candidates x T partials)");
 }
 
 int armour_eval_candidates(armour_planner* p, int N, const double* x, double* cost, double* violation, int* feasible,
@@ -1841,7 +1790,7 @@ int armour_eval_candidates(armour_planner* p, int N, const double* x, double* co
     DeviceScope device_scope(p);
     if (!p || !x) return fail(ARMOUR_E_ARG, "null planner / x");
     if (p->armtd) return fail(ARMOUR_E_ARG, "candidate evaluation is not available on an ARMTD planner");
-    if (p->eval_f32) return fail(ARMOUR_E_ARG, "candidate evaluation is not available with the fp32 study (ARMOUR_EVAL_F32)");
+    if (p->set.eval_f32) return fail(ARMOUR_E_ARG, "candidate evaluation is not available with the fp32 study (ARMOUR_EVAL_F32)");
     if (N < 1) return fail(ARMOUR_E_ARG, "num_candidates must be at least 1");
     if (!p->reached) return fail(ARMOUR_E_STATE, "no batch: call a reach or plan entry first");
     const int W = p->W;
@@ -1884,17 +1833,9 @@ static int motion_reserve(armour_planner* p, int S) {
     if (!p->mo_traj && ((rc = p->alloc(&p->mo_traj, (size_t)p->Wmax * TRAJ_DOUBLES)) ||
                         (rc = p->alloc(&p->mo_clear, (size_t)p->Wmax)) || (rc = p->alloc(&p->mo_where, 3 * (size_t)p->Wmax))))
         return rc;
-    if (S <= p->motion_cap) return 0;
-    HIPCK(hipStreamSynchronize(p->stream));
-    if (p->mo_pval) (void)hipFree(p->mo_pval);
-    if (p->mo_pidx) (void)hipFree(p->mo_pidx);
-    p->mo_pval = nullptr;
-    p->mo_pidx = nullptr;
-    p->motion_cap = 0;
-    if (dalloc(&p->mo_pval, (size_t)p->Wmax * S) != hipSuccess || dalloc(&p->mo_pidx, (size_t)p->Wmax * S) != hipSuccess)
-        return fail(ARMOUR_E_HIP, "hipMalloc failed for the execution check's buffers (max_worlds x samples)");
-    p->motion_cap = S;
-    return 0;
+    const size_t n = (size_t)p->Wmax * S;
+    return p->motion.reserve(p->stream, S, {GrowSet::buf(p->mo_pval, n), GrowSet::buf(p->mo_pidx, n)},
+                             "hipMalloc failed for the execution check's buffers (max_worlds x samples)");
 }
 
 // the execution check of the resident batch over S samples of `traj` (device, [W][4][7]): per-world
@@ -1922,7 +1863,7 @@ int armour_check_motion(armour_planner* p, const double* traj, double t0, double
     DeviceScope device_scope(p);
     if (!p || !traj) return fail(ARMOUR_E_ARG, "null planner / traj");
     if (p->armtd) return fail(ARMOUR_E_ARG, "the execution check is not available on an ARMTD planner");
-    if (p->eval_f32) return fail(ARMOUR_E_ARG, "the execution check is not available with the fp32 study (ARMOUR_EVAL_F32)");
+    if (p->set.eval_f32) return fail(ARMOUR_E_ARG, "the execution check is not available with the fp32 study (ARMOUR_EVAL_F32)");
     if (samples < 1 || samples > 65535) return fail(ARMOUR_E_ARG, "samples must lie in 1 .. 65535");
     if (!(t0 >= 0.0 && t1 <= 1.0 && t0 <= t1)) return fail(ARMOUR_E_ARG, "the window must satisfy 0 <= t0 <= t1 <= 1");
     if (!p->reached) return fail(ARMOUR_E_STATE, "no batch: call a reach or plan entry first");
@@ -1949,7 +1890,7 @@ int armour_track(armour_planner* p, int N, const double* traj, int S, const doub
     DeviceScope device_scope(p);
     if (!p || !traj || !out) return fail(ARMOUR_E_ARG, "null planner / traj / out");
     if (p->armtd) return fail(ARMOUR_E_ARG, "tracking rollouts are not available on an ARMTD planner");
-    if (p->eval_f32) return fail(ARMOUR_E_ARG, "tracking rollouts are not available with the fp32 study (ARMOUR_EVAL_F32)");
+    if (p->set.eval_f32) return fail(ARMOUR_E_ARG, "tracking rollouts are not available with the fp32 study (ARMOUR_EVAL_F32)");
     if (N < 1 || S < 1) return fail(ARMOUR_E_ARG, "num_traj and num_samples must be at least 1");
     if ((long)N * S > ARMOUR_TRACK_MAX_ROLLOUTS) return fail(ARMOUR_E_ARG, "num_traj x num_samples exceeds ARMOUR_TRACK_MAX_ROLLOUTS");
     if (steps < 1 || steps > ARMOUR_TRACK_MAX_STEPS) return fail(ARMOUR_E_ARG, "steps must lie in 1 .. ARMOUR_TRACK_MAX_STEPS");
@@ -2029,7 +1970,7 @@ int armour_episode_begin(armour_planner* p, int W, const armour_world* worlds, c
     DeviceScope device_scope(p);
     if (!p || !worlds || !goals || !cfg) return fail(ARMOUR_E_ARG, "null argument");
     if (p->armtd) return fail(ARMOUR_E_ARG, "episodes are not available on an ARMTD planner");
-    if (p->eval_f32) return fail(ARMOUR_E_ARG, "episodes are not available with the fp32 study (ARMOUR_EVAL_F32)");
+    if (p->set.eval_f32) return fail(ARMOUR_E_ARG, "episodes are not available with the fp32 study (ARMOUR_EVAL_F32)");
     if (!(cfg->lookahead > 0.0) || !std::isfinite(cfg->lookahead) || !(cfg->goal_radius >= 0.0) ||
         !std::isfinite(cfg->goal_radius) || cfg->check_samples < 2 || cfg->check_samples > 65535)
         return fail(ARMOUR_E_ARG, "episode config: lookahead > 0, goal_radius >= 0, 2 <= check_samples <= 65535");
@@ -2040,7 +1981,7 @@ int armour_episode_begin(armour_planner* p, int W, const armour_world* worlds, c
     // the worlds' q_des is ignored: the waypoints are written on the device
     std::vector<armour_world> ws(worlds, worlds + W);
     for (armour_world& w : ws) std::memcpy(w.q_des, w.q0, sizeof(w.q_des));
-    if ((rc = upload_worlds_mixed(p, W, ws.data()))) return rc;
+    if ((rc = upload_worlds(p, W, ws.data(), true))) return rc;
     if ((rc = motion_reserve(p, cfg->check_samples))) return rc;
     EpisodeDev& e = p->ep;
     if (!e.st) {
@@ -2238,7 +2179,7 @@ int armour_get_plane_cache_stats(armour_planner* p, long long* out, int n) {
     if (!p) return fail(ARMOUR_E_ARG, "null planner");
     if (!p->reached) return fail(ARMOUR_E_STATE, "no reach set");
     NlpDev& d = p->d;
-    if (!d.pcache || p->eval_f32 || d.O == 0) return fail(ARMOUR_E_STATE, "plane cache off (ARMOUR_PLANE_CACHE=0, float study or no obstacles)");
+    if (!d.pcache || p->set.eval_f32 || d.O == 0) return fail(ARMOUR_E_STATE, "plane cache off (ARMOUR_PLANE_CACHE=0, float study or no obstacles)");
     ensure_plane_cache(p);
     const size_t blocks = (size_t)p->W * p->T, NP = (size_t)p->NJ * d.O;
     std::vector<unsigned> off(blocks * NP);

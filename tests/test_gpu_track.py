@@ -268,14 +268,17 @@ def test_refusals():
 def test_tracking_leaves_the_batch_and_the_next_plan_unchanged():
     world = A.make_world(3, 3)
     tb, traj, scale, err0 = TC.case_inputs("kinova", (3, 5))
+    # first use, a call that grows the buffers, and the first call again in the larger buffers
+    calls = [(traj, scale, err0, 0.0, 0.5, TC.STEPS), (np.repeat(traj, 40, axis=0), None, None, 0.5, 1.0, 5),
+             (traj, scale, err0, 0.0, 0.5, TC.STEPS)]
+    tracked = []
 
     def plans(with_track):
         P = A.Planner(T=10, max_obstacles=3, max_worlds=1)
         r1, _ = P.plan([world])
         g1 = P.constraints(0)
         if with_track:
-            P.track(traj, scale, err0, 0.0, 0.5, TC.STEPS)
-            P.track(np.repeat(traj, 40, axis=0), None, None, 0.5, 1.0, 5)   # (grows the buffers)
+            tracked.extend(P.track(*c) for c in calls)
         g2 = P.constraints(0)
         c2 = P.link_centers(0)
         r2, _ = P.plan([world])
@@ -289,6 +292,15 @@ def test_tracking_leaves_the_batch_and_the_next_plan_unchanged():
         assert np.array_equal(x, y)
     for ra, rb in ((a[0], b[0]), (a[4], b[4])):
         assert np.array_equal(ra[0]["k_opt"], rb[0]["k_opt"]) and ra[0]["iterations"] == rb[0]["iterations"]
+    # every tracking output, before and after the grow, is bitwise a fresh planner's that makes only that call
+    for c, out in zip(calls[:2], tracked[:2]):
+        Q = A.Planner(T=10, max_obstacles=3, max_worlds=1)
+        ref = Q.track(*c)
+        Q.close()
+        for k in TC.FIELDS + ("status",):
+            assert out[k].shape == ref[k].shape and out[k].tobytes() == ref[k].tobytes(), k
+    for k in TC.FIELDS + ("status",):
+        assert tracked[2][k].tobytes() == tracked[0][k].tobytes(), k
 
 
 def test_tracking_needs_no_batch():

@@ -2,7 +2,7 @@
 ctypes, no device: values that are not finite or angles beyond ARMOUR_MAX_ABS_ANGLE are refused with
 ARMOUR_E_ARG and a message that names the field; everything inside the domain is accepted, every edge
 case of tests/domain_edges.py included. The planning entries run this check before they copy or
-launch anything (planner.hip upload_worlds*), and armour_main reports a refused world as a failed
+launch anything (planner.hip upload_worlds, upload_armtd), and armour_main reports a refused world as a failed
 replan."""
 import os
 import re
