@@ -79,7 +79,8 @@ class EpisodeState(ctypes.Structure):
 
 
 T_PLAN = 0.5  # ARMOUR_T_PLAN
-EPISODE_STATUS = ("running", "goal reached", "collided", "no fail-safe", "left the input domain")
+EPISODE_STATUS = ("running", "goal reached", "collided", "no fail-safe", "left the input domain",
+                  "input over the limit", "ultimate bound exceeded", "joint limit exceeded", "rollout not finite")
 
 
 class TrackOutput(ctypes.Structure):
@@ -90,6 +91,31 @@ class TrackOutput(ctypes.Structure):
 
 
 TRACK_MAX_STEPS = 100000  # ARMOUR_TRACK_MAX_STEPS
+
+
+class TrackMotionOutput(ctypes.Structure):
+    """armour_track_motion_output (include/armour_hip.h): the rollouts' outputs, the true arm's clearance
+    per rollout and per world, the flags, and the device time of the check"""
+    _fields_ = [("track", TrackOutput), ("clearance", _dp), ("where", ctypes.POINTER(ctypes.c_int)),
+                ("flags", ctypes.POINTER(ctypes.c_int)), ("world_clearance", _dp),
+                ("world_where", ctypes.POINTER(ctypes.c_int)), ("check_ms", ctypes.c_double)]
+
+
+class EpisodeTrackConfig(ctypes.Structure):
+    """armour_episode_track_config (include/armour_hip.h)"""
+    _fields_ = [("num_samples", ctypes.c_int), ("scale", _dp), ("err0", _dp), ("steps", ctypes.c_int),
+                ("stop_on_input", ctypes.c_int), ("stop_on_bound", ctypes.c_int), ("stop_on_limit", ctypes.c_int)]
+
+
+class EpisodeTracked(ctypes.Structure):
+    """armour_episode_tracked (include/armour_hip.h): a world's record of its true arms"""
+    _fields_ = [("clearance", ctypes.c_double), ("clearance_at", ctypes.c_int * 4), ("max_pos_err", ctypes.c_double * NF),
+                ("max_vel_err", ctypes.c_double * NF), ("max_torque", ctypes.c_double * NF), ("max_V", ctypes.c_double),
+                ("max_robust", ctypes.c_double), ("flags", ctypes.c_int), ("flag_step", ctypes.c_int * 5)]
+
+
+# ARMOUR_TRACK_COLLISION .. ARMOUR_TRACK_NOT_FINITE: the bits of armour_track_motion's flags
+TRACK_COLLISION, TRACK_INPUT, TRACK_BOUND, TRACK_LIMIT, TRACK_NOT_FINITE = 1, 2, 4, 8, 16
 
 
 class PlanOutput(ctypes.Structure):
@@ -144,7 +170,12 @@ def lib():
                                                     _dp]),
                            ("armour_episode_get", [ctypes.c_void_p, ctypes.POINTER(EpisodeState)]),
                            ("armour_track", [ctypes.c_void_p, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp, ctypes.c_double,
-                                             ctypes.c_double, ctypes.c_int, ctypes.POINTER(TrackOutput)])):
+                                             ctypes.c_double, ctypes.c_int, ctypes.POINTER(TrackOutput)]),
+                           ("armour_track_motion", [ctypes.c_void_p, _dp, ctypes.c_int, _dp, _dp, ctypes.c_double,
+                                                    ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.POINTER(TrackMotionOutput)]),
+                           ("armour_episode_track", [ctypes.c_void_p, ctypes.POINTER(EpisodeTrackConfig)]),
+                           ("armour_episode_get_tracked", [ctypes.c_void_p, ctypes.POINTER(EpisodeTracked), _dp, ip, _dp])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = args
         for name, args in (("armour_check_world", [ctypes.POINTER(World), ctypes.c_int]),
@@ -184,7 +215,7 @@ ABI_SYMBOLS = ["armour_copy_bandwidth", "armour_create", "armour_create_robot", 
                "armour_plan_batch_mixed", "armour_reach_batch_mixed", "armour_world_num_obstacles",
                "armour_eval_candidates", "armour_sq_selfcheck", "armour_check_world", "armour_check_armtd_world",
                "armour_check_motion", "armour_episode_begin", "armour_episode_step", "armour_episode_get",
-               "armour_track"]
+               "armour_track", "armour_track_motion", "armour_episode_track", "armour_episode_get_tracked"]
 
 
 def default_batch(T: int, device: int = 0, waves: int = 2) -> int:
@@ -474,9 +505,19 @@ class Planner:
         Needs no batch. Returns a dict: max_pos_err, max_vel_err, max_torque [N, S, 7], max_V, max_robust
         [N, S], end_state [N, S, 2, 7], status [N, S] (1: the rollout stopped being finite), track_ms, and
         the ultimate bounds qe, qde of the planner's tables the errors are read against."""
+        traj, scale, err0, N, S = self._track_inputs("track", traj, scale, err0)
+        out, o = self._track_outputs(N, S)
+        _check(lib().armour_track(self.h, N, _ptr(traj), S, _ptr(scale), _ptr(err0), float(t0), float(t1), int(steps),
+                                  ctypes.byref(o)))
+        out["track_ms"] = float(o.track_ms)
+        out["qe"], out["qde"] = self._ultimate_bound()
+        return out
+
+    def _track_inputs(self, name, traj, scale, err0, N=None):
+        """the shape checks of the tracking entries: (traj, scale, err0, N, S), contiguous float64"""
         traj = np.ascontiguousarray(np.asarray(traj, dtype=np.float64))
-        if traj.ndim != 3 or traj.shape[1:] != (4, NF) or traj.shape[0] < 1:
-            raise ValueError(f"track: traj must have shape [N, 4, {NF}], got {traj.shape}")
+        if traj.ndim != 3 or traj.shape[1:] != (4, NF) or traj.shape[0] < 1 or (N is not None and traj.shape[0] != N):
+            raise ValueError(f"{name}: traj must have shape [{'N' if N is None else N}, 4, {NF}], got {traj.shape}")
         N = traj.shape[0]
         S = None
         if scale is not None:
@@ -484,7 +525,7 @@ class Planner:
             if scale.ndim == 3:
                 scale = np.broadcast_to(scale, (N,) + scale.shape)
             if scale.ndim != 4 or scale.shape[0] != N or scale.shape[1] < 1 or scale.shape[2:] != (2, self.NJ):
-                raise ValueError(f"track: scale must have shape [N, S, 2, {self.NJ}] or [S, 2, {self.NJ}] (N = {N}), "
+                raise ValueError(f"{name}: scale must have shape [N, S, 2, {self.NJ}] or [S, 2, {self.NJ}] (N = {N}), "
                                  f"got {scale.shape}")
             scale = np.ascontiguousarray(scale)
             S = scale.shape[1]
@@ -492,25 +533,49 @@ class Planner:
             err0 = np.ascontiguousarray(np.asarray(err0, dtype=np.float64))
             if err0.ndim != 4 or err0.shape[0] != N or err0.shape[1] < 1 or err0.shape[2:] != (2, NF) or \
                     (S is not None and err0.shape[1] != S):
-                raise ValueError(f"track: err0 must have shape [N, S, 2, {NF}] (N = {N}, S = {S}), got {err0.shape}")
+                raise ValueError(f"{name}: err0 must have shape [N, S, 2, {NF}] (N = {N}, S = {S}), got {err0.shape}")
             S = err0.shape[1]
-        S = 1 if S is None else S
+        return traj, scale, err0, N, 1 if S is None else S
+
+    @staticmethod
+    def _track_outputs(N, S):
+        """(dict of the output arrays of armour_track_output, the structure that points at them)"""
         out = dict(max_pos_err=np.zeros((N, S, NF)), max_vel_err=np.zeros((N, S, NF)), max_torque=np.zeros((N, S, NF)),
                    max_V=np.zeros((N, S)), max_robust=np.zeros((N, S)), end_state=np.zeros((N, S, 2, NF)))
-        status = np.zeros((N, S), dtype=np.int32)
+        out["status"] = np.zeros((N, S), dtype=np.int32)
         o = TrackOutput(*[_ptr(out[k]) for k in ("max_pos_err", "max_vel_err", "max_torque", "max_V", "max_robust",
-                                                  "end_state")], status.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), 0.0)
-        _check(lib().armour_track(self.h, N, _ptr(traj), S, _ptr(scale), _ptr(err0), float(t0), float(t1), int(steps),
-                                  ctypes.byref(o)))
-        out["status"] = status
-        out["track_ms"] = float(o.track_ms)
-        r = getattr(self, "_robot", None)   # the tables' ultimate bound, as the library derives it
+                                                  "end_state")], out["status"].ctypes.data_as(ctypes.POINTER(ctypes.c_int)), 0.0)
+        return out, o
+
+    def _ultimate_bound(self):
+        """(qe, qde) of the planner's tables, as the library derives them"""
+        r = getattr(self, "_robot", None)
         if r is None:
             from .robot_tables import ArmourRobot
             r = ArmourRobot()
             _check(lib().armour_robot_builtin(0, ctypes.byref(r)))
         eps = float(np.sqrt(2 * r.V_m / r.M_min))
-        out["qe"], out["qde"] = eps / r.K, 2 * eps
+        return eps / r.K, 2 * eps
+
+    def track_motion(self, traj, scale=None, err0=None, t0=0.0, t1=0.5, steps=250, check_samples=11):
+        """armour_track_motion: Planner.track for one trajectory per world of the last batch (traj [W, 4, 7],
+        scale [W, S, 2, num_joints] / [S, 2, num_joints] / None, err0 [W, S, 2, 7] / None), with the true arm's
+        states at `check_samples` check points (steps must be a multiple of check_samples - 1) tested
+        against the world's own obstacles. Returns track's dict plus clearance [W, S], where [W, S, 3] (check
+        point, link, obstacle), flags [W, S] (TRACK_COLLISION, TRACK_INPUT, TRACK_BOUND, TRACK_LIMIT,
+        TRACK_NOT_FINITE), world_clearance [W], world_where [W, 4] (sample, check point, link, obstacle)
+        and check_ms; +inf and -1 without obstacles."""
+        traj, scale, err0, W, S = self._track_inputs("track_motion", traj, scale, err0, N=self._W)
+        out, o = self._track_outputs(W, S)
+        ip = ctypes.POINTER(ctypes.c_int)
+        out.update(clearance=np.zeros((W, S)), where=np.zeros((W, S, 3), dtype=np.int32), flags=np.zeros((W, S), dtype=np.int32),
+                   world_clearance=np.zeros(W), world_where=np.zeros((W, 4), dtype=np.int32))
+        m = TrackMotionOutput(o, _ptr(out["clearance"]), out["where"].ctypes.data_as(ip), out["flags"].ctypes.data_as(ip),
+                              _ptr(out["world_clearance"]), out["world_where"].ctypes.data_as(ip), 0.0)
+        _check(lib().armour_track_motion(self.h, _ptr(traj), S, _ptr(scale), _ptr(err0), float(t0), float(t1), int(steps),
+                                         int(check_samples), ctypes.byref(m)))
+        out["track_ms"], out["check_ms"] = float(m.track.track_ms), float(m.check_ms)
+        out["qe"], out["qde"] = self._ultimate_bound()
         return out
 
     def episode_begin(self, worlds, goals, lookahead=0.1, goal_radius=np.pi / 30, check_samples=11):
@@ -543,6 +608,62 @@ class Planner:
         t = self._span(tm.as_dict())
         t["check_ms"], t["advance_ms"] = float(ems[0]), float(ems[1])
         return n, self._results(res)[:self._W], t
+
+    def episode_track(self, scale=None, err0=None, num_samples=None, steps=250, stop_on_input=True, stop_on_bound=True,
+                      stop_on_limit=False):
+        """armour_episode_track, after episode_begin and before the first step: from then on every step also
+        rolls S true arms per world along what the world executes. scale [W, S, 2, num_joints] /
+        [S, 2, num_joints] / None (nominal), err0 [W, S, 2, 7] / None (the first start's offset from the
+        episode's start state); S comes from them, or from num_samples when both are None. steps must be a
+        multiple of the episode's check_samples - 1. The stops default to the reference's (input and
+        ultimate bound, not the joint limits)."""
+        W = self._W
+        S = None
+        if scale is not None:
+            scale = np.asarray(scale, dtype=np.float64)
+            if scale.ndim == 3:
+                scale = np.broadcast_to(scale, (W,) + scale.shape)
+            if scale.ndim != 4 or scale.shape[0] != W or scale.shape[1] < 1 or scale.shape[2:] != (2, self.NJ):
+                raise ValueError(f"episode_track: scale must have shape [W, S, 2, {self.NJ}] or [S, 2, {self.NJ}] (W = {W}), "
+                                 f"got {scale.shape}")
+            scale = np.ascontiguousarray(scale)
+            S = scale.shape[1]
+        if err0 is not None:
+            err0 = np.ascontiguousarray(np.asarray(err0, dtype=np.float64))
+            if err0.ndim != 4 or err0.shape[0] != W or err0.shape[1] < 1 or err0.shape[2:] != (2, NF) or \
+                    (S is not None and err0.shape[1] != S):
+                raise ValueError(f"episode_track: err0 must have shape [W, S, 2, {NF}] (W = {W}, S = {S}), got {err0.shape}")
+            S = err0.shape[1]
+        if S is None:
+            S = 1 if num_samples is None else int(num_samples)
+        elif num_samples is not None and int(num_samples) != S:
+            raise ValueError(f"episode_track: num_samples = {num_samples} but the arrays carry {S} samples")
+        cfg = EpisodeTrackConfig(S, _ptr(scale), _ptr(err0), int(steps), int(bool(stop_on_input)), int(bool(stop_on_bound)),
+                                 int(bool(stop_on_limit)))
+        _check(lib().armour_episode_track(self.h, ctypes.byref(cfg)))
+        self._track_S = S
+
+    def episode_tracked(self):
+        """armour_episode_get_tracked: dict of arrays over the worlds: clearance [W], clearance_at [W, 4] (step,
+        sample, link, obstacle), max_pos_err, max_vel_err, max_torque [W, 7], max_V, max_robust [W], flags
+        [W], flag_step [W, 5]; and true_state [W, S, 2, 7], last_flags [W, S], rollout_ms, check_ms"""
+        W, S = self._W, getattr(self, "_track_S", 1)
+        rec = (EpisodeTracked * max(W, 1))()
+        true = np.zeros((W, S, 2, NF))
+        flags = np.zeros((W, S), dtype=np.int32)
+        ms = np.zeros(2)
+        _check(lib().armour_episode_get_tracked(self.h, rec, _ptr(true), flags.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                _ptr(ms)))
+        rec = rec[:W]
+        out = {k: np.array([getattr(r, k)[:] for r in rec], dtype=np.float64).reshape(W, NF)
+               for k in ("max_pos_err", "max_vel_err", "max_torque")}
+        for k in ("clearance", "max_V", "max_robust"):
+            out[k] = np.array([getattr(r, k) for r in rec], dtype=np.float64)
+        out["clearance_at"] = np.array([r.clearance_at[:] for r in rec], dtype=np.int64).reshape(W, 4)
+        out["flags"] = np.array([r.flags for r in rec], dtype=np.int64)
+        out["flag_step"] = np.array([r.flag_step[:] for r in rec], dtype=np.int64).reshape(W, 5)
+        out.update(true_state=true, last_flags=flags, rollout_ms=float(ms[0]), check_ms=float(ms[1]))
+        return out
 
     def episode_states(self):
         """armour_episode_get: dict of arrays over the worlds (q, qd, qdd, q_des [W, 7], status, mode, steps,
@@ -648,18 +769,25 @@ class Planner:
         return r
 
 
-def run_episodes(planner, worlds, goals, max_steps, **config):
+def run_episodes(planner, worlds, goals, max_steps, track=None, **config):
     """Drive `worlds` toward `goals` [W, 7] with receding-horizon episodes on `planner` (episode_begin,
     then episode_step until no world runs or max_steps steps were taken; config: lookahead,
-    goal_radius, check_samples). Returns dict(status, steps, clearance: [W] each)."""
+    goal_radius, check_samples). track (optional): the arguments of Planner.episode_track as a dict; the
+    true arms are then rolled along every executed segment. Returns dict(status, steps, clearance: [W]
+    each), and with track also tracked: the records (Planner.episode_tracked)."""
     st = planner.episode_begin(worlds, goals, **config)
+    if track is not None:
+        planner.episode_track(**track)
     running = int(np.sum(st["status"] == 0))
     for _ in range(int(max_steps)):
         if running == 0:
             break
         running, _, _ = planner.episode_step()
     st = planner.episode_states()
-    return dict(status=st["status"], steps=st["steps"], clearance=st["clearance"])
+    out = dict(status=st["status"], steps=st["steps"], clearance=st["clearance"])
+    if track is not None:
+        out["tracked"] = planner.episode_tracked()
+    return out
 
 
 class ArmtdPlanner(Planner):
@@ -699,4 +827,4 @@ class ArmtdPlanner(Planner):
         return lib().armour_reach_armtd_batch(*a)
 
 
-__all__ = ["ArmtdPlanner", "Planner", "ArmourError", "ARMOUR_E_CAPACITY", "ARMOUR_E_INTERNAL", "copy_bandwidth", "default_batch", "make_world", "example_world", "csv_world", "straight_line_waypoint", "KINOVA", "LIB_PATH", "ABI_SYMBOLS", "candidates_array", "check_world", "check_armtd_world", "run_episodes", "EpisodeConfig", "EpisodeState", "T_PLAN", "EPISODE_STATUS"]
+__all__ = ["ArmtdPlanner", "Planner", "ArmourError", "ARMOUR_E_CAPACITY", "ARMOUR_E_INTERNAL", "copy_bandwidth", "default_batch", "make_world", "example_world", "csv_world", "straight_line_waypoint", "KINOVA", "LIB_PATH", "ABI_SYMBOLS", "candidates_array", "check_world", "check_armtd_world", "run_episodes", "EpisodeConfig", "EpisodeState", "T_PLAN", "EPISODE_STATUS", "TrackMotionOutput", "EpisodeTrackConfig", "EpisodeTracked"]

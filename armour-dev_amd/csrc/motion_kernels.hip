@@ -16,7 +16,13 @@
 //                       pairs, the minimum is taken per wave (wave.h), and thread 0 stores the block's
 //                       (value, pair) with one plain store. No atomics.
 // motion_finish_kernel  one wave per world: first minimum over the samples, in (sample, link, obstacle) order.
+// motion_state_check_kernel   the same block body on recorded states of the true arm instead of a curve
+//                       (armour_track_motion): grid (check point, sample, world).
+// motion_state_finish_kernel  one wave per world: per rollout the first minimum over the check points and
+//                       the flags, then the first minimum over the world's samples.
 // episode_*_kernel      one thread per world: the bookkeeping of armour_episode_begin / _step.
+// episode_track_*_kernel  one thread per world: a tracked episode's trajectory and window (choose) and its
+//                       record and stops (fold), armour_episode_track.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <climits>
@@ -59,7 +65,8 @@ AD void mat3_mul(const double* A, const double* B, double* C) {  // row-major C 
 }
 
 // separation of the link box (centre lc, generators lg[3][3]) from the obstacle zonotope ob[12]
-__device__ inline double motion_separation(const double* ob, const double* link) {
+// (inlined into each of the two check kernels, as it was into the one)
+__device__ __forceinline__ double motion_separation(const double* ob, const double* link) {
     double g[6][3], diff[3];
     for (int e = 0; e < 3; e++) diff[e] = link[e] - ob[e];
     for (int j = 0; j < 3; j++)
@@ -91,8 +98,32 @@ __device__ inline double motion_separation(const double* ob, const double* link)
 // (value, index) ordered by value, then by index: the first minimiser
 __device__ inline bool motion_before(double v, int i, double bv, int bi) { return v < bv || (v == bv && i < bi); }
 
-__global__ __launch_bounds__(MOTION_THREADS) void motion_check_kernel(MotionArgs a) {
-    const int s = blockIdx.x, w = blockIdx.y, tid = threadIdx.x;
+// Where the configuration of a block comes from. MotionFromCurve: sample s of the world's Bezier curve
+// over its window (armour_check_motion, the episodes). MotionFromStates: check point c of rollout
+// (w, s) as the recording track kernels stored it (armour_track_motion); nothing is skipped.
+struct MotionFromCurve {
+    const double* tr;  // [4][NF] of this world
+    double t0, t1;
+    int s, S;
+    __device__ bool empty() const { return !(t0 <= t1); }
+    __device__ double angle(const RobotParams& rp, int j) const {
+        double q, qd, qdd;
+        bezier_joint(tr[j], tr[NF + j], tr[2 * NF + j], tr[3 * NF + j] * rp.k_range[j], motion_time(t0, t1, s, S), q, qd, qdd);
+        return q;
+    }
+};
+struct MotionFromStates {
+    const double* state;  // [2][NF] of this check point and rollout
+    bool skipped;         // a tracked episode's world that executes nothing this step
+    __device__ bool empty() const { return skipped; }
+    __device__ double angle(const RobotParams&, int j) const { return state[j]; }
+};
+
+// one block: the smallest separation of world w's obstacles from the arm at src's configuration, and
+// its first (link, obstacle) pair, stored at `out`
+template <class Src>
+__device__ __forceinline__ void motion_check_body(const MotionArgs& a, int w, long out, const Src& src) {
+    const int tid = threadIdx.x;
     __shared__ double s_obs[MAX_OBS * 12];
     __shared__ double s_cs[NF][2];
     __shared__ double s_link[MAX_J][12];
@@ -102,14 +133,8 @@ __global__ __launch_bounds__(MOTION_THREADS) void motion_check_kernel(MotionArgs
     const int NJ = rp.num_joints;
     int O = a.Ow ? a.Ow[w] : a.O;
     O = O < 0 ? 0 : (O > MAX_OBS ? MAX_OBS : O);
-    double t0 = a.t0, t1 = a.t1;
-    if (a.win) {
-        t0 = a.win[2 * w];
-        t1 = a.win[2 * w + 1];
-    }
-    const long out = (long)w * a.S + s;
     // (block-uniform) a world without obstacles, or one that executes nothing
-    if (O == 0 || !(t0 <= t1)) {
+    if (O == 0 || src.empty()) {
         if (tid == 0) {
             a.pval[out] = INFINITY;
             a.pidx[out] = -1;
@@ -119,10 +144,7 @@ __global__ __launch_bounds__(MOTION_THREADS) void motion_check_kernel(MotionArgs
     const double* ob = a.obs + (long)w * a.O * 12;
     for (int i = tid; i < O * 12; i += MOTION_THREADS) s_obs[i] = ob[i];
     if (tid < NF) {
-        const double* tr = a.traj + (long)w * TRAJ_DOUBLES;
-        double q, qd, qdd;
-        bezier_joint(tr[tid], tr[NF + tid], tr[2 * NF + tid], tr[3 * NF + tid] * rp.k_range[tid], motion_time(t0, t1, s, a.S), q,
-                     qd, qdd);
+        const double q = src.angle(rp, tid);
         s_cs[tid][0] = cos(q);
         s_cs[tid][1] = sin(q);
     }
@@ -191,6 +213,108 @@ __global__ __launch_bounds__(MOTION_THREADS) void motion_check_kernel(MotionArgs
             }
         a.pval[out] = best;
         a.pidx[out] = bidx == INT_MAX ? -1 : bidx;
+    }
+}
+
+__global__ __launch_bounds__(MOTION_THREADS) void motion_check_kernel(MotionArgs a) {
+    const int s = blockIdx.x, w = blockIdx.y;
+    double t0 = a.t0, t1 = a.t1;
+    if (a.win) {
+        t0 = a.win[2 * w];
+        t1 = a.win[2 * w + 1];
+    }
+    motion_check_body(a, w, (long)w * a.S + s, MotionFromCurve{a.traj + (long)w * TRAJ_DOUBLES, t0, t1, s, a.S});
+}
+
+// The true-arm check of armour_track_motion: grid (check point, sample, world) over the recorded states
+// rec [C][W * S][2][NF]; pval / pidx are [W][S][C]. a.traj is not read; a.win (a tracked episode's step;
+// null otherwise) only says which worlds are skipped: those with an empty window.
+__device__ inline bool motion_world_skipped(const MotionArgs& a, int w) { return a.win && !(a.win[2 * w] <= a.win[2 * w + 1]); }
+__global__ __launch_bounds__(MOTION_THREADS) void motion_state_check_kernel(MotionArgs a, const double* rec, int C) {
+    const int c = blockIdx.x, s = blockIdx.y, w = blockIdx.z;
+    const long r = (long)w * a.S + s, NR = (long)a.W * a.S;
+    motion_check_body(a, w, r * C + c, MotionFromStates{rec + ((long)c * NR + r) * 2 * NF, motion_world_skipped(a, w)});
+}
+
+// What the true-arm check reports per rollout and per world (armour_track_motion), from the per-check-point
+// minima, the recorded states and the rollouts' outputs. One wave per world, its samples in turn: the
+// first minimum over the check points (lanes stride over them; wave reduction), the limit test at the
+// check points, the flags, and the first minimum over the samples (a strict comparison: ties to the
+// lowest sample). Trip counts depend on S and C only.
+struct TrackedFinish {
+    int C;
+    const double* rec;      // [C][W * S][2][NF]
+    const double* out;      // the rollouts' outputs by field (track_store)
+    const int* status;      // [W * S]
+    double* clearance;      // [W][S]
+    int* where;             // [W][S][3] check point, link, obstacle
+    int* flags;             // [W][S]
+    double* wclear;         // [W]
+    int* wwhere;            // [W][4] sample, check point, link, obstacle
+};
+__global__ __launch_bounds__(64) void motion_state_finish_kernel(MotionArgs a, TrackedFinish f) {
+    const int w = blockIdx.x, lane = threadIdx.x;
+    if (motion_world_skipped(a, w)) return;  // (block-uniform) its outputs stay as they were
+    const RobotParams& rp = *a.rp;
+    const long NR = (long)a.W * a.S;
+    int O = a.Ow ? a.Ow[w] : a.O;
+    O = O < 0 ? 0 : (O > MAX_OBS ? MAX_OBS : O);
+    double wbest = INFINITY;
+    int ws = -1, wc = -1, widx = -1;
+    for (int s = 0; s < a.S; s++) {
+        const long r = (long)w * a.S + s;
+        double best = INFINITY;
+        int bc = INT_MAX, out_of_limits = 0;
+        for (int c = lane; c < f.C; c += 64) {
+            const double v = a.pval[r * f.C + c];
+            if (a.pidx[r * f.C + c] >= 0 && motion_before(v, c, best, bc)) {
+                best = v;
+                bc = c;
+            }
+            const double* st = f.rec + ((long)c * NR + r) * 2 * NF;
+            for (int j = 0; j < NF; j++)
+                if (st[j] < rp.state_lb[j] || st[j] > rp.state_ub[j] || fabs(st[NF + j]) > rp.speed_limits[j]) out_of_limits = 1;
+        }
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            const double ov = xor_f64(best, m);
+            const int oc = xor_i32(bc, m);
+            if (motion_before(ov, oc, best, bc)) {
+                best = ov;
+                bc = oc;
+            }
+            out_of_limits |= xor_i32(out_of_limits, m);
+        }
+        const bool none = bc == INT_MAX || O <= 0;
+        const int idx = none ? -1 : a.pidx[r * f.C + bc];
+        int fl = 0;
+        if (!none && best <= 0) fl |= ARMOUR_TRACK_COLLISION;
+        for (int j = 0; j < NF; j++) {
+            if (f.out[(2 * NR + r) * NF + j] > rp.torque_limits[j]) fl |= ARMOUR_TRACK_INPUT;
+            if (f.out[r * NF + j] > rp.qe || f.out[(NR + r) * NF + j] > rp.qde) fl |= ARMOUR_TRACK_BOUND;
+        }
+        if (out_of_limits) fl |= ARMOUR_TRACK_LIMIT;
+        if (f.status[r] != 0) fl |= ARMOUR_TRACK_NOT_FINITE;
+        if (lane == 0) {
+            f.clearance[r] = none ? INFINITY : best;
+            f.where[3 * r] = none ? -1 : bc;
+            f.where[3 * r + 1] = none ? -1 : idx / O;
+            f.where[3 * r + 2] = none ? -1 : idx - (idx / O) * O;
+            f.flags[r] = fl;
+        }
+        if (!none && best < wbest) {
+            wbest = best;
+            ws = s;
+            wc = bc;
+            widx = idx;
+        }
+    }
+    if (lane == 0) {
+        f.wclear[w] = wbest;
+        f.wwhere[4 * w] = ws;
+        f.wwhere[4 * w + 1] = wc;
+        f.wwhere[4 * w + 2] = ws < 0 ? -1 : widx / O;
+        f.wwhere[4 * w + 3] = ws < 0 ? -1 : widx - (widx / O) * O;
     }
 }
 
@@ -405,6 +529,103 @@ __global__ void episode_advance_kernel(EpisodeDev e) {
         S.status = 2;
     else if (reached)
         S.status = 1;
+}
+
+// ---- tracked episodes (armour_episode_track) --------------------------------------------------------
+struct EpisodeTrackDev {
+    int S;                        // true arms per world
+    int stop_input, stop_bound, stop_limit;
+    double* traj;                 // [W][4][NF] what the world's true arms follow this step
+    double* win;                  // [W][2] its window; empty: the world is skipped
+    armour_episode_tracked* rec;  // [W] the running record
+    int* flags;                   // [W][S] of the last step each world executed
+    // this step's results (the recording rollouts and motion_state_finish_kernel)
+    const double* out;            // by field (track_store)
+    const int* rflags;            // [W][S]
+    const double* wclear;         // [W]
+    const int* wwhere;            // [W][4]
+};
+
+__global__ void episode_track_begin_kernel(EpisodeDev e, EpisodeTrackDev t) {
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= e.W) return;
+    armour_episode_tracked& R = t.rec[w];
+    R.clearance = INFINITY;
+    for (int k = 0; k < 4; k++) R.clearance_at[k] = -1;
+    for (int j = 0; j < NF; j++) R.max_pos_err[j] = R.max_vel_err[j] = R.max_torque[j] = 0.0;
+    R.max_V = R.max_robust = 0.0;
+    R.flags = 0;
+    for (int k = 0; k < 5; k++) R.flag_step[k] = -1;
+    for (int s = 0; s < t.S; s++) t.flags[(long)w * t.S + s] = 0;
+}
+
+// after step (b): the trajectory and window the true arms follow: what the world executes, or, for a
+// world that stays at rest, the constant trajectory (q, 0, 0, k = 0) on [0, t_plan] (the controller holds
+// the arm and its error keeps evolving); a frozen world gets an empty window
+__global__ void episode_track_choose_kernel(EpisodeDev e, EpisodeTrackDev t) {
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= e.W) return;
+    const int kind = e.kind[w];
+    double* tr = t.traj + (long)w * TRAJ_DOUBLES;
+    if (kind >= 1) {
+        for (int j = 0; j < TRAJ_DOUBLES; j++) tr[j] = e.exec[(long)w * TRAJ_DOUBLES + j];
+        t.win[2 * w] = e.win[2 * w];
+        t.win[2 * w + 1] = e.win[2 * w + 1];
+        return;
+    }
+    for (int j = 0; j < NF; j++) {
+        tr[j] = e.st[w].q[j];
+        tr[NF + j] = tr[2 * NF + j] = tr[3 * NF + j] = 0.0;
+    }
+    t.win[2 * w] = kind == 0 ? 0.0 : 1.0;
+    t.win[2 * w + 1] = kind == 0 ? e.rp->t_plan : 0.0;
+}
+
+// after step (c): the step's rollouts folded into the world's record, and the stops. The existing
+// rules came first (episode_advance_kernel: 4, then 2 for the desired arm); the goal test's status 1
+// stands only if no stop applies.
+__global__ void episode_track_fold_kernel(EpisodeDev e, EpisodeTrackDev t) {
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= e.W) return;
+    if (e.kind[w] < 0) return;
+    armour_episode_state& S = e.st[w];
+    armour_episode_tracked& R = t.rec[w];
+    const int step = S.steps - 1;  // (episode_advance_kernel counted this step)
+    const long NR = (long)e.W * t.S;
+    if (t.wclear[w] < R.clearance) {
+        R.clearance = t.wclear[w];
+        R.clearance_at[0] = step;
+        R.clearance_at[1] = t.wwhere[4 * w];
+        R.clearance_at[2] = t.wwhere[4 * w + 2];
+        R.clearance_at[3] = t.wwhere[4 * w + 3];
+    }
+    int fl = 0;
+    for (int s = 0; s < t.S; s++) {
+        const long r = (long)w * t.S + s;
+        for (int j = 0; j < NF; j++) {
+            R.max_pos_err[j] = fmax(R.max_pos_err[j], t.out[r * NF + j]);
+            R.max_vel_err[j] = fmax(R.max_vel_err[j], t.out[(NR + r) * NF + j]);
+            R.max_torque[j] = fmax(R.max_torque[j], t.out[(2 * NR + r) * NF + j]);
+        }
+        R.max_V = fmax(R.max_V, t.out[21 * NR + r]);
+        R.max_robust = fmax(R.max_robust, t.out[22 * NR + r]);
+        t.flags[r] = t.rflags[r];
+        fl |= t.rflags[r];
+    }
+    for (int k = 0; k < 5; k++)
+        if (((fl >> k) & 1) && R.flag_step[k] < 0) R.flag_step[k] = step;
+    R.flags |= fl;
+    if (S.status == 4 || S.status == 2) return;
+    if (fl & ARMOUR_TRACK_COLLISION)
+        S.status = 2;
+    else if (fl & ARMOUR_TRACK_NOT_FINITE)
+        S.status = 8;
+    else if ((fl & ARMOUR_TRACK_INPUT) && t.stop_input)
+        S.status = 5;
+    else if ((fl & ARMOUR_TRACK_BOUND) && t.stop_bound)
+        S.status = 6;
+    else if ((fl & ARMOUR_TRACK_LIMIT) && t.stop_limit)
+        S.status = 7;
 }
 
 }  // namespace armour

@@ -100,7 +100,7 @@ constexpr long JOB_ENGINE_JOBS = 5120;
 
 // Every environment variable a planner reads when it is created, parsed once (INTEGRATION.md has the
 // table). A planner keeps its settings for life; only three test hooks are read per call, at their
-// call sites: ARMOUR_TRACK_KERNEL (armour_track), ARMOUR_DUMP_LANE (armour_get_reach_dump) and
+// call sites: ARMOUR_TRACK_KERNEL (the tracking entries), ARMOUR_DUMP_LANE (armour_get_reach_dump) and
 // ARMOUR_PC_GROW_FAIL (ensure_plane_cache).
 struct Settings {
     // g_planners sees this process's planners only; planners of other processes on the same GPU
@@ -297,6 +297,22 @@ struct armour_planner {
     int* tr_status = nullptr;
     GrowSet track;
     hipEvent_t tr_ev[2] = {nullptr, nullptr};
+    // armour_track_motion (the recording track kernels, motion_state_*_kernel): the recorded check points,
+    // their per-check-point minima and the per-rollout and per-world results, for tracked.cap =
+    // rollouts x check points, allocated on first use and regrown on demand
+    double *tm_rec = nullptr, *tm_pval = nullptr, *tm_clear = nullptr, *tm_wclear = nullptr;
+    int *tm_pidx = nullptr, *tm_where = nullptr, *tm_flags = nullptr, *tm_wwhere = nullptr;
+    GrowSet tracked;
+    hipEvent_t tm_ev[2] = {nullptr, nullptr};
+    // armour_episode_track: what a tracked episode keeps between steps (the true arms' states, their
+    // scales, the worlds' records), for ep_tracked.cap = max_worlds x num_samples rollouts
+    bool ep_track_on = false;  // armour_episode_track .. the next armour_episode_begin
+    bool ep_stepped = false;   // the episode has taken a step
+    EpisodeTrackDev ept{};
+    int ept_steps = 0;
+    double *ept_state = nullptr, *ept_scale = nullptr;
+    bool ept_scaled = false;
+    GrowSet ep_tracked;
     std::vector<void*> allocs;
 
     template <class T>
@@ -1572,10 +1588,12 @@ void armour_destroy(armour_planner* p) {
     if (!p) return;
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     for (void* a : p->allocs) (void)hipFree(a);
-    for (GrowSet* g : {&p->cand, &p->motion, &p->track}) g->release();
+    for (GrowSet* g : {&p->cand, &p->motion, &p->track, &p->tracked, &p->ep_tracked}) g->release();
     for (hipEvent_t e : p->ep_ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : p->tr_ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : p->tm_ev)
         if (e) (void)hipEventDestroy(e);
     if (p->h_flags) (void)hipHostFree(p->h_flags);
     if (p->h_sum) (void)hipHostFree(p->h_sum);
@@ -1885,10 +1903,16 @@ int armour_check_motion(armour_planner* p, const double* traj, double t0, double
     return 0;
 }
 
-int armour_track(armour_planner* p, int N, const double* traj, int S, const double* scale, const double* err0, double t0,
-                 double t1, int steps, armour_track_output* out) {
-    DeviceScope device_scope(p);
-    if (!p || !traj || !out) return fail(ARMOUR_E_ARG, "null planner / traj / out");
+// ARMOUR_TRACK_KERNEL=serial (a test hook, read per call): the serial form of the rollouts, which
+// computes the same bits as the row form; armour_track and armour_track_motion both ask here
+static bool track_serial_asked() {
+    const char* kv = std::getenv("ARMOUR_TRACK_KERNEL");
+    return kv && !std::strcmp(kv, "serial");
+}
+
+// the argument checks of the tracking entries after their null checks: before any device work
+static int track_check_args(armour_planner* p, int N, const double* traj, int S, const double* scale, const double* err0,
+                            double t0, double t1, int steps) {
     if (p->armtd) return fail(ARMOUR_E_ARG, "tracking rollouts are not available on an ARMTD planner");
     if (p->set.eval_f32) return fail(ARMOUR_E_ARG, "tracking rollouts are not available with the fp32 study (ARMOUR_EVAL_F32)");
     if (N < 1 || S < 1) return fail(ARMOUR_E_ARG, "num_traj and num_samples must be at least 1");
@@ -1914,12 +1938,49 @@ int armour_track(armour_planner* p, int N, const double* traj, int S, const doub
     if (err0)
         for (size_t i = 0; i < (size_t)NR * 2 * NF; i++)
             if (!std::isfinite(err0[i])) return fail(ARMOUR_E_ARG, "err0 holds a value that is not finite");
+    return 0;
+}
+
+// launches the rollouts of `a` (device pointers; out and status are filled in here) between the events
+// tr_ev[0] and tr_ev[1]: the plain kernels, the recording ones (x.rec) or a tracked episode's (x.win)
+static int track_launch(armour_planner* p, TrackArgs a, const TrackExtra& x) {
+    const long NR = (long)a.N * a.S;
+    a.rp = p->d_rp;
+    a.out = p->tr_out;
+    a.status = p->tr_status;
+    // the row form is the default (DESIGN.md section 4 has the measurement)
+    const bool serial = track_serial_asked();
+    const dim3 grid((unsigned)(serial ? (NR + TRACK_THREADS - 1) / TRACK_THREADS : (NR + TRACK_ROWS - 1) / TRACK_ROWS));
+    const dim3 block(TRACK_THREADS);
+    HIPCK(hipEventRecord(p->tr_ev[0], p->stream));
+    if (x.win && serial)
+        hipLaunchKernelGGL(track_serial_episode_kernel, grid, block, 0, p->stream, a, x);
+    else if (x.win)
+        hipLaunchKernelGGL(track_row_episode_kernel, grid, block, 0, p->stream, a, x);
+    else if (x.rec && serial)
+        hipLaunchKernelGGL(track_serial_rec_kernel, grid, block, 0, p->stream, a, x);
+    else if (x.rec)
+        hipLaunchKernelGGL(track_row_rec_kernel, grid, block, 0, p->stream, a, x);
+    else if (serial)
+        hipLaunchKernelGGL(track_serial_kernel, grid, block, 0, p->stream, a);
+    else
+        hipLaunchKernelGGL(track_row_kernel, grid, block, 0, p->stream, a);
+    HIPCK(hipGetLastError());
+    HIPCK(hipEventRecord(p->tr_ev[1], p->stream));
+    return 0;
+}
+
+// uploads the caller's inputs of N x S rollouts and launches them; rec (device,
+// [steps / stride + 1][N * S][2][7]) selects the recording kernels, null the plain ones
+static int track_upload_launch(armour_planner* p, int N, const double* traj, int S, const double* scale, const double* err0,
+                               double t0, double t1, int steps, double* rec, int stride) {
+    const long NR = (long)N * S;
+    const int NJ = p->NJ;
     if (int rc = track_reserve(p, NR)) return rc;
     HIPCK(hipMemcpyAsync(p->tr_traj, traj, sizeof(double) * N * TRAJ_DOUBLES, hipMemcpyHostToDevice, p->stream));
     if (scale) HIPCK(hipMemcpyAsync(p->tr_scale, scale, sizeof(double) * NR * 2 * NJ, hipMemcpyHostToDevice, p->stream));
     if (err0) HIPCK(hipMemcpyAsync(p->tr_err0, err0, sizeof(double) * NR * 2 * NF, hipMemcpyHostToDevice, p->stream));
     TrackArgs a{};
-    a.rp = p->d_rp;
     a.N = N;
     a.S = S;
     a.traj = p->tr_traj;
@@ -1928,21 +1989,11 @@ int armour_track(armour_planner* p, int N, const double* traj, int S, const doub
     a.t0 = t0;
     a.t1 = t1;
     a.steps = steps;
-    a.out = p->tr_out;
-    a.status = p->tr_status;
-    // the row form is the default (DESIGN.md section 4 has the measurement); ARMOUR_TRACK_KERNEL=serial
-    // selects the serial form, which computes the same bits
-    const char* kv = std::getenv("ARMOUR_TRACK_KERNEL");
-    const bool serial = kv && !std::strcmp(kv, "serial");
-    HIPCK(hipEventRecord(p->tr_ev[0], p->stream));
-    if (serial)
-        hipLaunchKernelGGL(track_serial_kernel, dim3((unsigned)((NR + TRACK_THREADS - 1) / TRACK_THREADS)), dim3(TRACK_THREADS), 0,
-                           p->stream, a);
-    else
-        hipLaunchKernelGGL(track_row_kernel, dim3((unsigned)((NR + TRACK_ROWS - 1) / TRACK_ROWS)), dim3(TRACK_THREADS), 0,
-                           p->stream, a);
-    HIPCK(hipGetLastError());
-    HIPCK(hipEventRecord(p->tr_ev[1], p->stream));
+    return track_launch(p, a, TrackExtra{rec, stride, nullptr, nullptr});
+}
+
+// queues the copies of the rollouts' outputs the caller asked for
+static int track_copy_out(armour_planner* p, long NR, armour_track_output* out) {
     const size_t n = (size_t)NR;
     struct { double* dst; size_t off, len; } parts[] = {
         {out->max_pos_err, 0, n * NF},       {out->max_vel_err, n * NF, n * NF}, {out->max_torque, 2 * n * NF, n * NF},
@@ -1951,10 +2002,90 @@ int armour_track(armour_planner* p, int N, const double* traj, int S, const doub
         if (part.dst)
             HIPCK(hipMemcpyAsync(part.dst, p->tr_out + part.off, sizeof(double) * part.len, hipMemcpyDeviceToHost, p->stream));
     if (out->status) HIPCK(hipMemcpyAsync(out->status, p->tr_status, sizeof(int) * n, hipMemcpyDeviceToHost, p->stream));
+    return 0;
+}
+
+int armour_track(armour_planner* p, int N, const double* traj, int S, const double* scale, const double* err0, double t0,
+                 double t1, int steps, armour_track_output* out) {
+    DeviceScope device_scope(p);
+    if (!p || !traj || !out) return fail(ARMOUR_E_ARG, "null planner / traj / out");
+    if (int rc = track_check_args(p, N, traj, S, scale, err0, t0, t1, steps)) return rc;
+    if (int rc = track_upload_launch(p, N, traj, S, scale, err0, t0, t1, steps, nullptr, 1)) return rc;
+    if (int rc = track_copy_out(p, (long)N * S, out)) return rc;
     HIPCK(hipStreamSynchronize(p->stream));
     float ms = 0.f;
     HIPCK(hipEventElapsedTime(&ms, p->tr_ev[0], p->tr_ev[1]));
     out->track_ms = ms;
+    return 0;
+}
+
+// buffers of armour_track_motion for `cells` = rollouts x check points (check points >= 2, so at most
+// cells / 2 rollouts: the per-rollout arrays are sized by cells as well, which holds for every split)
+static int tracked_reserve(armour_planner* p, long cells) {
+    if (!p->tm_ev[0])
+        for (int i = 0; i < 2; i++) HIPCK(hipEventCreate(&p->tm_ev[i]));
+    const size_t n = (size_t)cells, Wm = (size_t)p->Wmax;
+    return p->tracked.reserve(p->stream, cells,
+                              {GrowSet::buf(p->tm_rec, n * 2 * NF), GrowSet::buf(p->tm_pval, n), GrowSet::buf(p->tm_pidx, n),
+                               GrowSet::buf(p->tm_clear, n), GrowSet::buf(p->tm_where, n * 3), GrowSet::buf(p->tm_flags, n),
+                               GrowSet::buf(p->tm_wclear, Wm), GrowSet::buf(p->tm_wwhere, Wm * 4)},
+                              "hipMalloc failed for the true-arm check's buffers (worlds x num_samples x check_samples)");
+}
+
+// the true-arm check of the resident batch over the C recorded check points of its W x S rollouts
+// (tm_rec, with the rollouts' outputs in tr_out / tr_status), between the events tm_ev[0] and tm_ev[1];
+// win (device, [W][2]; a tracked episode's step): worlds with an empty window are skipped
+static int launch_state_check(armour_planner* p, int S, int C, const double* win) {
+    MotionArgs a{};
+    a.rp = p->d_rp;
+    a.W = p->W;
+    a.S = S;
+    a.O = p->d.O;
+    a.Ow = p->d.Ow;
+    a.obs = p->obs;
+    a.win = win;
+    a.pval = p->tm_pval;
+    a.pidx = p->tm_pidx;
+    TrackedFinish f{C, p->tm_rec, p->tr_out, p->tr_status, p->tm_clear, p->tm_where, p->tm_flags, p->tm_wclear, p->tm_wwhere};
+    HIPCK(hipEventRecord(p->tm_ev[0], p->stream));
+    hipLaunchKernelGGL(motion_state_check_kernel, dim3(C, S, p->W), dim3(MOTION_THREADS), 0, p->stream, a,
+                       (const double*)p->tm_rec, C);
+    hipLaunchKernelGGL(motion_state_finish_kernel, dim3(p->W), dim3(64), 0, p->stream, a, f);
+    HIPCK(hipGetLastError());
+    HIPCK(hipEventRecord(p->tm_ev[1], p->stream));
+    return 0;
+}
+
+int armour_track_motion(armour_planner* p, const double* traj, int S, const double* scale, const double* err0, double t0,
+                        double t1, int steps, int check_samples, armour_track_motion_output* out) {
+    DeviceScope device_scope(p);
+    // (the rule between the two counts needs no planner: it is refused first)
+    if (check_samples < 2) return fail(ARMOUR_E_ARG, "check_samples must be at least 2");
+    if (steps >= 1 && steps % (check_samples - 1) != 0) return fail(ARMOUR_E_ARG, "steps must be a multiple of check_samples - 1");
+    if (!p || !traj || !out) return fail(ARMOUR_E_ARG, "null planner / traj / out");
+    if (!p->armtd && !p->set.eval_f32 && !p->reached) return fail(ARMOUR_E_STATE, "no batch: call a reach or plan entry first");
+    const int W = p->reached ? p->W : 1;
+    if (int rc = track_check_args(p, W, traj, S, scale, err0, t0, t1, steps)) return rc;
+    if (S > 65535) return fail(ARMOUR_E_ARG, "num_samples must be at most 65535");
+    const int C = check_samples, stride = steps / (C - 1);
+    const long NR = (long)W * S;
+    if (int rc = tracked_reserve(p, NR * C)) return rc;
+    if (int rc = track_upload_launch(p, W, traj, S, scale, err0, t0, t1, steps, p->tm_rec, stride)) return rc;
+    if (int rc = launch_state_check(p, S, C, nullptr)) return rc;
+    if (int rc = track_copy_out(p, NR, &out->track)) return rc;
+    const size_t n = (size_t)NR;
+    if (out->clearance) HIPCK(hipMemcpyAsync(out->clearance, p->tm_clear, sizeof(double) * n, hipMemcpyDeviceToHost, p->stream));
+    if (out->where) HIPCK(hipMemcpyAsync(out->where, p->tm_where, sizeof(int) * 3 * n, hipMemcpyDeviceToHost, p->stream));
+    if (out->flags) HIPCK(hipMemcpyAsync(out->flags, p->tm_flags, sizeof(int) * n, hipMemcpyDeviceToHost, p->stream));
+    if (out->world_clearance)
+        HIPCK(hipMemcpyAsync(out->world_clearance, p->tm_wclear, sizeof(double) * W, hipMemcpyDeviceToHost, p->stream));
+    if (out->world_where) HIPCK(hipMemcpyAsync(out->world_where, p->tm_wwhere, sizeof(int) * 4 * W, hipMemcpyDeviceToHost, p->stream));
+    HIPCK(hipStreamSynchronize(p->stream));
+    float ms = 0.f;
+    HIPCK(hipEventElapsedTime(&ms, p->tr_ev[0], p->tr_ev[1]));
+    out->track.track_ms = ms;
+    HIPCK(hipEventElapsedTime(&ms, p->tm_ev[0], p->tm_ev[1]));
+    out->check_ms = ms;
     return 0;
 }
 
@@ -2009,6 +2140,113 @@ int armour_episode_begin(armour_planner* p, int W, const armour_world* worlds, c
     HIPCK(hipGetLastError());
     if ((rc = episode_read(p))) return rc;  // (also: `goals` is the caller's, its copy has finished)
     p->episode = true;
+    p->ep_track_on = p->ep_stepped = false;
+    return 0;
+}
+
+int armour_episode_track(armour_planner* p, const armour_episode_track_config* cfg) {
+    DeviceScope device_scope(p);
+    if (!p || !cfg) return fail(ARMOUR_E_ARG, "null argument");
+    if (!p->episode) return fail(ARMOUR_E_STATE, "no episode: call armour_episode_begin first (any other reach or plan entry ends one)");
+    if (p->ep_stepped) return fail(ARMOUR_E_STATE, "the episode has taken a step: tracking is enabled before the first step");
+    const int W = p->W, S = cfg->num_samples, NJ = p->NJ, C = p->ep.S;
+    if (S < 1 || S > 65535) return fail(ARMOUR_E_ARG, "num_samples must lie in 1 .. 65535");
+    if ((long)W * S > ARMOUR_TRACK_MAX_ROLLOUTS) return fail(ARMOUR_E_ARG, "num_worlds x num_samples exceeds ARMOUR_TRACK_MAX_ROLLOUTS");
+    if (cfg->steps < 1 || cfg->steps > ARMOUR_TRACK_MAX_STEPS) return fail(ARMOUR_E_ARG, "steps must lie in 1 .. ARMOUR_TRACK_MAX_STEPS");
+    if (cfg->steps % (C - 1) != 0) return fail(ARMOUR_E_ARG, "steps must be a multiple of the episode's check_samples - 1");
+    const size_t NR = (size_t)W * S;
+    if (cfg->scale)
+        for (size_t i = 0; i < NR * 2 * NJ; i++) {
+            if (!std::isfinite(cfg->scale[i])) return fail(ARMOUR_E_ARG, "scale holds a value that is not finite");
+            if (!(cfg->scale[i] > 0)) return fail(ARMOUR_E_ARG, "every scale must be positive");
+        }
+    if (cfg->err0)
+        for (size_t i = 0; i < NR * 2 * NF; i++)
+            if (!std::isfinite(cfg->err0[i])) return fail(ARMOUR_E_ARG, "err0 holds a value that is not finite");
+    // the true arms start from the episode's start states plus err0
+    std::vector<double> start(NR * 2 * NF);
+    for (size_t r = 0; r < NR; r++) {
+        const armour_episode_state& st = p->ep_host[r / S];
+        for (int j = 0; j < NF; j++) {
+            const double* e0 = cfg->err0 ? cfg->err0 + r * 2 * NF : nullptr;
+            start[r * 2 * NF + j] = e0 ? st.q[j] + e0[j] : st.q[j];
+            start[r * 2 * NF + NF + j] = e0 ? st.qd[j] + e0[NF + j] : st.qd[j];
+            if (!std::isfinite(start[r * 2 * NF + j]) || !std::isfinite(start[r * 2 * NF + NF + j]))
+                return fail(ARMOUR_E_ARG, "err0 leads to a start state that is not finite");
+        }
+    }
+    EpisodeTrackDev& t = p->ept;
+    const size_t n = (size_t)p->Wmax * S, Wm = (size_t)p->Wmax;
+    if (int rc = p->ep_tracked.reserve(p->stream, (long)n,
+                                       {GrowSet::buf(p->ept_state, n * 2 * NF), GrowSet::buf(p->ept_scale, n * 2 * MAX_J),
+                                        GrowSet::buf(t.flags, n), GrowSet::buf(t.traj, Wm * TRAJ_DOUBLES), GrowSet::buf(t.win, Wm * 2),
+                                        GrowSet::buf(t.rec, Wm)},
+                                       "hipMalloc failed for the tracked episode's buffers (max_worlds x num_samples)"))
+        return rc;
+    if (int rc = track_reserve(p, (long)NR)) return rc;
+    if (int rc = tracked_reserve(p, (long)NR * C)) return rc;
+    t.S = S;
+    t.stop_input = cfg->stop_on_input != 0;
+    t.stop_bound = cfg->stop_on_bound != 0;
+    t.stop_limit = cfg->stop_on_limit != 0;
+    p->ept_steps = cfg->steps;
+    p->ept_scaled = cfg->scale != nullptr;
+    HIPCK(hipMemcpyAsync(p->ept_state, start.data(), sizeof(double) * NR * 2 * NF, hipMemcpyHostToDevice, p->stream));
+    if (cfg->scale) HIPCK(hipMemcpyAsync(p->ept_scale, cfg->scale, sizeof(double) * NR * 2 * NJ, hipMemcpyHostToDevice, p->stream));
+    hipLaunchKernelGGL(episode_track_begin_kernel, dim3((W + 63) / 64), dim3(64), 0, p->stream, p->ep, t);
+    HIPCK(hipGetLastError());
+    HIPCK(hipStreamSynchronize(p->stream));  // (`start` and the caller's arrays outlive their copies)
+    p->ep_track_on = true;
+    return 0;
+}
+
+// step (c) of a tracked episode, after episode_advance_kernel: the true arms along what each running
+// world executes, the check of their recorded states, and the fold into the records and the status
+static int episode_track_step(armour_planner* p) {
+    const int W = p->W, C = p->ep.S;
+    EpisodeTrackDev& t = p->ept;
+    const long NR = (long)W * t.S;
+    // (another tracking entry between two steps may have regrown these; their contents live one step)
+    if (int rc = track_reserve(p, NR)) return rc;
+    if (int rc = tracked_reserve(p, NR * C)) return rc;
+    t.out = p->tr_out;
+    t.rflags = p->tm_flags;
+    t.wclear = p->tm_wclear;
+    t.wwhere = p->tm_wwhere;
+    const dim3 wg((W + 63) / 64), wb(64);
+    hipLaunchKernelGGL(episode_track_choose_kernel, wg, wb, 0, p->stream, p->ep, t);
+    TrackArgs a{};
+    a.N = W;
+    a.S = t.S;
+    a.traj = t.traj;
+    a.scale = p->ept_scaled ? p->ept_scale : nullptr;
+    a.steps = p->ept_steps;
+    if (int rc = track_launch(p, a, TrackExtra{p->tm_rec, p->ept_steps / (C - 1), t.win, p->ept_state})) return rc;
+    if (int rc = launch_state_check(p, t.S, C, t.win)) return rc;
+    hipLaunchKernelGGL(episode_track_fold_kernel, wg, wb, 0, p->stream, p->ep, t);
+    HIPCK(hipGetLastError());
+    return 0;
+}
+
+int armour_episode_get_tracked(armour_planner* p, armour_episode_tracked* records, double* true_state, int* flags, double* ms) {
+    DeviceScope device_scope(p);
+    if (!p || !records) return fail(ARMOUR_E_ARG, "null argument");
+    if (!p->episode) return fail(ARMOUR_E_STATE, "no episode: call armour_episode_begin first (any other reach or plan entry ends one)");
+    if (!p->ep_track_on) return fail(ARMOUR_E_STATE, "tracking is not enabled: call armour_episode_track after armour_episode_begin");
+    const size_t W = (size_t)p->W, NR = W * p->ept.S;
+    HIPCK(hipMemcpyAsync(records, p->ept.rec, sizeof(armour_episode_tracked) * W, hipMemcpyDeviceToHost, p->stream));
+    if (true_state) HIPCK(hipMemcpyAsync(true_state, p->ept_state, sizeof(double) * NR * 2 * NF, hipMemcpyDeviceToHost, p->stream));
+    if (flags) HIPCK(hipMemcpyAsync(flags, p->ept.flags, sizeof(int) * NR, hipMemcpyDeviceToHost, p->stream));
+    HIPCK(hipStreamSynchronize(p->stream));
+    if (ms) {
+        float a = 0, b = 0;
+        if (p->ep_stepped) {
+            (void)hipEventElapsedTime(&a, p->tr_ev[0], p->tr_ev[1]);
+            (void)hipEventElapsedTime(&b, p->tm_ev[0], p->tm_ev[1]);
+        }
+        ms[0] = a;
+        ms[1] = b;
+    }
     return 0;
 }
 
@@ -2050,6 +2288,8 @@ int armour_episode_step(armour_planner* p, const int* reject, armour_result* res
     hipLaunchKernelGGL(episode_advance_kernel, wg, wb, 0, p->stream, e);
     HIPCK(hipEventRecord(p->ep_ev[3], p->stream));
     HIPCK(hipGetLastError());
+    p->ep_stepped = true;
+    if (p->ep_track_on && (rc = episode_track_step(p))) return rc;
     if ((rc = episode_read(p))) return rc;  // (ends in a synchronisation: `accept` outlives its copy)
     if (episode_ms) {
         float a = 0, b = 0, c = 0;

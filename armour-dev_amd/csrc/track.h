@@ -9,6 +9,7 @@
 //                    Cholesky solve of the plant and the true storage function
 //   track_step       one classical RK4 step; track_record the maxima; track_rollout_serial the whole
 //                    rollout with every RNEA in one thread ("serial form")
+//   TrackCheckpoints the recorder of armour_track_motion: the states its clearance check reads
 //
 // A stage is written as pre -> ten track_rnea calls that differ only in inputs -> post, so that the
 // row kernel (track_kernels.hip: one RNEA per lane, the rest replicated over the 16 lanes of a row)
@@ -317,6 +318,18 @@ AD void track_init(const RobotParams& rp, const double* traj, const double* err0
     X.status = ok ? 0 : 1;
 }
 
+// the absolute-state form: the rollout starts from state = q [NF], then qd [NF] (a tracked episode's
+// carried true state, finite by construction: it is a start the host checked or an end state)
+AD void track_init(const double* state, TrackState& X) {
+    for (int j = 0; j < NF; j++) {
+        X.q[j] = state[j];
+        X.qd[j] = state[NF + j];
+        X.max_pos_err[j] = X.max_vel_err[j] = X.max_torque[j] = 0.0;
+    }
+    X.max_V = X.max_robust = 0.0;
+    X.status = 0;
+}
+
 // the maxima at a recorded stage; a stage that is not ok ends the rollout
 AD void track_record(const TrackPre& P, const TrackStage& S, TrackState& X) {
     if (X.status != 0) return;
@@ -388,19 +401,54 @@ AD void track_step(Eval& ev, double t, double h, TrackState& X) {
     }
 }
 
+// A recorder sees the state at the first stage of every step (s = 0 .. steps - 1) and at t1 (s = steps).
+// It only reads: the rollout is the same with and without one. TrackNoRecord is the empty one.
+struct TrackNoRecord {
+    AD void operator()(int, const TrackState&) const {}
+};
+// Check point c = s / stride of rollout i goes to rec [check point][rollout][2][NF] (q, then qd) when
+// s is a multiple of stride (steps % stride == 0, so t1 is the last check point). A rollout that
+// stopped being finite records the state it keeps. `on` gates the stores (one lane of a row; a live row).
+struct TrackCheckpoints {
+    double* rec;
+    long NR, i;
+    int stride;
+    bool on;
+    AD void operator()(int s, const TrackState& X) const {
+        if (!on || s % stride != 0) return;
+        double* dst = rec + ((long)(s / stride) * NR + i) * 2 * NF;
+        for (int j = 0; j < NF; j++) {
+            dst[j] = X.q[j];
+            dst[NF + j] = X.qd[j];
+        }
+    }
+};
+
 // `steps` RK4 steps over [t0, t1] (step s starts at t0 + s h) and the last record at t1
-template <class Eval>
-AD void track_run(Eval& ev, double t0, double t1, int steps, TrackState& X) {
+template <class Eval, class Rec>
+AD void track_run(Eval& ev, double t0, double t1, int steps, TrackState& X, const Rec& rec) {
     const double h = (t1 - t0) / steps;
-    for (int s = 0; s < steps; s++) track_step(ev, t0 + s * h, h, X);
+    for (int s = 0; s < steps; s++) {
+        rec(s, X);
+        track_step(ev, t0 + s * h, h, X);
+    }
     TrackPre P;
     TrackStage S;
     ev(t1, X.q, X.qd, P, S);
     track_record(P, S, X);
+    rec(steps, X);
+}
+template <class Eval>
+AD void track_run(Eval& ev, double t0, double t1, int steps, TrackState& X) {
+    track_run(ev, t0, t1, steps, X, TrackNoRecord{});
 }
 
-// the serial form of a stage: all ten RNEAs in this thread
-struct TrackSerialEval {
+// the serial form of a stage: all ten RNEAs in this thread. KERNEL only names the instantiation: every
+// kernel runs track_step / track_run on a stage type of its own, so that each copy has one caller and is
+// inlined into its kernel as when there was one kernel per form (a shared copy is called, not inlined:
+// measured 106 ms against 83 ms for the rollouts of profiles/track_time.txt)
+template <int KERNEL = 0>
+struct TrackSerialEvalT {
     const RobotParams& rp;
     const double* traj;  // [4][7]
     const double* ms;    // [num_joints] mass scales (null: 1)
@@ -421,6 +469,7 @@ struct TrackSerialEval {
         track_post(rp, P, G, S);
     }
 };
+using TrackSerialEval = TrackSerialEvalT<>;
 
 AD void track_rollout_serial(const RobotParams& rp, const double* traj, const double* ms, const double* is, const double* err0,
                              double t0, double t1, int steps, TrackState& X) {

@@ -13,7 +13,14 @@
 // track_serial_kernel  the serial form of track.h, one thread per rollout: the definition the host
 //                      build tests and the baseline the row form is measured against
 //                      (ARMOUR_TRACK_KERNEL=serial).
-// Both run the same functions on the same values in the same order and agree bitwise.
+// track_row_rec_kernel, track_serial_rec_kernel   the same two bodies with a recorder (armour_track_motion;
+//                      the _episode_ kernels: a tracked episode's step, with per-trajectory windows and
+//                      carried states, TrackMode below):
+//                      lane 0 of a row (the thread, in the serial form) also stores the 14 doubles of
+//                      every check point into rec [check point][rollout][2][7], so neighbouring rows
+//                      store neighbouring memory. The recorder only reads the state: maxima, end state
+//                      and status are those of the kernels without one.
+// Both forms run the same functions on the same values in the same order and agree bitwise.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -38,7 +45,8 @@ struct TrackArgs {
     int* status;            // [NR]
 };
 
-// a stage in row form: this lane's RNEA, the rest replicated over the row
+// a stage in row form: this lane's RNEA, the rest replicated over the row (KERNEL: as TrackSerialEvalT's)
+template <int KERNEL>
 struct TrackRowEval {
     const RobotParams& rp;
     const double* traj;
@@ -75,7 +83,53 @@ struct TrackRowEval {
     }
 };
 
-__global__ __launch_bounds__(TRACK_THREADS) void track_row_kernel(TrackArgs a) {
+// What a kernel does beyond the plain rollouts. TRACK_RECORD: check points go to rec (TrackCheckpoints).
+// TRACK_EPISODE (a tracked episode's step): the record, and every trajectory carries its own window
+// win [N][2] and every rollout starts from its carried state [NR][2][NF], which its end state replaces.
+// An empty window (t0 < t1 does not hold) skips the rollout: no thread may leave before a barrier, so it
+// computes on [0, 1] and stores nothing, as rows past the last rollout do.
+enum TrackMode { TRACK_PLAIN = 0, TRACK_RECORD = 1, TRACK_EPISODE = 2 };
+struct TrackExtra {
+    double* rec;        // [steps / stride + 1][NR][2][NF]
+    int stride;
+    const double* win;  // TRACK_EPISODE
+    double* state;      // TRACK_EPISODE
+};
+
+// window, start and gate of rollout i; returns whether its results are stored
+template <int MODE>
+__device__ __forceinline__ bool track_begin(const TrackArgs& a, const TrackExtra& e, const RobotParams& rp, const double* traj,
+                                            long i, bool live, double& t0, double& t1, TrackState& X) {
+    t0 = a.t0;
+    t1 = a.t1;
+    if constexpr (MODE == TRACK_EPISODE) {
+        t0 = e.win[2 * (i / a.S)];
+        t1 = e.win[2 * (i / a.S) + 1];
+        const bool run = t0 < t1;
+        if (!run) {
+            t0 = 0.0;
+            t1 = 1.0;
+        }
+        track_init(e.state + i * 2 * NF, X);
+        return live && run;
+    } else {
+        track_init(rp, traj, a.err0 ? a.err0 + i * 2 * NF : nullptr, t0, X);
+        return live;
+    }
+}
+template <int MODE>
+__device__ __forceinline__ void track_end(const TrackArgs& a, const TrackExtra& e, const TrackState& X, long i, long NR) {
+    track_store(X, i, NR, a.out, a.status);
+    if constexpr (MODE == TRACK_EPISODE)
+        for (int j = 0; j < NF; j++) {
+            e.state[i * 2 * NF + j] = X.q[j];
+            e.state[i * 2 * NF + NF + j] = X.qd[j];
+        }
+}
+
+// the body of the row form; lane 0 of a live row stores
+template <int MODE>
+__device__ __forceinline__ void track_row_body(const TrackArgs& a, const TrackExtra& e) {
     __shared__ RobotParams s_rp;
     __shared__ double s_traj[TRACK_ROWS][TRAJ_DOUBLES];
     __shared__ double s_scale[TRACK_ROWS][2][MAX_J];
@@ -98,14 +152,24 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_row_kernel(TrackArgs a) {
         s_scale[row][which][l] = (a.scale && l < NJ) ? a.scale[(i * 2 + which) * NJ + l] : 1.0;
     }
     __syncthreads();
-    TrackRowEval ev{s_rp, s_traj[row], s_scale[row][0], s_scale[row][1], s_cs[row], s_G[row], sub};
+    TrackRowEval<MODE> ev{s_rp, s_traj[row], s_scale[row][0], s_scale[row][1], s_cs[row], s_G[row], sub};
     TrackState X;
-    track_init(s_rp, s_traj[row], a.err0 ? a.err0 + i * 2 * NF : nullptr, a.t0, X);
-    track_run(ev, a.t0, a.t1, a.steps, X);
-    if (live && sub == 0) track_store(X, i, NR, a.out, a.status);
+    double t0, t1;
+    const bool store = track_begin<MODE>(a, e, s_rp, s_traj[row], i, live, t0, t1, X) && sub == 0;
+    if constexpr (MODE == TRACK_PLAIN)
+        track_run(ev, t0, t1, a.steps, X);
+    else
+        track_run(ev, t0, t1, a.steps, X, TrackCheckpoints{e.rec, NR, i, e.stride, store});
+    if (store) track_end<MODE>(a, e, X, i, NR);
+}
+__global__ __launch_bounds__(TRACK_THREADS) void track_row_kernel(TrackArgs a) { track_row_body<TRACK_PLAIN>(a, TrackExtra{}); }
+__global__ __launch_bounds__(TRACK_THREADS) void track_row_rec_kernel(TrackArgs a, TrackExtra e) { track_row_body<TRACK_RECORD>(a, e); }
+__global__ __launch_bounds__(TRACK_THREADS) void track_row_episode_kernel(TrackArgs a, TrackExtra e) {
+    track_row_body<TRACK_EPISODE>(a, e);
 }
 
-__global__ __launch_bounds__(TRACK_THREADS) void track_serial_kernel(TrackArgs a) {
+template <int MODE>
+__device__ __forceinline__ void track_serial_body(const TrackArgs& a, const TrackExtra& e) {
     __shared__ RobotParams s_rp;
     const int tid = threadIdx.x;
     const long NR = (long)a.N * a.S;
@@ -126,8 +190,23 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_serial_kernel(TrackArgs a
         is[l] = (a.scale && l < NJ) ? a.scale[(i * 2 + 1) * NJ + l] : 1.0;
     }
     TrackState X;
-    track_rollout_serial(s_rp, traj, ms, is, a.err0 ? a.err0 + i * 2 * NF : nullptr, a.t0, a.t1, a.steps, X);
-    if (live) track_store(X, i, NR, a.out, a.status);
+    if constexpr (MODE == TRACK_PLAIN) {
+        track_rollout_serial(s_rp, traj, ms, is, a.err0 ? a.err0 + i * 2 * NF : nullptr, a.t0, a.t1, a.steps, X);
+        if (live) track_store(X, i, NR, a.out, a.status);
+    } else {
+        TrackSerialEvalT<MODE> ev{s_rp, traj, ms, is};
+        double t0, t1;
+        const bool store = track_begin<MODE>(a, e, s_rp, traj, i, live, t0, t1, X);
+        track_run(ev, t0, t1, a.steps, X, TrackCheckpoints{e.rec, NR, i, e.stride, store});
+        if (store) track_end<MODE>(a, e, X, i, NR);
+    }
+}
+__global__ __launch_bounds__(TRACK_THREADS) void track_serial_kernel(TrackArgs a) { track_serial_body<TRACK_PLAIN>(a, TrackExtra{}); }
+__global__ __launch_bounds__(TRACK_THREADS) void track_serial_rec_kernel(TrackArgs a, TrackExtra e) {
+    track_serial_body<TRACK_RECORD>(a, e);
+}
+__global__ __launch_bounds__(TRACK_THREADS) void track_serial_episode_kernel(TrackArgs a, TrackExtra e) {
+    track_serial_body<TRACK_EPISODE>(a, e);
 }
 
 }  // namespace armour

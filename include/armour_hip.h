@@ -279,8 +279,8 @@ int armour_check_motion(armour_planner* p, const double* traj, double t0, double
  * the new trajectory for ARMOUR_T_PLAN of its duration 1 (KSI/uarmtd_planner.m:56-62) or, when the
  * plan failed, brakes along the second half of the previous trajectory (uarmtd_planner.m:922-932),
  * and stops on collision or inside the goal radius (kinova_world_static.m:417-425). The state
- * advances on the desired trajectory (no tracking error or dynamics simulation; armour_track below is
- * that simulation, for given trajectories).
+ * advances on the desired trajectory; the true arm with its tracking error is simulated along it only
+ * when armour_episode_track (below, after armour_track) turns that on.
  *
  * armour_episode_begin checks every world with armour_check_world (its q_des is ignored; goals must be
  * finite and within ARMOUR_MAX_ABS_ANGLE; lookahead > 0, goal_radius >= 0, 2 <= check_samples <=
@@ -331,7 +331,8 @@ typedef struct armour_episode_config {
 typedef struct armour_episode_state {
     double q[ARMOUR_NUM_FACTORS], qd[ARMOUR_NUM_FACTORS], qdd[ARMOUR_NUM_FACTORS];
     double q_des[ARMOUR_NUM_FACTORS]; /* what the next plan starts from, and its waypoint */
-    int status;        /* 0 running, 1 goal reached, 2 collided, 3 no fail-safe, 4 left the input domain */
+    int status;        /* 0 running, 1 goal reached, 2 collided, 3 no fail-safe, 4 left the input domain; tracked
+                          episodes also: 5 input, 6 ultimate bound, 7 joint limit, 8 rollout not finite */
     int mode;          /* 0 at rest, 1 moving: the braking half of the last accepted plan is pending */
     int steps, failed_plans, failed_streak;
     double clearance;  /* smallest over every executed sample so far (+infinity: none yet) */
@@ -412,6 +413,112 @@ typedef struct armour_track_output {   /* every pointer optional (null: skipped)
 } armour_track_output;
 int armour_track(armour_planner* p, int num_traj, const double* traj, int num_samples, const double* scale,
                  const double* err0, double t0, double t1, int steps, armour_track_output* out);
+
+/* Rollouts with a record, and the true arm's clearance: armour_track and armour_check_motion joined on
+ * the device. armour_track_motion rolls num_samples true arms per world of the last batch along that
+ * world's trajectory and tests the states the arms actually took, not the desired curve, against the
+ * world's own obstacles. It is defined for the worlds of the last batch (uniform or mixed, after any
+ * reach or plan entry), as armour_check_motion is; ARMOUR_E_STATE before any batch. It touches no plan
+ * or episode state.
+ *
+ * Rollouts. Everything is as armour_track defines it with num_traj = W (traj [W][4][7], scale
+ *   [W][S][2][num_joints] or null, err0 [W][S][2][7] or null, the window, steps), with one addition:
+ * Check points. check_samples (2 ..) must satisfy steps % (check_samples - 1) == 0. With
+ *   stride = steps / (check_samples - 1), check point c is the rollout's state (q, qd) at the first stage
+ *   of step c * stride; the last check point is the state at t1. A rollout that stopped being finite
+ *   records the state it keeps.
+ * Same rollouts. The maxima, the end state and the status (out->track, every pointer optional) are bit
+ *   for bit those armour_track returns for the same inputs: the record only reads the state.
+ * True-arm clearance. At each check point the link boxes come from the point forward kinematics of
+ *   armour_check_motion at the recorded q, and are tested against the world's own obstacles with the
+ *   same 15 axes, skip rule and -1e8 convention.
+ *   clearance [W][S], where [W][S][3]   per rollout: the minimum over (check point, link, obstacle) and
+ *                                       its first minimiser in that order
+ *   world_clearance [W], world_where [W][4]   per world: the minimum over its samples, ties to the lowest
+ *                                       sample, as (sample, check point, link, obstacle)
+ *   A world without obstacles gets +infinity and -1s.
+ * Flags per rollout (flags [W][S]), a bit mask with the reference's strict comparisons
+ *   (uarmtd_agent.m:592-664, uarmtd_robust_CBF_LLC.m:192-219):
+ *   ARMOUR_TRACK_COLLISION   clearance <= 0
+ *   ARMOUR_TRACK_INPUT       some max_torque[j] > torque_limits[j]. The maximum runs over every recorded
+ *                            stage (steps + 1 of them), which is finer than the reference's sampling of
+ *                            the input: a flag here can precede the reference's.
+ *   ARMOUR_TRACK_BOUND       some max_pos_err[j] > qe or max_vel_err[j] > qde, with qe = eps / K and
+ *                            qde = 2 eps of the planner's robot tables (eps = sqrt(2 V_m / M_min))
+ *   ARMOUR_TRACK_LIMIT       at a check point q[j] < state_lb[j], q[j] > state_ub[j] or
+ *                            |qd[j]| > speed_limits[j]
+ *   ARMOUR_TRACK_NOT_FINITE  rollout status 1
+ * check_ms: device time of the check and finish kernels; track.track_ms: that of the rollouts.
+ *
+ * ARMOUR_E_ARG as armour_track (num_traj being the batch's world count), and for num_samples > 65535,
+ * check_samples < 2 or steps % (check_samples - 1) != 0, naming the field and before any device work. */
+#define ARMOUR_TRACK_COLLISION 1
+#define ARMOUR_TRACK_INPUT 2
+#define ARMOUR_TRACK_BOUND 4
+#define ARMOUR_TRACK_LIMIT 8
+#define ARMOUR_TRACK_NOT_FINITE 16
+typedef struct armour_track_motion_output {   /* every pointer optional (null: skipped) */
+    armour_track_output track;  /* the rollouts, [W][S] */
+    double* clearance;          /* [W][S] */
+    int* where;                 /* [W][S][3] check point, link, obstacle */
+    int* flags;                 /* [W][S] */
+    double* world_clearance;    /* [W] */
+    int* world_where;           /* [W][4] sample, check point, link, obstacle */
+    double check_ms;            /* device time of the true-arm check */
+} armour_track_motion_output;
+int armour_track_motion(armour_planner* p, const double* traj, int num_samples, const double* scale, const double* err0,
+                        double t0, double t1, int steps, int check_samples, armour_track_motion_output* out);
+
+/* Tracked episodes: the true arm run through each executed segment (simulator_armtd.m:189-271 with
+ * uarmtd_agent.m:469; its four checks on the true states and inputs: input_check, ultimate_bound_check,
+ * joint_limit_check and collision_check, of which the reference stops on the first, second and fourth).
+ * armour_episode_track is called after armour_episode_begin and before the first step; from then on step
+ * (c) of armour_episode_step also rolls num_worlds x num_samples true arms, as armour_track_motion
+ * defines them, along what each running world executes, with the episode's check_samples check points
+ * (steps % (check_samples - 1) == 0).
+ *   What each rollout follows: the new plan on [0, ARMOUR_T_PLAN]; the pending plan on
+ *     [ARMOUR_T_PLAN, 1]; for a world that stays at rest the constant trajectory (q, 0, 0, k = 0) on
+ *     [0, ARMOUR_T_PLAN]: the controller holds the arm, and its error keeps evolving.
+ *   Where it starts: from the true state (q, qd) the previous step left, an absolute state, not an
+ *     offset; at the first step from the episode's start state plus err0 (null: zero).
+ *   Windows. Each world's trajectory carries its own window; an empty window (t0 > t1) means its rollouts
+ *     are skipped: their states and outputs stay as they were. Frozen worlds are skipped.
+ *   Planning is unaffected: it still starts from the desired state, as the reference's planner does
+ *     (uarmtd_planner.m:91-93); results and armour_episode_state's trajectory fields are bit for bit those
+ *     of an untracked episode until a stop below. Tracking feeds back only through these stops.
+ *   A record per world accumulates over steps and samples (armour_episode_tracked): the smallest true
+ *     clearance with its step, sample, link and obstacle; the per-joint maxima of position error, velocity
+ *     error and torque; the largest V and lambda; the OR of the flags and the first step of each flag.
+ *   Status. The existing rules come first: 4, then 2 for the desired arm. After them, in this order: a
+ *     true clearance <= 0 gives 2; NOT_FINITE gives 8; INPUT gives 5 if stop_on_input; BOUND gives 6 if
+ *     stop_on_bound; LIMIT gives 7 if stop_on_limit; then the goal test as before (on the desired samples).
+ * ARMOUR_E_STATE without an episode or after its first step; ARMOUR_E_ARG for a null argument,
+ * num_samples < 1 (or > 65535, or more than ARMOUR_TRACK_MAX_ROLLOUTS rollouts), steps outside
+ * 1 .. ARMOUR_TRACK_MAX_STEPS or no multiple of check_samples - 1, a scale that is not finite or not
+ * positive, an err0 that is not finite. A new armour_episode_begin ends the tracking.
+ *
+ * armour_episode_get_tracked: records [W]; true_state [W][S][2][7] (optional) the true arms' states now;
+ * flags [W][S] (optional) of the last step each world executed; ms [2] (optional) the device time of the
+ * last step's rollouts and of its true-arm check. ARMOUR_E_STATE when there is no episode or tracking is
+ * not enabled. */
+typedef struct armour_episode_track_config {
+    int num_samples;
+    const double* scale;   /* [W][S][2][num_joints] or null: nominal */
+    const double* err0;    /* [W][S][2][7] or null: zero */
+    int steps;             /* RK4 steps per executed segment */
+    int stop_on_input, stop_on_bound, stop_on_limit;   /* the reference: 1, 1, 0 (simulator_armtd.m:14-16) */
+} armour_episode_track_config;
+typedef struct armour_episode_tracked {
+    double clearance;      /* smallest true clearance so far (+infinity: none yet) */
+    int clearance_at[4];   /* its step, sample, link, obstacle (-1: none yet) */
+    double max_pos_err[ARMOUR_NUM_FACTORS], max_vel_err[ARMOUR_NUM_FACTORS], max_torque[ARMOUR_NUM_FACTORS];
+    double max_V, max_robust;
+    int flags;             /* the OR of every rollout's flags so far */
+    int flag_step[5];      /* first step of COLLISION, INPUT, BOUND, LIMIT, NOT_FINITE (-1: never) */
+} armour_episode_tracked;
+int armour_episode_track(armour_planner* p, const armour_episode_track_config* cfg);
+int armour_episode_get_tracked(armour_planner* p, armour_episode_tracked* records, double* true_state, int* flags,
+                               double* ms);
 
 /* Outputs of world w of the last batch (the armour_*.out payloads, armour_main.cu:340-398) */
 int armour_get_constraints(armour_planner* p, int w, double* g);              /* m values at k_opt (m_w of world w) */
