@@ -72,6 +72,47 @@ constexpr int WS_RESTO = 6;
 // interior-point loop hand it back to lists that still name it (planner.hip ipm_loop)
 constexpr int WS_RESTART = 7;
 
+// Slots of the device counters NlpDev::cnt and of the mapped host flags NlpDev::flags. A slot named
+// with a parity is a pair (base, base + 1), taken with slot(base, parity).
+enum CntSlot : int {
+    CNT_RUN = 0,      // worlds a world kernel has appended to wl_run (round 0) / counted (resto_count)
+    CNT_SEARCH = 1,   // worlds appended to wl_search (ipm_world_Cs_all: worlds that searched past round 0)
+    CNT_TICKET = 2,   // block ticket: the last block publishes the counts and zeroes the three
+    CNT_LS = 4,       // + parity of the line-search round: length of that round's searching list
+    CNT_PC_MISS = 7,  // evaluations that found a block's plane records missing (get_plane_cache_stats)
+    CNT_ITER = 8,     // + parity of the iteration: length of that iteration's running list
+    CNT_RL = 12,      // length of the append list of restoration work (Round::rl_app)
+    CNT_PL = 14,      // length of the phase list resto_publish moved it into
+    CNT_LEN = 16
+};
+enum FlagSlot : int {
+    FLAG_RUN = 0,     // worlds running after round 0 / counted by resto_count, ipm_collect
+    FLAG_SEARCH = 1,  // worlds still searching after the last line-search round
+    FLAG_NRUN = 2,    // + parity: a sync-free iteration's running count, read one iteration later
+    FLAG_BT = 4,      // + parity: its worlds that searched past round 0
+    FLAG_PEND = 6,    // + parity: CNT_RL as its last world kernel saw it (Round::pend_flag)
+    FLAG_PUB = 8,     // + parity: the list length a concurrent phase iteration's publish moved
+    FLAG_LEN = 12
+};
+constexpr int slot(int base, int parity) { return base + (parity & 1); }
+// Every slot, a pair with both parities, lies inside its array of len entries and no two overlap:
+// the bit masks of the slots (slot1: a single slot, slot2: a pair) add up without a carry
+constexpr unsigned slot1(int s) { return 1u << s; }
+constexpr unsigned slot2(int s) { return 3u << s; }
+template <class... M>
+constexpr bool slots_apart(int len, M... m) { return (m + ...) == (m | ...) && (m | ...) < (1u << len); }
+static_assert(slots_apart(CNT_LEN, slot1(CNT_RUN), slot1(CNT_SEARCH), slot1(CNT_TICKET), slot2(CNT_LS), slot1(CNT_PC_MISS), slot2(CNT_ITER),
+                          slot1(CNT_RL), slot1(CNT_PL)), "cnt slots");
+static_assert(slots_apart(FLAG_LEN, slot1(FLAG_RUN), slot1(FLAG_SEARCH), slot2(FLAG_NRUN), slot2(FLAG_BT), slot2(FLAG_PEND), slot2(FLAG_PUB)),
+              "flags slots");
+enum EvalMode : int {  // what an evaluation launch evaluates (eval_kernel_t's int mode)
+    EVAL_POINT = 0,   // the start point / a caller's point, every world, into slot 0
+    EVAL_TRIAL = 1,   // the trial point of the searching worlds
+    EVAL_CHOSEN = 5   // the trial a speculative round chose, in full
+};
+
+// What a solve is, fixed from init_solver / upload_* / ensure_plane_cache until the next batch.
+// Every solver kernel takes it by value; what one launch does with it is the Round beside it.
 struct NlpDev {
     int W, T, NJ, O, m, R, nblk, chunk;
     // the ARMTD comparison planner (ACMP/NLPclass.cu): no torque rows (nt = 0, else NF * T),
@@ -95,7 +136,7 @@ struct NlpDev {
     // rows' Jacobian is held compactly: row (l, t, o) is J = n . dc/dx with n the winning plane's
     // signed normal, jn [2][W][T * NJ * O][3], and dc/dx the sliced link centre's derivatives,
     // jd [2][W][T][NJ][NF][3] (shared by the row's O obstacles); J keeps the other rows (and, after a
-    // start-point / caller evaluation, mode 0, the collision rows dense too). row_va expands them.
+    // start-point / caller evaluation, EVAL_POINT, the collision rows dense too). row_va expands them.
     double* g;
     double* J;
     double* jn;
@@ -111,48 +152,8 @@ struct NlpDev {
     double* partial;        // [W][nblk][KA]
     double* partial2;       // [W][nblk][KA2]: pass D
     WorldState* ws;         // [W]
-    int* flags;             // mapped host memory: [0] worlds running (round 0 of an iteration),
-                            // [1] worlds still searching after the last line-search round
-    // Active-world compaction: a solver launch covers only the worlds of list `wl` (blockIdx -> wl[b];
-    // null: every world, blockIdx = world). ipm_world_C appends the worlds still running (round 0)
-    // and still searching into wl_run / wl_search; the last block publishes the counts to flags.
-    const int* wl;
-    int* wl_run;
-    int* wl_search;
-    unsigned* cnt;          // device: [0] running, [1] searching, [2] block ticket
-    int ls0;                // this ipm_world_C launch is round 0 of an iteration
-    // rounds launched without a host synchronisation: grids sized by an upper bound, the list's
-    // true length in device memory (lcount; null: the grid is exact); ipm_world_C stores the length
-    // of the list it appends to into lcount_out
-    const unsigned* lcount;
-    unsigned* lcount_out;
-    // sync-free tail iterations (few worlds running): ipm_world_C of round 0 also stores the running
-    // count into lrun_out (device, read as the next iteration's lcount) and nrun_flag (mapped host
-    // memory, read by the host one iteration later)
-    unsigned* lrun_out;
-    int* nrun_flag;
-    int* bt_flag;           // mapped host: worlds of this iteration that searched past round 0
-    // Speculative line-search round: the values (g, f) of the remaining K = max_ls - 1 trial points
-    // of every world still searching after round 0, [list entry i][trial k] (eval_trials_kernel,
-    // ipm_world_Cs); the trial that ends the search is then evaluated in full into the world's trial
-    // slot (eval_kernel_t mode 5).
-    int K;
-    double *gs, *fs, *partial_s;
-    // sync-free tail, one-round line search (planner.hip run_solver): pass B's world step runs in
-    // ipm_world_Cs_all; the trial passes before it take the first step from pass B's partials
-    // (pass_b_alpha) and every running world searches
-    int b_in_cs;
-    // restoration launches: the trial and full evaluations take the worlds in the restoration
-    // phase (status WS_RESTO) instead of the searching ones
-    int resto;
-    int rflag;              // mapped host flag that resto_world_G's count goes to
-    // restoration phases inside the interior-point loop (planner.hip ipm_loop): a world whose line
-    // search fails is appended here (cnt[12]), and so is every world resto_world_Vs keeps in its
-    // phase; resto_publish moves the list into the next phase iteration's (null: phases run after
-    // the loop, run_resto). pend_flag: mapped host flag the round's last world kernel stores the
-    // list's length into (the host's view of pending phase work)
-    int* rl_app;
-    int* pend_flag;
+    int* flags;             // mapped host memory, [FLAG_LEN] (FlagSlot): kernels store counts, the host reads them
+    unsigned* cnt;          // device counters, [CNT_LEN] (CntSlot)
     // Certified plane cache (plane_cache_kernel). The 36 planes of a buffered
     // obstacle and their offsets d, delta do not depend on x; only A . c(x) does. For every
     // (world, t, link, obstacle) the cache holds the planes that can attain the maximum for some x in
@@ -176,13 +177,51 @@ struct NlpDev {
     // sizes; a world's own extents come from shape_of<true>.
     const int* Ow;
 };
+
+// What one launch does: the planner builds one per launch family (planner.hip, the round_*
+// functions) and passes it beside the NlpDev. Round{} is a launch over every world (blockIdx =
+// world) that appends to no list, publishes no count and is no restoration launch.
+struct Round {
+    // Active-world compaction: the launch covers the worlds of list wl (blockIdx -> wl[b]). The
+    // world kernels append the worlds still running (round 0, ls0) into wl_run and those still
+    // searching into wl_search; the last block publishes the counts (FLAG_RUN, FLAG_SEARCH).
+    // Launched without a host synchronisation: the grid is an upper bound, the list's true length
+    // is *lcount (null: the grid is exact); ipm_world_C stores wl_search's length into lcount_out.
+    // (wl and lcount come first: Round{wl, lcount} is a launch over a list and nothing else.)
+    const int* wl = nullptr;
+    const unsigned* lcount = nullptr;
+    int *wl_run = nullptr, *wl_search = nullptr;
+    int ls0 = 0;                      // this ipm_world_C launch is round 0 of an iteration
+    unsigned* lcount_out = nullptr;
+    // sync-free iterations: round 0 also stores the running count into lrun_out (the next
+    // iteration's lcount) and nrun_flag, and the worlds that searched past round 0 into bt_flag
+    // (both mapped host memory, read by the host one iteration later)
+    unsigned* lrun_out = nullptr;
+    int *nrun_flag = nullptr, *bt_flag = nullptr;
+    // Speculative rows: the values (g, f) of K trial points of every listed world, [list entry i]
+    // [trial k], and their row sums (eval_trials_*, ipm_rows_Cs / resto_rows_Vs, the *_Cs / _Vs world
+    // kernels); the chosen trial is then evaluated in full (EVAL_CHOSEN). The view is the planner's
+    // buffers, shifted for a phase iteration that runs beside the tail (planner.hip spec_view).
+    int K = 0;
+    double *gs = nullptr, *fs = nullptr, *partial_s = nullptr;
+    // the tail's one-round search: pass B's world step runs in ipm_world_Cs_all, the trial passes
+    // before it take the first step from pass B's partials (pass_b_alpha), every running world searches
+    int b_in_cs = 0;
+    // restoration launch: the evaluations take the worlds in the phase (WS_RESTO), not the searching
+    // ones; rflag: the FlagSlot resto_world_G's count of them goes to (-1: none)
+    int resto = 0, rflag = -1;
+    // phases inside the interior-point loop: a world whose line search fails, and every world
+    // resto_world_Vs keeps, is appended to rl_app (CNT_RL; null: phases run after the loop);
+    // pend_flag: mapped host flag the round's last world kernel stores that list's length into
+    int *rl_app = nullptr, *pend_flag = nullptr;
+};
 constexpr int EV_MAXK = 9;   // speculative trials per world (max_ls - 1)
 constexpr int PC_K = 12;               // initial pool: records per pair per block (ARMOUR_PC_K; the survey workload keeps 5.3)
 constexpr double PC_XBOX = 1.0 + 1e-6; // certified box of x (the solver keeps |x_i| <= 1)
 constexpr double PC_RADF = 1.0001;     // >= PC_XBOX^21, the largest monomial degree sum (7 x 3)
 constexpr double PC_MARGIN = 1e-9;     // >> the rounding of the bound and of A . c (~1e-15)
 
-AD int world_of(const NlpDev& d, int b) { return d.wl ? d.wl[b] : b; }
+AD int world_of(const Round& r, int b) { return r.wl ? r.wl[b] : b; }
 
 AD long gidx(const NlpDev& d, int slot, int w, long r) { return ((long)slot * d.W + w) * d.m + r; }
 

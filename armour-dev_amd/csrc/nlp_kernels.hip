@@ -823,8 +823,8 @@ __device__ __attribute__((always_inline)) void pair_max(unsigned long long* key,
 }
 
 // ------------------------------------------------------------------------------------------
-// g(x) and dense Jacobian, grid (T, W). mode 0: ws.x into slot 0 (start point,
-// armour_eval_constraints); mode 1: the line-search trial ws.xt into the non-current slot (worlds
+// g(x) and dense Jacobian, grid (T, W). EVAL_POINT: ws.x into slot 0 (start point,
+// armour_eval_constraints); EVAL_TRIAL: the line-search trial ws.xt into the non-current slot (worlds
 // still searching only). The sliced link centres go to the slot's own region (feasible_kernel
 // copies the current slot's, the final iterate's, out).
 // ARMTD selects the comparison planner's extrema and cost at compile time: a call into them from
@@ -845,25 +845,25 @@ __host__ __device__ constexpr int eval_pair_doubles(int np) { return np + (np + 
 // MX (a mixed batch, fp64 ARMOUR only): the world's own obstacle count O decides its rows; the
 // obstacle, jn and pcoff slabs keep the batch's strides (OS)
 template <typename R, bool ARMTD, bool CACHED, int LM, int UM, int UB, bool MX = false>
-__device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mode) {
+__device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, const Round& r, int mode) {
     static_assert(!CACHED || std::is_same<R, double>::value, "the plane cache is fp64");
     static_assert(!MX || (std::is_same<R, double>::value && !ARMTD), "mixed batches: the fp64 ARMOUR planner");
-    // mode 5: the trial point the speculative round chose (ipm_world_Cs: spec_k >= 0), in full,
+    // EVAL_CHOSEN: the trial point the speculative round chose (ipm_world_Cs: spec_k >= 0), in full,
     // into the world's trial slot (list entries, blockIdx.y -> wl)
-    if ((mode == 1 || mode == 5) && d.lcount && blockIdx.y >= *d.lcount) return;
-    const int t = blockIdx.x, w = world_of(d, blockIdx.y);
+    if ((mode == EVAL_TRIAL || mode == EVAL_CHOSEN) && r.lcount && blockIdx.y >= *r.lcount) return;
+    const int t = blockIdx.x, w = world_of(r, blockIdx.y);
     WorldState& S = d.ws[w];
-    // (restoration launches, d.resto: the worlds in the restoration phase, WS_RESTO)
-    if (mode == 1 && !((d.resto ? S.status == WS_RESTO : S.status == 0) && S.searching)) return;
-    if (mode == 5 && !(d.resto ? (S.status == WS_RESTO && S.rpend) : (S.status == 0 && S.spec_k >= 0))) return;
+    // (restoration launches, r.resto: the worlds in the restoration phase, WS_RESTO)
+    if (mode == EVAL_TRIAL && !((r.resto ? S.status == WS_RESTO : S.status == 0) && S.searching)) return;
+    if (mode == EVAL_CHOSEN && !(r.resto ? (S.status == WS_RESTO && S.rpend) : (S.status == 0 && S.spec_k >= 0))) return;
     EVP_DECL EVP_MARK
-    const int slot = mode == 0 ? 0 : 1 - S.cur;
+    const int slot = mode == EVAL_POINT ? 0 : 1 - S.cur;
     double* const Gb = d.g + gidx(d, slot, w, 0);
     double* const Jb = d.J + gidx(d, slot, w, 0) * NF;
     double* const Lcb = d.link_c + slot * d.lcs + (long)w * d.T * d.NJ * 3;
     double* const fb = d.f + slot * d.W + w;
     double* const gradb = d.grad + ((long)slot * d.W + w) * NF;
-    // compact collision Jacobian (NlpDev::jn / jd); mode 0 also writes those rows densely into Jb
+    // compact collision Jacobian (NlpDev::jn / jd); EVAL_POINT also writes those rows densely into Jb
     const long ncol = (long)d.T * d.NJ * d.O;
     double* const Jnb = d.jn + slot * d.njn + (long)w * ncol * 3;
     double* const Jdb = d.jd + slot * d.njd + (long)w * d.T * d.NJ * NF * 3;
@@ -895,7 +895,7 @@ __device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mo
     __shared__ int lcnt[MAX_J], tcnt[NF];
     __shared__ R ptab[NF][8];
     if (tid < NF) {
-        const double xd = mode == 0 ? S.x[tid] : S.xt[tid];
+        const double xd = mode == EVAL_POINT ? S.x[tid] : S.xt[tid];
         x[tid] = xd;
         const R xj = (R)xd;
         power_table(xj, ptab[tid]);
@@ -1007,7 +1007,7 @@ __device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mo
         if (coll && !inbox) {
             for (int pr = tid; pr < NJ * O; pr += blockDim.x)
                 Gb[nt + ((long)(pr / O) * d.T + t) * O + pr % O] = __builtin_nan("");
-            if (tid == 0) atomicAdd(d.cnt + 7, 1u);
+            if (tid == 0) atomicAdd(d.cnt + CNT_PC_MISS, 1u);
         } else if (coll) {
             // Record-parallel scan. Every thread takes records q = tid, tid + 256, ... of the block's
             // kept planes straight from global memory and forms both candidates, A . c - P before
@@ -1115,7 +1115,7 @@ __device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mo
                 jn[0] = isneg ? B0 : -B0;
                 jn[1] = isneg ? B1 : -B1;
                 jn[2] = isneg ? B2 : -B2;
-                if (mode == 0) {
+                if (mode == EVAL_POINT) {
 #pragma unroll
                     for (int kk = 0; kk < NF; kk++) {
                         const double dot = B0 * dlc[l][kk][0] + B1 * dlc[l][kk][1] + B2 * dlc[l][kk][2];
@@ -1249,7 +1249,7 @@ __device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mo
         jn[0] = isneg ? B0 : -B0;
         jn[1] = isneg ? B1 : -B1;
         jn[2] = isneg ? B2 : -B2;
-        if (mode == 0) {
+        if (mode == EVAL_POINT) {
 #pragma unroll
             for (int k = 0; k < NF; k++) {
                 const R dot = B0 * dlc[l][k][0] + B1 * dlc[l][k][1] + B2 * dlc[l][k][2];
@@ -1265,35 +1265,35 @@ __device__ __attribute__((always_inline)) void eval_body(const NlpDev& d, int mo
 // (ARMOUR_EVAL_F32, tools/fp32_study.py): reach sets stay fp64, the slicing and collision
 // arithmetic runs in float
 template <typename R, bool ARMTD, bool CACHED>
-__global__ __launch_bounds__(EVAL_THREADS) void eval_kernel_t(NlpDev d, int mode) {
-    eval_body<R, ARMTD, CACHED, CAP_LM, CAP_UM, UB_FULL>(d, mode);
+__global__ __launch_bounds__(EVAL_THREADS) void eval_kernel_t(NlpDev d, Round r, int mode) {
+    eval_body<R, ARMTD, CACHED, CAP_LM, CAP_UM, UB_FULL>(d, r, mode);
 }
-__global__ __launch_bounds__(EVAL_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void eval_kernel_small(NlpDev d, int mode) {
-    eval_body<double, false, true, LM_S, UM_S, UB_S>(d, mode);
+__global__ __launch_bounds__(EVAL_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void eval_kernel_small(NlpDev d, Round r, int mode) {
+    eval_body<double, false, true, LM_S, UM_S, UB_S>(d, r, mode);
 }
-template __global__ void eval_kernel_t<double, false, false>(NlpDev, int);
-template __global__ void eval_kernel_t<float, false, false>(NlpDev, int);
-template __global__ void eval_kernel_t<double, true, false>(NlpDev, int);
-template __global__ void eval_kernel_t<float, true, false>(NlpDev, int);
-template __global__ void eval_kernel_t<double, false, true>(NlpDev, int);
-template __global__ void eval_kernel_t<double, true, true>(NlpDev, int);
+template __global__ void eval_kernel_t<double, false, false>(NlpDev, Round, int);
+template __global__ void eval_kernel_t<float, false, false>(NlpDev, Round, int);
+template __global__ void eval_kernel_t<double, true, false>(NlpDev, Round, int);
+template __global__ void eval_kernel_t<float, true, false>(NlpDev, Round, int);
+template __global__ void eval_kernel_t<double, false, true>(NlpDev, Round, int);
+template __global__ void eval_kernel_t<double, true, true>(NlpDev, Round, int);
 // the mixed-batch instantiations (fp64 ARMOUR planner; full scan or plane cache, and the small form)
 template <bool CACHED>
-__global__ __launch_bounds__(EVAL_THREADS) void eval_kernel_mx(NlpDev d, int mode) {
-    eval_body<double, false, CACHED, CAP_LM, CAP_UM, UB_FULL, true>(d, mode);
+__global__ __launch_bounds__(EVAL_THREADS) void eval_kernel_mx(NlpDev d, Round r, int mode) {
+    eval_body<double, false, CACHED, CAP_LM, CAP_UM, UB_FULL, true>(d, r, mode);
 }
-__global__ __launch_bounds__(EVAL_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void eval_kernel_small_mx(NlpDev d, int mode) {
-    eval_body<double, false, true, LM_S, UM_S, UB_S, true>(d, mode);
+__global__ __launch_bounds__(EVAL_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void eval_kernel_small_mx(NlpDev d, Round r, int mode) {
+    eval_body<double, false, true, LM_S, UM_S, UB_S, true>(d, r, mode);
 }
-template __global__ void eval_kernel_mx<false>(NlpDev, int);
-template __global__ void eval_kernel_mx<true>(NlpDev, int);
+template __global__ void eval_kernel_mx<false>(NlpDev, Round, int);
+template __global__ void eval_kernel_mx<true>(NlpDev, Round, int);
 
 // ------------------------------------------------------------------------------------------
 // Speculative line-search round, values only. Block (t, list entry i) evaluates the K = max_ls - 1
 // remaining trial points of world wl[i] (alpha halved k times from the round's alpha: the points
 // ipm_world_C's sequential rounds would visit) — the constraint values and the cost, all the
 // acceptance test reads (ipm_rows_Cs / ipm_world_Cs); the Jacobian is formed only for the trial
-// chosen, by a full evaluation (eval_kernel_t mode 5). The monomials are staged and each
+// chosen, by a full evaluation (eval_kernel_t EVAL_CHOSEN). The monomials are staged and each
 // certified-plane record is loaded once for all K points; every value is formed by the functions
 // eval_body forms it with (sum4 over value_term, extremum_rows, traj_cost, record_candidate).
 // LM, UM, UB as eval_body; the staging buffer then holds the (trial, pair) keys, K * NP <= UB
@@ -1303,15 +1303,15 @@ template <bool MX>
 __device__ inline double pass_b_alpha(const NlpDev& d, int w);
 // MX (a mixed batch): the world's own O and NP; the trial slots gs and pcoff keep the batch's strides
 template <int LM, int UM, int UB, int KM = EV_MAXK, bool MX = false>
-__device__ __attribute__((always_inline)) void eval_trials_body(const NlpDev& d) {
-    if (d.lcount && blockIdx.y >= *d.lcount) return;
-    const int t = blockIdx.x, i = blockIdx.y, w = d.wl[i];
+__device__ __attribute__((always_inline)) void eval_trials_body(const NlpDev& d, const Round& r) {
+    if (r.lcount && blockIdx.y >= *r.lcount) return;
+    const int t = blockIdx.x, i = blockIdx.y, w = r.wl[i];
     const WorldState& S = d.ws[w];
-    // (restoration launches, d.resto: the trials of the phase's Armijo search)
-    if (!(d.resto ? (S.status == WS_RESTO && S.searching) : (S.status == 0 && (d.b_in_cs || S.searching)))) return;
+    // (restoration launches, r.resto: the trials of the phase's Armijo search)
+    if (!(r.resto ? (S.status == WS_RESTO && S.searching) : (S.status == 0 && (r.b_in_cs || S.searching)))) return;
     EVP_DECL EVP_MARK
     const RobotParams& rp = *d.rp;
-    const int tid = threadIdx.x, K = d.K;
+    const int tid = threadIdx.x, K = r.K;
     const long jt = (long)w * d.T + t;
     const int NJ = d.NJ, O = shape_of<MX>(d, w).O, NP = NJ * O;
     const long nt = d.nt;
@@ -1327,7 +1327,7 @@ __device__ __attribute__((always_inline)) void eval_trials_body(const NlpDev& d)
     auto tco = reinterpret_cast<double (*)[UM]>(ubuf + MAX_J * LM * 3);
     if (tid < K * NF) {
         const int kk = tid / NF, j = tid % NF;
-        double a = d.b_in_cs ? pass_b_alpha<MX>(d, w) : S.alpha;
+        double a = r.b_in_cs ? pass_b_alpha<MX>(d, w) : S.alpha;
         for (int q = 0; q < kk; q++) a *= 0.5;
         const double xj = S.x[j] + a * S.dx[j];
         xk[kk][j] = xj;
@@ -1353,7 +1353,7 @@ __device__ __attribute__((always_inline)) void eval_trials_body(const NlpDev& d)
             const int v = u - nlv, kk = v / NF, j = v % NF;
             const long base = jt * NF + j;
             const double c = sum4(d.ro.tq_center[base], tcnt[j], [&](int q) { return value_term(tco[j][q], th[j][q], ptab[kk]); });
-            d.gs[((long)i * K + kk) * d.m + (long)t * NF + j] = interval_mid(c, d.ro.tq_rad[base]);
+            r.gs[((long)i * K + kk) * d.m + (long)t * NF + j] = interval_mid(c, d.ro.tq_rad[base]);
         }
     }
     // extremum rows (NLPclass.cu:319-320, 390-391) and cost (NLPclass.cu:207-267) of every trial:
@@ -1364,7 +1364,7 @@ __device__ __attribute__((always_inline)) void eval_trials_body(const NlpDev& d)
     for (int v = t; v <= 2 * NF && tid >= (int)blockDim.x - K; v += d.T) {
         const int kk = tid - ((int)blockDim.x - K);
         const double* x = xk[kk];
-        double* const Gb = d.gs + ((long)i * K + kk) * d.m;
+        double* const Gb = r.gs + ((long)i * K + kk) * d.m;
         const TrajStart ts = traj_start(d, w);
         if (v < 2 * NF) {
             const long off2 = (long)NF * d.T + (long)d.T * d.NJ * O;
@@ -1376,7 +1376,7 @@ __device__ __attribute__((always_inline)) void eval_trials_body(const NlpDev& d)
             continue;
         }
         double qp[NF];
-        d.fs[(long)i * K + kk] = traj_cost(d, rp, ts, w, x, qp) * rp.cost_scale;
+        r.fs[(long)i * K + kk] = traj_cost(d, rp, ts, w, x, qp) * rp.cost_scale;
     }
     __syncthreads();
     EVP_MARK
@@ -1406,31 +1406,31 @@ __device__ __attribute__((always_inline)) void eval_trials_body(const NlpDev& d)
     for (int u = tid; u < K * NP; u += blockDim.x) {
         const int kk = u / NP, pr = u - kk * NP;
         const int l = pr / O, o = pr % O;
-        d.gs[((long)i * K + kk) * d.m + nt + ((long)l * d.T + t) * O + o] = -dkey(pkey[u]);
+        r.gs[((long)i * K + kk) * d.m + nt + ((long)l * d.T + t) * O + o] = -dkey(pkey[u]);
     }
     EVP_PRINT("TR")
 }
-__global__ __launch_bounds__(EVAL_THREADS) void eval_trials_kernel(NlpDev d) { eval_trials_body<CAP_LM, CAP_UM, UB_FULL>(d); }
-__global__ __launch_bounds__(EVAL_THREADS) void eval_trials_kernel_mx(NlpDev d) {
-    eval_trials_body<CAP_LM, CAP_UM, UB_FULL, EV_MAXK, true>(d);
+__global__ __launch_bounds__(EVAL_THREADS) void eval_trials_kernel(NlpDev d, Round r) { eval_trials_body<CAP_LM, CAP_UM, UB_FULL>(d, r); }
+__global__ __launch_bounds__(EVAL_THREADS) void eval_trials_kernel_mx(NlpDev d, Round r) {
+    eval_trials_body<CAP_LM, CAP_UM, UB_FULL, EV_MAXK, true>(d, r);
 }
 // the sync-free tail's single line-search round: all max_ls trials (K = EV_MAXK + 1) of the few
 // running worlds, round 0's trial included (ipm_world_Cs_all); K * NJ * O <= UB_FULL (host check)
-__global__ __launch_bounds__(EVAL_THREADS) void eval_trials_all(NlpDev d) { eval_trials_body<CAP_LM, CAP_UM, UB_FULL, EV_MAXK + 1>(d); }
-__global__ __launch_bounds__(EVAL_THREADS) void eval_trials_all_mx(NlpDev d) {
-    eval_trials_body<CAP_LM, CAP_UM, UB_FULL, EV_MAXK + 1, true>(d);
+__global__ __launch_bounds__(EVAL_THREADS) void eval_trials_all(NlpDev d, Round r) { eval_trials_body<CAP_LM, CAP_UM, UB_FULL, EV_MAXK + 1>(d, r); }
+__global__ __launch_bounds__(EVAL_THREADS) void eval_trials_all_mx(NlpDev d, Round r) {
+    eval_trials_body<CAP_LM, CAP_UM, UB_FULL, EV_MAXK + 1, true>(d, r);
 }
 // five waves per SIMD (91 VGPRs): six measured slower (5.5 -> 5.7 ms per solve)
-__global__ __launch_bounds__(EVAL_THREADS) __attribute__((amdgpu_waves_per_eu(5, 5))) void eval_trials_small(NlpDev d) {
-    eval_trials_body<LM_S, UM_S, UB_TS>(d);
+__global__ __launch_bounds__(EVAL_THREADS) __attribute__((amdgpu_waves_per_eu(5, 5))) void eval_trials_small(NlpDev d, Round r) {
+    eval_trials_body<LM_S, UM_S, UB_TS>(d, r);
 }
-__global__ __launch_bounds__(EVAL_THREADS) __attribute__((amdgpu_waves_per_eu(5, 5))) void eval_trials_small_mx(NlpDev d) {
-    eval_trials_body<LM_S, UM_S, UB_TS, EV_MAXK, true>(d);
+__global__ __launch_bounds__(EVAL_THREADS) __attribute__((amdgpu_waves_per_eu(5, 5))) void eval_trials_small_mx(NlpDev d, Round r) {
+    eval_trials_body<LM_S, UM_S, UB_TS, EV_MAXK, true>(d, r);
 }
 
 // ------------------------------------------------------------------------------------------
 // armour-IPM
-__global__ __launch_bounds__(64) void ipm_world_init(NlpDev d) {
+__global__ __launch_bounds__(64) void ipm_world_init(NlpDev d, Round r) {
     const int w = blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= d.W) return;
     WorldState& S = d.ws[w];
@@ -1448,8 +1448,8 @@ __global__ __launch_bounds__(64) void ipm_world_init(NlpDev d) {
     S.nfilt = 0;
     S.cur = 0;
     S.status = d.ro.err[w] ? 4 : 0;  // 4: reach set over capacity (planner.hip run_reach), not planned
-    d.wl_run[w] = w;                 // the first iteration covers every world
-    if (w == 0) { d.cnt[0] = 0; d.cnt[1] = 0; d.cnt[2] = 0; }
+    r.wl_run[w] = w;                 // the first iteration covers every world
+    if (w == 0) { d.cnt[CNT_RUN] = 0; d.cnt[CNT_SEARCH] = 0; d.cnt[CNT_TICKET] = 0; }
     S.searching = 0;
     S.first_update = 1;
     S.nfail = 0;
@@ -1465,8 +1465,8 @@ __global__ __launch_bounds__(64) void ipm_world_init(NlpDev d) {
 }
 
 template <bool MX>
-__device__ __attribute__((always_inline)) void ipm_rows_init_body(const NlpDev& d) {
-    const int w = world_of(d, blockIdx.y);  // every world, or the list restarted by a restoration phase
+__device__ __attribute__((always_inline)) void ipm_rows_init_body(const NlpDev& d, const Round& r) {
+    const int w = world_of(r, blockIdx.y);  // every world, or the list restarted by a restoration phase
     const Shape sh = shape_of<MX>(d, w);
     if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
     const WorldState& S = d.ws[w];
@@ -1495,8 +1495,8 @@ __device__ __attribute__((always_inline)) void ipm_rows_init_body(const NlpDev& 
         }
     }
 }
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_init(NlpDev d) { ipm_rows_init_body<false>(d); }
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_init_mx(NlpDev d) { ipm_rows_init_body<true>(d); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_init(NlpDev d, Round r) { ipm_rows_init_body<false>(d, r); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_init_mx(NlpDev d, Round r) { ipm_rows_init_body<true>(d, r); }
 
 // pass A: residuals, errors, reduced Newton system sums
 // pass A's row accumulation (residuals, Newton system) at the current point: value v, gradient a
@@ -1614,8 +1614,8 @@ __device__ inline __attribute__((always_inline)) void row_D(const NlpDev& d, lon
 }
 
 template <bool MX>
-__device__ __attribute__((always_inline)) void ipm_rows_A_body(const NlpDev& d) {
-    const int w = world_of(d, blockIdx.y);
+__device__ __attribute__((always_inline)) void ipm_rows_A_body(const NlpDev& d, const Round& r) {
+    const int w = world_of(r, blockIdx.y);
     const Shape sh = shape_of<MX>(d, w);
     if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
     const WorldState& S = d.ws[w];
@@ -1635,8 +1635,8 @@ __device__ __attribute__((always_inline)) void ipm_rows_A_body(const NlpDev& d) 
     }
     reduce_A(d, w, c, lds);
 }
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_A(NlpDev d) { ipm_rows_A_body<false>(d); }
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_A_mx(NlpDev d) { ipm_rows_A_body<true>(d); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_A(NlpDev d, Round r) { ipm_rows_A_body<false>(d, r); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_A_mx(NlpDev d, Round r) { ipm_rows_A_body<true>(d, r); }
 
 // passes D (of the previous iteration) and A (of this one) in one sweep over the rows: the trial
 // point D accepts is the point A works at, so each row's value and gradient are read once; the
@@ -1648,9 +1648,9 @@ __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_A_mx(NlpDev d) { ipm_row
 // grids below four blocks per CU keep the register form (planner.hip ipm_loop)
 constexpr int DA_ML = 20;
 template <int ML, bool MX = false>
-__device__ __attribute__((always_inline)) void rows_DA_body(const NlpDev& d) {
-    if (d.lcount && blockIdx.y >= *d.lcount) return;
-    const int w = world_of(d, blockIdx.y);
+__device__ __attribute__((always_inline)) void rows_DA_body(const NlpDev& d, const Round& r) {
+    if (r.lcount && blockIdx.y >= *r.lcount) return;
+    const int w = world_of(r, blockIdx.y);
     const Shape sh = shape_of<MX>(d, w);
     if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
     const WorldState& S = d.ws[w];
@@ -1708,10 +1708,10 @@ __device__ __attribute__((always_inline)) void rows_DA_body(const NlpDev& d) {
     __syncthreads();
     reduce_A<ML>(d, w, c, lds, ml);
 }
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_DA(NlpDev d) { rows_DA_body<0>(d); }
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_DA_lds(NlpDev d) { rows_DA_body<DA_ML>(d); }
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_DA_mx(NlpDev d) { rows_DA_body<0, true>(d); }
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_DA_lds_mx(NlpDev d) { rows_DA_body<DA_ML, true>(d); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_DA(NlpDev d, Round r) { rows_DA_body<0>(d, r); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_DA_lds(NlpDev d, Round r) { rows_DA_body<DA_ML>(d, r); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_DA_mx(NlpDev d, Round r) { rows_DA_body<0, true>(d, r); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_DA_lds_mx(NlpDev d, Round r) { rows_DA_body<DA_ML, true>(d, r); }
 
 __device__ bool chol_solve7(const double* M, double shift, const double* b, double* x) {
     double L[NF * NF];
@@ -1818,8 +1818,8 @@ __device__ inline void ws_copy(WorldState& dst, const WorldState& src) {
     for (int k = threadIdx.x; k < (int)(sizeof(WorldState) / 8); k += blockDim.x) t[k] = s[k];
 }
 template <bool MX>
-__device__ __attribute__((always_inline)) void ipm_world_A_body(const NlpDev& d, int nside) {
-    const int w = world_of(d, blockIdx.x);
+__device__ __attribute__((always_inline)) void ipm_world_A_body(const NlpDev& d, const Round& r, int nside) {
+    const int w = world_of(r, blockIdx.x);
     __shared__ WorldState S;
     ws_copy(S, d.ws[w]);
     __syncthreads();
@@ -1828,8 +1828,8 @@ __device__ __attribute__((always_inline)) void ipm_world_A_body(const NlpDev& d,
     __syncthreads();
     if (act) ws_copy(d.ws[w], S);
 }
-__global__ __launch_bounds__(64) void ipm_world_A(NlpDev d, int nside) { ipm_world_A_body<false>(d, nside); }
-__global__ __launch_bounds__(64) void ipm_world_A_mx(NlpDev d, int nside) { ipm_world_A_body<true>(d, nside); }
+__global__ __launch_bounds__(64) void ipm_world_A(NlpDev d, Round r, int nside) { ipm_world_A_body<false>(d, r, nside); }
+__global__ __launch_bounds__(64) void ipm_world_A_mx(NlpDev d, Round r, int nside) { ipm_world_A_body<true>(d, r, nside); }
 // pass A's world step: convergence test, barrier update, Newton step; every lane of the wave calls it.
 // nside: the finite constraint sides of a world, a batch constant from the host (planner.hip
 // nside_count); a mixed batch's world counts its own: torque 2 per row, collision 1, extrema 2,
@@ -1924,9 +1924,9 @@ __device__ inline void world_A_body(const NlpDev& d, WorldState& S, int w, int n
 // SIMD (128 VGPRs, 2 spilled): 3.66 ms per 327-world solve against 3.95 at three. ipm_rows_DA held
 // to three spills 32 registers and slows from 6.5 to 7.9 ms, so it stays at two.
 template <bool MX>
-__device__ __attribute__((always_inline)) void ipm_rows_B_body(const NlpDev& d) {
-    if (d.lcount && blockIdx.y >= *d.lcount) return;
-    const int w = world_of(d, blockIdx.y);
+__device__ __attribute__((always_inline)) void ipm_rows_B_body(const NlpDev& d, const Round& r) {
+    if (r.lcount && blockIdx.y >= *r.lcount) return;
+    const int w = world_of(r, blockIdx.y);
     const Shape sh = shape_of<MX>(d, w);
     if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
     const WorldState& S = d.ws[w];
@@ -1989,8 +1989,8 @@ __device__ __attribute__((always_inline)) void ipm_rows_B_body(const NlpDev& d) 
     for (int k = 0; k < 19; k++) kinds[k] = k < 2 ? 2 : 0;
     block_reduce_n(v, kinds, lds, out);
 }
-__global__ __launch_bounds__(ROW_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void ipm_rows_B(NlpDev d) { ipm_rows_B_body<false>(d); }
-__global__ __launch_bounds__(ROW_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void ipm_rows_B_mx(NlpDev d) { ipm_rows_B_body<true>(d); }
+__global__ __launch_bounds__(ROW_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void ipm_rows_B(NlpDev d, Round r) { ipm_rows_B_body<false>(d, r); }
+__global__ __launch_bounds__(ROW_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void ipm_rows_B_mx(NlpDev d, Round r) { ipm_rows_B_body<true>(d, r); }
 
 // pass B's world step: step sizes, line-search ingredients, the first trial point (every lane of
 // the wave calls it; ipm_world_B, or ipm_world_Cs_all in the sync-free tail)
@@ -2025,9 +2025,9 @@ __device__ inline void world_B_body(const NlpDev& d, WorldState& S, int w) {
     S.accepted_ok = 0;
 }
 template <bool MX>
-__device__ __attribute__((always_inline)) void ipm_world_B_body(const NlpDev& d) {
-    if (d.lcount && blockIdx.x >= *d.lcount) return;
-    const int w = world_of(d, blockIdx.x);
+__device__ __attribute__((always_inline)) void ipm_world_B_body(const NlpDev& d, const Round& r) {
+    if (r.lcount && blockIdx.x >= *r.lcount) return;
+    const int w = world_of(r, blockIdx.x);
     __shared__ WorldState S;
     ws_copy(S, d.ws[w]);
     __syncthreads();
@@ -2036,8 +2036,8 @@ __device__ __attribute__((always_inline)) void ipm_world_B_body(const NlpDev& d)
     __syncthreads();
     if (act) ws_copy(d.ws[w], S);
 }
-__global__ __launch_bounds__(64) void ipm_world_B(NlpDev d) { ipm_world_B_body<false>(d); }
-__global__ __launch_bounds__(64) void ipm_world_B_mx(NlpDev d) { ipm_world_B_body<true>(d); }
+__global__ __launch_bounds__(64) void ipm_world_B(NlpDev d, Round r) { ipm_world_B_body<false>(d, r); }
+__global__ __launch_bounds__(64) void ipm_world_B_mx(NlpDev d, Round r) { ipm_world_B_body<true>(d, r); }
 // the first trial's step alpha = S.ap as world_B_body forms it: pass B's block partials of the
 // primal fraction to the boundary, min onto 1 in block order (world_partials' arithmetic), for the
 // tail's trial passes that run before the world step (NlpDev::b_in_cs)
@@ -2059,9 +2059,9 @@ __device__ inline double pass_b_alpha(const NlpDev& d, int w) {
 
 // pass C: barrier objective and constraint violation at the trial point
 template <bool MX>
-__device__ __attribute__((always_inline)) void ipm_rows_C_body(const NlpDev& d) {
-    if (d.lcount && blockIdx.y >= *d.lcount) return;
-    const int w = world_of(d, blockIdx.y);
+__device__ __attribute__((always_inline)) void ipm_rows_C_body(const NlpDev& d, const Round& r) {
+    if (r.lcount && blockIdx.y >= *r.lcount) return;
+    const int w = world_of(r, blockIdx.y);
     const Shape sh = shape_of<MX>(d, w);
     if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
     const WorldState& S = d.ws[w];
@@ -2085,10 +2085,10 @@ __device__ __attribute__((always_inline)) void ipm_rows_C_body(const NlpDev& d) 
     const int kinds[2] = {0, 0};
     block_reduce_n(v, kinds, lds, out);
 }
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_C(NlpDev d) { ipm_rows_C_body<false>(d); }
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_C_mx(NlpDev d) { ipm_rows_C_body<true>(d); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_C(NlpDev d, Round r) { ipm_rows_C_body<false>(d, r); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_C_mx(NlpDev d, Round r) { ipm_rows_C_body<true>(d, r); }
 
-__device__ inline void accept_trial(const NlpDev& d, WorldState& S, double logt, double rpt, double ft, bool filt, int w);
+__device__ inline void accept_trial(const NlpDev& d, const Round& r, WorldState& S, double logt, double rpt, double ft, bool filt, int w);
 // the filter test of a trial (theta_t, phi_t) on a whole wave, one filter entry per lane
 // (MAX_FILTER <= 64): acceptable to the filter iff no entry dominates it
 __device__ inline bool filter_pass(const WorldState& S, double thetat, double phit) {
@@ -2097,7 +2097,7 @@ __device__ inline bool filter_pass(const WorldState& S, double thetat, double ph
     return __ballot(fail) == 0;
 }
 template <bool MX>
-__device__ inline void world_C_body(const NlpDev& d, WorldState& S, int w) {
+__device__ inline void world_C_body(const NlpDev& d, const Round& r, WorldState& S, int w) {
     if (!(S.status == 0 && S.searching)) return;
     double P[2];
     const double init[2] = {0.0, 0.0};
@@ -2106,12 +2106,12 @@ __device__ inline void world_C_body(const NlpDev& d, WorldState& S, int w) {
     const double ft = d.f[(1 - S.cur) * d.W + w];
     const bool filt = filter_pass(S, P[1], ft - S.mu * P[0]);
     if (threadIdx.x != 0) return;
-    accept_trial(d, S, P[0], P[1], ft, filt, w);
+    accept_trial(d, r, S, P[0], P[1], ft, filt, w);
 }
 
 // the filter acceptance test of one trial point (barrier terms logt, violation rpt, objective ft);
 // on failure the next trial (alpha halved) or, after max_ls trials, the forced last one
-__device__ inline void accept_trial(const NlpDev& d, WorldState& S, double logt, double rpt, double ft, bool filt, int w) {
+__device__ inline void accept_trial(const NlpDev& d, const Round& r, WorldState& S, double logt, double rpt, double ft, bool filt, int w) {
     S.nevals++;
     const double phit = ft - S.mu * logt, thetat = rpt;
     bool ok = thetat <= S.theta_max && filt;  // filt: filter_pass of (thetat, phit)
@@ -2149,7 +2149,7 @@ __device__ inline void accept_trial(const NlpDev& d, WorldState& S, double logt,
             S.rphi = -1;
             S.rstall = 0;
             S.rpend = 0;
-            if (d.rl_app) d.rl_app[atomicAdd(&d.cnt[12], 1u)] = w;  // the loop's phase list
+            if (r.rl_app) r.rl_app[atomicAdd(&d.cnt[CNT_RL], 1u)] = w;  // the loop's phase list
         }
         return;
     }
@@ -2162,58 +2162,58 @@ __device__ inline void accept_trial(const NlpDev& d, WorldState& S, double logt,
 // decides which block serves which world), and the last block to finish publishes both counts to
 // the mapped host flags and resets the counters for the next launch.
 template <bool MX>
-__device__ __attribute__((always_inline)) void ipm_world_C_body(const NlpDev& d) {
-    const bool valid = !d.lcount || blockIdx.x < *d.lcount;
-    const int w = valid ? world_of(d, blockIdx.x) : 0;
+__device__ __attribute__((always_inline)) void ipm_world_C_body(const NlpDev& d, const Round& r) {
+    const bool valid = !r.lcount || blockIdx.x < *r.lcount;
+    const int w = valid ? world_of(r, blockIdx.x) : 0;
     __shared__ WorldState S;
     if (valid) {
         ws_copy(S, d.ws[w]);
         __syncthreads();
         const bool act = S.status == 0;
-        world_C_body<MX>(d, S, w);
+        world_C_body<MX>(d, r, S, w);
         __syncthreads();
         if (act) ws_copy(d.ws[w], S);
     }
     if (threadIdx.x != 0) return;
     if (valid && S.status == 0) {
-        if (d.ls0) d.wl_run[atomicAdd(&d.cnt[0], 1u)] = w;
-        if (S.searching) d.wl_search[atomicAdd(&d.cnt[1], 1u)] = w;
+        if (r.ls0) r.wl_run[atomicAdd(&d.cnt[CNT_RUN], 1u)] = w;
+        if (S.searching) r.wl_search[atomicAdd(&d.cnt[CNT_SEARCH], 1u)] = w;
     }
     __threadfence();
-    if (atomicAdd(&d.cnt[2], 1u) == gridDim.x - 1) {
+    if (atomicAdd(&d.cnt[CNT_TICKET], 1u) == gridDim.x - 1) {
         __threadfence();
-        const unsigned nrun = atomicAdd(&d.cnt[0], 0u), nsearch = atomicAdd(&d.cnt[1], 0u);
-        if (d.ls0) d.flags[0] = (int)nrun;
-        if (d.ls0 && d.lrun_out) *d.lrun_out = nrun;
-        if (d.ls0 && d.nrun_flag) *d.nrun_flag = (int)nrun;
-        if (d.ls0 && d.bt_flag) *d.bt_flag = (int)nsearch;
-        d.flags[1] = (int)nsearch;
-        if (d.lcount_out) *d.lcount_out = nsearch;
-        if (d.pend_flag) *d.pend_flag = (int)atomicAdd(&d.cnt[12], 0u);
-        d.cnt[0] = 0;
-        d.cnt[1] = 0;
-        d.cnt[2] = 0;
+        const unsigned nrun = atomicAdd(&d.cnt[CNT_RUN], 0u), nsearch = atomicAdd(&d.cnt[CNT_SEARCH], 0u);
+        if (r.ls0) d.flags[FLAG_RUN] = (int)nrun;
+        if (r.ls0 && r.lrun_out) *r.lrun_out = nrun;
+        if (r.ls0 && r.nrun_flag) *r.nrun_flag = (int)nrun;
+        if (r.ls0 && r.bt_flag) *r.bt_flag = (int)nsearch;
+        d.flags[FLAG_SEARCH] = (int)nsearch;
+        if (r.lcount_out) *r.lcount_out = nsearch;
+        if (r.pend_flag) *r.pend_flag = (int)atomicAdd(&d.cnt[CNT_RL], 0u);
+        d.cnt[CNT_RUN] = 0;
+        d.cnt[CNT_SEARCH] = 0;
+        d.cnt[CNT_TICKET] = 0;
     }
 }
-__global__ __launch_bounds__(64) void ipm_world_C(NlpDev d) { ipm_world_C_body<false>(d); }
-__global__ __launch_bounds__(64) void ipm_world_C_mx(NlpDev d) { ipm_world_C_body<true>(d); }
+__global__ __launch_bounds__(64) void ipm_world_C(NlpDev d, Round r) { ipm_world_C_body<false>(d, r); }
+__global__ __launch_bounds__(64) void ipm_world_C_mx(NlpDev d, Round r) { ipm_world_C_body<true>(d, r); }
 
 // Speculative line-search round (the tail: few worlds still searching after round 0). Pass C of
 // every remaining trial k = 0 .. K-1 (alpha halved k times) of list entry i, blockIdx.y = i * K + k,
 // from the trial's own slot; the arithmetic of ipm_rows_C at that trial.
 template <bool MX>
-__device__ __attribute__((always_inline)) void ipm_rows_Cs_body(const NlpDev& d) {
-    const int i = blockIdx.y / d.K, k = blockIdx.y % d.K;
-    if (d.lcount && (unsigned)i >= *d.lcount) return;
-    const int w = d.wl[i];
+__device__ __attribute__((always_inline)) void ipm_rows_Cs_body(const NlpDev& d, const Round& r) {
+    const int i = blockIdx.y / r.K, k = blockIdx.y % r.K;
+    if (r.lcount && (unsigned)i >= *r.lcount) return;
+    const int w = r.wl[i];
     const Shape sh = shape_of<MX>(d, w);
     if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
     const WorldState& S = d.ws[w];
-    if (!(S.status == 0 && (d.b_in_cs || S.searching))) return;
+    if (!(S.status == 0 && (r.b_in_cs || S.searching))) return;
     __shared__ double lds[(ROW_THREADS / 64) * NA];
-    double alpha = d.b_in_cs ? pass_b_alpha<MX>(d, w) : S.alpha;
+    double alpha = r.b_in_cs ? pass_b_alpha<MX>(d, w) : S.alpha;
     for (int q = 0; q < k; q++) alpha *= 0.5;
-    const double* G = d.gs + (long)blockIdx.y * d.m;
+    const double* G = r.gs + (long)blockIdx.y * d.m;
     double logt = 0, rpt = 0;
     const long r0 = (long)blockIdx.x * d.chunk, wb = (long)w * d.R;
     for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.R; r += blockDim.x) {
@@ -2225,85 +2225,85 @@ __device__ __attribute__((always_inline)) void ipm_rows_Cs_body(const NlpDev& d)
         if (has_lo(d, L)) { const double st = slo + alpha * dslo; logt += log(st); rpt += fabs((v - L) - st); }
         if (has_hi(d, U)) { const double st = shi + alpha * dshi; logt += log(st); rpt += fabs((U - v) - st); }
     }
-    double* out = d.partial_s + ((long)blockIdx.y * d.nblk + blockIdx.x) * KA;
+    double* out = r.partial_s + ((long)blockIdx.y * d.nblk + blockIdx.x) * KA;
     double v[2] = {logt, rpt};
     const int kinds[2] = {0, 0};
     block_reduce_n(v, kinds, lds, out);
 }
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_Cs(NlpDev d) { ipm_rows_Cs_body<false>(d); }
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_Cs_mx(NlpDev d) { ipm_rows_Cs_body<true>(d); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_Cs(NlpDev d, Round r) { ipm_rows_Cs_body<false>(d, r); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_Cs_mx(NlpDev d, Round r) { ipm_rows_Cs_body<true>(d, r); }
 
 // the trials of a speculative round tested in order, exactly as the sequential rounds would
 // (ipm_world_C): the first acceptable one ends the search, or the last (forced) one
 // list entry blockIdx.x (one wave): every trial's two partial sums at once (lane 2 k + q, block
 // partials summed in order as world_partials_at), then the acceptance tests in trial order on lane 0
 template <bool MX>
-__device__ inline void world_Cs_body(const NlpDev& d, WorldState& S, int i);
+__device__ inline void world_Cs_body(const NlpDev& d, const Round& r, WorldState& S, int i);
 template <bool MX>
-__device__ __attribute__((always_inline)) void ipm_world_Cs_body(const NlpDev& d) {
-    if (d.lcount && blockIdx.x >= *d.lcount) return;
-    const int w = d.wl[blockIdx.x];
+__device__ __attribute__((always_inline)) void ipm_world_Cs_body(const NlpDev& d, const Round& r) {
+    if (r.lcount && blockIdx.x >= *r.lcount) return;
+    const int w = r.wl[blockIdx.x];
     __shared__ WorldState S;
     ws_copy(S, d.ws[w]);
     __syncthreads();
     const bool act = S.status == 0;
-    world_Cs_body<MX>(d, S, blockIdx.x);
+    world_Cs_body<MX>(d, r, S, blockIdx.x);
     __syncthreads();
     if (act) ws_copy(d.ws[w], S);
 }
-__global__ __launch_bounds__(64) void ipm_world_Cs(NlpDev d) { ipm_world_Cs_body<false>(d); }
-__global__ __launch_bounds__(64) void ipm_world_Cs_mx(NlpDev d) { ipm_world_Cs_body<true>(d); }
+__global__ __launch_bounds__(64) void ipm_world_Cs(NlpDev d, Round r) { ipm_world_Cs_body<false>(d, r); }
+__global__ __launch_bounds__(64) void ipm_world_Cs_mx(NlpDev d, Round r) { ipm_world_Cs_body<true>(d, r); }
 // The tail's whole line search in one round (planner.hip run_solver, sync-free tail): every trial
 // k = 0 .. max_ls - 1 of every running world was evaluated values-only (eval_trials_kernel with
 // K = max_ls) and summed (ipm_rows_Cs), so this is round 0 and every later round of
 // ipm_world_C's sequential search at once: the acceptance tests in trial order (world_Cs_body),
 // then round 0's bookkeeping — the worlds still running appended to the next iteration's list, the
 // last block publishing the count as ipm_world_C does for ls0. The chosen trial is then evaluated in
-// full (eval_kernel_t mode 5).
+// full (eval_kernel_t EVAL_CHOSEN).
 template <bool MX>
-__device__ __attribute__((always_inline)) void ipm_world_Cs_all_body(const NlpDev& d) {
-    const bool valid = !d.lcount || blockIdx.x < *d.lcount;
-    const int w = valid ? d.wl[blockIdx.x] : 0;
+__device__ __attribute__((always_inline)) void ipm_world_Cs_all_body(const NlpDev& d, const Round& r) {
+    const bool valid = !r.lcount || blockIdx.x < *r.lcount;
+    const int w = valid ? r.wl[blockIdx.x] : 0;
     __shared__ WorldState S;
     if (valid) {
         ws_copy(S, d.ws[w]);
         __syncthreads();
         const bool act = S.status == 0;
-        if (d.b_in_cs) world_B_body<MX>(d, S, w);
+        if (r.b_in_cs) world_B_body<MX>(d, S, w);
         __syncthreads();  // lane 0's WorldState stores before every lane's reads (filter_pass)
-        world_Cs_body<MX>(d, S, blockIdx.x);
+        world_Cs_body<MX>(d, r, S, blockIdx.x);
         __syncthreads();
         if (act) ws_copy(d.ws[w], S);
     }
     if (threadIdx.x != 0) return;
     if (valid && S.status == 0) {
-        d.wl_run[atomicAdd(&d.cnt[0], 1u)] = w;
-        if (S.spec_k > 0) atomicAdd(&d.cnt[1], 1u);  // searched past round 0
+        r.wl_run[atomicAdd(&d.cnt[CNT_RUN], 1u)] = w;
+        if (S.spec_k > 0) atomicAdd(&d.cnt[CNT_SEARCH], 1u);  // searched past round 0
     }
     __threadfence();
-    if (atomicAdd(&d.cnt[2], 1u) == gridDim.x - 1) {
+    if (atomicAdd(&d.cnt[CNT_TICKET], 1u) == gridDim.x - 1) {
         __threadfence();
-        const unsigned nrun = atomicAdd(&d.cnt[0], 0u), nbt = atomicAdd(&d.cnt[1], 0u);
-        d.flags[0] = (int)nrun;
-        d.flags[1] = 0;
-        if (d.lrun_out) *d.lrun_out = nrun;
-        if (d.nrun_flag) *d.nrun_flag = (int)nrun;
-        if (d.bt_flag) *d.bt_flag = (int)nbt;
-        if (d.pend_flag) *d.pend_flag = (int)atomicAdd(&d.cnt[12], 0u);
-        d.cnt[0] = 0;
-        d.cnt[1] = 0;
-        d.cnt[2] = 0;
+        const unsigned nrun = atomicAdd(&d.cnt[CNT_RUN], 0u), nbt = atomicAdd(&d.cnt[CNT_SEARCH], 0u);
+        d.flags[FLAG_RUN] = (int)nrun;
+        d.flags[FLAG_SEARCH] = 0;
+        if (r.lrun_out) *r.lrun_out = nrun;
+        if (r.nrun_flag) *r.nrun_flag = (int)nrun;
+        if (r.bt_flag) *r.bt_flag = (int)nbt;
+        if (r.pend_flag) *r.pend_flag = (int)atomicAdd(&d.cnt[CNT_RL], 0u);
+        d.cnt[CNT_RUN] = 0;
+        d.cnt[CNT_SEARCH] = 0;
+        d.cnt[CNT_TICKET] = 0;
     }
 }
-__global__ __launch_bounds__(64) void ipm_world_Cs_all(NlpDev d) { ipm_world_Cs_all_body<false>(d); }
-__global__ __launch_bounds__(64) void ipm_world_Cs_all_mx(NlpDev d) { ipm_world_Cs_all_body<true>(d); }
+__global__ __launch_bounds__(64) void ipm_world_Cs_all(NlpDev d, Round r) { ipm_world_Cs_all_body<false>(d, r); }
+__global__ __launch_bounds__(64) void ipm_world_Cs_all_mx(NlpDev d, Round r) { ipm_world_Cs_all_body<true>(d, r); }
 template <bool MX>
-__device__ inline void world_Cs_body(const NlpDev& d, WorldState& S, int i) {
+__device__ inline void world_Cs_body(const NlpDev& d, const Round& r, WorldState& S, int i) {
     const int lane = threadIdx.x & 63;
     double s = 0.0;
-    if (lane < 2 * d.K) {
-        const double* in = d.partial_s + ((long)i * d.K + (lane >> 1)) * d.nblk * KA + (lane & 1);
-        const int nb = shape_of<MX>(d, d.wl[i]).nblk;
+    if (lane < 2 * r.K) {
+        const double* in = r.partial_s + ((long)i * r.K + (lane >> 1)) * d.nblk * KA + (lane & 1);
+        const int nb = shape_of<MX>(d, r.wl[i]).nblk;
         for (int b0 = 0; b0 < nb; b0 += 16) {
             double x[16];
 #pragma unroll
@@ -2316,10 +2316,10 @@ __device__ inline void world_Cs_body(const NlpDev& d, WorldState& S, int i) {
     const uint64_t u = __builtin_bit_cast(uint64_t, s);
     // the trials' objective values, one per lane in a single load round (a load per trial inside
     // the loop below waited a memory latency per trial)
-    const uint64_t uf = __builtin_bit_cast(uint64_t, lane < d.K ? d.fs[(long)i * d.K + lane] : 0.0);
+    const uint64_t uf = __builtin_bit_cast(uint64_t, lane < r.K ? r.fs[(long)i * r.K + lane] : 0.0);
     int chosen = -1;
     const double mu = S.mu;
-    for (int k = 0; k < d.K; k++) {
+    for (int k = 0; k < r.K; k++) {
         const uint32_t lo0 = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, 2 * k);
         const uint32_t hi0 = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), 2 * k);
         const uint32_t lo1 = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, 2 * k + 1);
@@ -2332,7 +2332,7 @@ __device__ inline void world_Cs_body(const NlpDev& d, WorldState& S, int i) {
         // (the filter does not change while a search goes on: an acceptance ends it)
         const bool filt = filter_pass(S, rpt, ft - mu * logt);
         if (threadIdx.x == 0 && chosen == k - 1 && S.status == 0 && S.searching) {
-            accept_trial(d, S, logt, rpt, ft, filt, d.wl[i]);
+            accept_trial(d, r, S, logt, rpt, ft, filt, r.wl[i]);
             chosen = k;
         }
     }
@@ -2341,8 +2341,8 @@ __device__ inline void world_Cs_body(const NlpDev& d, WorldState& S, int i) {
 
 // pass D: accept the trial point — slacks, multipliers, BFGS ingredients
 template <bool MX>
-__device__ __attribute__((always_inline)) void ipm_rows_D_body(const NlpDev& d) {
-    const int w = world_of(d, blockIdx.y);
+__device__ __attribute__((always_inline)) void ipm_rows_D_body(const NlpDev& d, const Round& r) {
+    const int w = world_of(r, blockIdx.y);
     const Shape sh = shape_of<MX>(d, w);
     if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
     const WorldState& S = d.ws[w];
@@ -2365,8 +2365,8 @@ __device__ __attribute__((always_inline)) void ipm_rows_D_body(const NlpDev& d) 
     const int kinds[NF] = {};
     block_reduce_n(wn, kinds, lds, out);
 }
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_D(NlpDev d) { ipm_rows_D_body<false>(d); }
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_D_mx(NlpDev d) { ipm_rows_D_body<true>(d); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_D(NlpDev d, Round r) { ipm_rows_D_body<false>(d, r); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_D_mx(NlpDev d, Round r) { ipm_rows_D_body<true>(d, r); }
 
 // pass D's world step: BFGS update, accept the trial point; every lane of the wave calls it. The
 // vectors and scalars are formed by every lane alike (the same arithmetic in the same order, so the
@@ -2444,8 +2444,8 @@ __device__ inline void world_D_body(const NlpDev& d, WorldState& S, int w) {
     if (S.nfail >= 3) S.status = 3;
 }
 template <bool MX>
-__device__ __attribute__((always_inline)) void ipm_world_D_body(const NlpDev& d) {
-    const int w = world_of(d, blockIdx.x);
+__device__ __attribute__((always_inline)) void ipm_world_D_body(const NlpDev& d, const Round& r) {
+    const int w = world_of(r, blockIdx.x);
     __shared__ WorldState S;
     ws_copy(S, d.ws[w]);
     __syncthreads();
@@ -2454,13 +2454,13 @@ __device__ __attribute__((always_inline)) void ipm_world_D_body(const NlpDev& d)
     __syncthreads();
     if (act) ws_copy(d.ws[w], S);
 }
-__global__ __launch_bounds__(64) void ipm_world_D(NlpDev d) { ipm_world_D_body<false>(d); }
-__global__ __launch_bounds__(64) void ipm_world_D_mx(NlpDev d) { ipm_world_D_body<true>(d); }
+__global__ __launch_bounds__(64) void ipm_world_D(NlpDev d, Round r) { ipm_world_D_body<false>(d, r); }
+__global__ __launch_bounds__(64) void ipm_world_D_mx(NlpDev d, Round r) { ipm_world_D_body<true>(d, r); }
 // the fused passes' world step: D's (of the previous iteration), then A's, one wave
 template <bool MX>
-__device__ __attribute__((always_inline)) void ipm_world_DA_body(const NlpDev& d, int nside) {
-    if (d.lcount && blockIdx.x >= *d.lcount) return;
-    const int w = world_of(d, blockIdx.x);
+__device__ __attribute__((always_inline)) void ipm_world_DA_body(const NlpDev& d, const Round& r, int nside) {
+    if (r.lcount && blockIdx.x >= *r.lcount) return;
+    const int w = world_of(r, blockIdx.x);
     __shared__ WorldState S;
     ws_copy(S, d.ws[w]);
     __syncthreads();
@@ -2471,8 +2471,8 @@ __device__ __attribute__((always_inline)) void ipm_world_DA_body(const NlpDev& d
     __syncthreads();
     if (act) ws_copy(d.ws[w], S);
 }
-__global__ __launch_bounds__(64) void ipm_world_DA(NlpDev d, int nside) { ipm_world_DA_body<false>(d, nside); }
-__global__ __launch_bounds__(64) void ipm_world_DA_mx(NlpDev d, int nside) { ipm_world_DA_body<true>(d, nside); }
+__global__ __launch_bounds__(64) void ipm_world_DA(NlpDev d, Round r, int nside) { ipm_world_DA_body<false>(d, r, nside); }
+__global__ __launch_bounds__(64) void ipm_world_DA_mx(NlpDev d, Round r, int nside) { ipm_world_DA_body<true>(d, r, nside); }
 
 // ------------------------------------------------------------------------------------------
 // Restoration phase (oracle/src/ipm.cpp restoration). A world whose line search
@@ -2481,7 +2481,7 @@ __global__ __launch_bounds__(64) void ipm_world_DA_mx(NlpDev d, int nside) { ipm
 //   resto_rows_G / resto_world_G  the Gauss-Newton system of Phi at the current point, the
 //                                 decisions (every row within its bounds -> restart; the cap;
 //                                 stall) and the step with its largest fraction to the box;
-//   eval (mode 1) / resto_rows_V / resto_world_V  one Armijo trial per round, alpha halved, at
+//   eval (EVAL_TRIAL) / resto_rows_V / resto_world_V  one Armijo trial per round, alpha halved, at
 //                                 most max_ls rounds (the oracle's sequential search).
 // The restarted worlds go back to the interior point (ipm_rows_init on their list, then the loop).
 constexpr int NRG = 37;  // pass G's partial sums: M (28, upper triangle), b (7), sum e^2, max original violation
@@ -2509,9 +2509,9 @@ __device__ inline double resto_barrier(const NlpDev& d, const double* x) {
 }
 
 template <bool MX>
-__device__ __attribute__((always_inline)) void resto_rows_G_body(const NlpDev& d) {
-    if (d.lcount && blockIdx.y >= *d.lcount) return;
-    const int w = world_of(d, blockIdx.y);
+__device__ __attribute__((always_inline)) void resto_rows_G_body(const NlpDev& d, const Round& r) {
+    if (r.lcount && blockIdx.y >= *r.lcount) return;
+    const int w = world_of(r, blockIdx.y);
     const Shape sh = shape_of<MX>(d, w);
     if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
     const WorldState& S = d.ws[w];
@@ -2556,8 +2556,8 @@ __device__ __attribute__((always_inline)) void resto_rows_G_body(const NlpDev& d
     for (int k = 0; k < NRG; k++) kinds[k] = k == 36 ? 1 : 0;
     block_reduce_n(v, kinds, lds, d.partial + ((long)w * d.nblk + blockIdx.x) * KA);
 }
-__global__ __launch_bounds__(ROW_THREADS) void resto_rows_G(NlpDev d) { resto_rows_G_body<false>(d); }
-__global__ __launch_bounds__(ROW_THREADS) void resto_rows_G_mx(NlpDev d) { resto_rows_G_body<true>(d); }
+__global__ __launch_bounds__(ROW_THREADS) void resto_rows_G(NlpDev d, Round r) { resto_rows_G_body<false>(d, r); }
+__global__ __launch_bounds__(ROW_THREADS) void resto_rows_G_mx(NlpDev d, Round r) { resto_rows_G_body<true>(d, r); }
 
 // a restoration phase that reached a point within every bound hands the world back to the
 // interior point: a fresh filter and BFGS matrix at the current mu (slacks: ipm_rows_init)
@@ -2631,20 +2631,20 @@ __device__ inline void resto_step(const NlpDev& d, WorldState& S, const double (
 // the last block of a restoration launch publishes a count (worlds still in the phase / still
 // searching) into the mapped host flags and resets the ticket counters
 __device__ inline void resto_count(const NlpDev& d, bool mine, int flag) {
-    if (mine) atomicAdd(&d.cnt[0], 1u);
+    if (mine) atomicAdd(&d.cnt[CNT_RUN], 1u);
     __threadfence();
-    if (atomicAdd(&d.cnt[2], 1u) == gridDim.x - 1) {
+    if (atomicAdd(&d.cnt[CNT_TICKET], 1u) == gridDim.x - 1) {
         __threadfence();
-        d.flags[flag] = (int)atomicAdd(&d.cnt[0], 0u);
-        d.cnt[0] = 0;
-        d.cnt[2] = 0;
+        d.flags[flag] = (int)atomicAdd(&d.cnt[CNT_RUN], 0u);
+        d.cnt[CNT_RUN] = 0;
+        d.cnt[CNT_TICKET] = 0;
     }
 }
 
 template <bool MX>
-__device__ __attribute__((always_inline)) void resto_world_G_body(const NlpDev& d) {
-    if (d.lcount && blockIdx.x >= *d.lcount) return;  // (one-round search: no count published)
-    const int w = world_of(d, blockIdx.x);
+__device__ __attribute__((always_inline)) void resto_world_G_body(const NlpDev& d, const Round& r) {
+    if (r.lcount && blockIdx.x >= *r.lcount) return;  // (one-round search: no count published)
+    const int w = world_of(r, blockIdx.x);
     __shared__ WorldState S;
     ws_copy(S, d.ws[w]);
     __syncthreads();
@@ -2667,15 +2667,15 @@ __device__ __attribute__((always_inline)) void resto_world_G_body(const NlpDev& 
     }
     __syncthreads();
     if (act) ws_copy(d.ws[w], S);
-    if (threadIdx.x == 0 && d.rflag >= 0) resto_count(d, S.status == WS_RESTO, d.rflag);
+    if (threadIdx.x == 0 && r.rflag >= 0) resto_count(d, S.status == WS_RESTO, r.rflag);
 }
-__global__ __launch_bounds__(64) void resto_world_G(NlpDev d) { resto_world_G_body<false>(d); }
-__global__ __launch_bounds__(64) void resto_world_G_mx(NlpDev d) { resto_world_G_body<true>(d); }
+__global__ __launch_bounds__(64) void resto_world_G(NlpDev d, Round r) { resto_world_G_body<false>(d, r); }
+__global__ __launch_bounds__(64) void resto_world_G_mx(NlpDev d, Round r) { resto_world_G_body<true>(d, r); }
 
-// sum e^2 at the trial point (the trial slot's full evaluation, mode 1)
+// sum e^2 at the trial point (the trial slot's full evaluation, EVAL_TRIAL)
 template <bool MX>
-__device__ __attribute__((always_inline)) void resto_rows_V_body(const NlpDev& d) {
-    const int w = world_of(d, blockIdx.y);
+__device__ __attribute__((always_inline)) void resto_rows_V_body(const NlpDev& d, const Round& r) {
+    const int w = world_of(r, blockIdx.y);
     const Shape sh = shape_of<MX>(d, w);
     if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
     const WorldState& S = d.ws[w];
@@ -2696,14 +2696,14 @@ __device__ __attribute__((always_inline)) void resto_rows_V_body(const NlpDev& d
     const int kinds[1] = {0};
     block_reduce_n(vv, kinds, lds, d.partial + ((long)w * d.nblk + blockIdx.x) * KA);
 }
-__global__ __launch_bounds__(ROW_THREADS) void resto_rows_V(NlpDev d) { resto_rows_V_body<false>(d); }
-__global__ __launch_bounds__(ROW_THREADS) void resto_rows_V_mx(NlpDev d) { resto_rows_V_body<true>(d); }
+__global__ __launch_bounds__(ROW_THREADS) void resto_rows_V(NlpDev d, Round r) { resto_rows_V_body<false>(d, r); }
+__global__ __launch_bounds__(ROW_THREADS) void resto_rows_V_mx(NlpDev d, Round r) { resto_rows_V_body<true>(d, r); }
 
 // the Armijo test of the round's trial; a rejected trial halves alpha (max_ls trials, then the
 // phase fails: local infeasibility at the current point)
 template <bool MX>
-__device__ __attribute__((always_inline)) void resto_world_V_body(const NlpDev& d) {
-    const int w = world_of(d, blockIdx.x);
+__device__ __attribute__((always_inline)) void resto_world_V_body(const NlpDev& d, const Round& r) {
+    const int w = world_of(r, blockIdx.x);
     __shared__ WorldState S;
     ws_copy(S, d.ws[w]);
     __syncthreads();
@@ -2730,27 +2730,27 @@ __device__ __attribute__((always_inline)) void resto_world_V_body(const NlpDev& 
     }
     __syncthreads();
     if (act) ws_copy(d.ws[w], S);
-    if (threadIdx.x == 0) resto_count(d, S.status == WS_RESTO && S.searching, 1);
+    if (threadIdx.x == 0) resto_count(d, S.status == WS_RESTO && S.searching, FLAG_SEARCH);
 }
-__global__ __launch_bounds__(64) void resto_world_V(NlpDev d) { resto_world_V_body<false>(d); }
-__global__ __launch_bounds__(64) void resto_world_V_mx(NlpDev d) { resto_world_V_body<true>(d); }
+__global__ __launch_bounds__(64) void resto_world_V(NlpDev d, Round r) { resto_world_V_body<false>(d, r); }
+__global__ __launch_bounds__(64) void resto_world_V_mx(NlpDev d, Round r) { resto_world_V_body<true>(d, r); }
 
 // The phase's Armijo search in one round (planner.hip run_resto, when the speculative machinery is
-// there): the values of all max_ls trials (eval_trials_all, d.resto) summed per trial
+// there): the values of all max_ls trials (eval_trials_all, r.resto) summed per trial
 // (resto_rows_Vs, list entry i and trial k at blockIdx.y = i K + k, the rows and partial sums of
 // resto_rows_V), the tests in trial order (resto_world_Vs), then the chosen trial in full (eval
-// mode 5, d.resto). The decisions and the chosen point are those of the sequential rounds.
+// EVAL_CHOSEN, r.resto). The decisions and the chosen point are those of the sequential rounds.
 template <bool MX>
-__device__ __attribute__((always_inline)) void resto_rows_Vs_body(const NlpDev& d) {
-    const int i = blockIdx.y / d.K;
-    if (d.lcount && (unsigned)i >= *d.lcount) return;
-    const int w = d.wl[i];
+__device__ __attribute__((always_inline)) void resto_rows_Vs_body(const NlpDev& d, const Round& r) {
+    const int i = blockIdx.y / r.K;
+    if (r.lcount && (unsigned)i >= *r.lcount) return;
+    const int w = r.wl[i];
     const Shape sh = shape_of<MX>(d, w);
     if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
     const WorldState& S = d.ws[w];
     if (!(S.status == WS_RESTO && S.searching)) return;
     __shared__ double lds[(ROW_THREADS / 64) * NRG];
-    const double* G = d.gs + (long)blockIdx.y * d.m;
+    const double* G = r.gs + (long)blockIdx.y * d.m;
     double V = 0;
     const long r0 = (long)blockIdx.x * d.chunk, wb = (long)w * d.R;
     for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.m; r += blockDim.x) {
@@ -2762,17 +2762,17 @@ __device__ __attribute__((always_inline)) void resto_rows_Vs_body(const NlpDev& 
     }
     double vv[1] = {V};
     const int kinds[1] = {0};
-    block_reduce_n(vv, kinds, lds, d.partial_s + ((long)blockIdx.y * d.nblk + blockIdx.x) * KA);
+    block_reduce_n(vv, kinds, lds, r.partial_s + ((long)blockIdx.y * d.nblk + blockIdx.x) * KA);
 }
-__global__ __launch_bounds__(ROW_THREADS) void resto_rows_Vs(NlpDev d) { resto_rows_Vs_body<false>(d); }
-__global__ __launch_bounds__(ROW_THREADS) void resto_rows_Vs_mx(NlpDev d) { resto_rows_Vs_body<true>(d); }
+__global__ __launch_bounds__(ROW_THREADS) void resto_rows_Vs(NlpDev d, Round r) { resto_rows_Vs_body<false>(d, r); }
+__global__ __launch_bounds__(ROW_THREADS) void resto_rows_Vs_mx(NlpDev d, Round r) { resto_rows_Vs_body<true>(d, r); }
 // ... and the list compaction of the one-round iterations: the worlds still in the phase go to the
 // next iteration's list (wl_run), whose length the last block stores for the next launches (lrun_out,
 // device) and for the host (nrun_flag, mapped; read one iteration late)
 template <bool MX>
-__device__ __attribute__((always_inline)) void resto_world_Vs_body(const NlpDev& d) {
-    const bool valid = !d.lcount || blockIdx.x < *d.lcount;
-    const int i = blockIdx.x, w = valid ? d.wl[i] : 0;
+__device__ __attribute__((always_inline)) void resto_world_Vs_body(const NlpDev& d, const Round& r) {
+    const bool valid = !r.lcount || blockIdx.x < *r.lcount;
+    const int i = blockIdx.x, w = valid ? r.wl[i] : 0;
     __shared__ WorldState S;
     bool act = false;
     if (valid) {
@@ -2784,8 +2784,8 @@ __device__ __attribute__((always_inline)) void resto_world_Vs_body(const NlpDev&
         // trial k's sum on lane k, its blocks combined in order (world_partials_at's arithmetic)
         const int lane = threadIdx.x & 63;
         double v = 0.0;
-        if (lane < d.K) {
-            const double* in = d.partial_s + ((long)i * d.K + lane) * d.nblk * KA;
+        if (lane < r.K) {
+            const double* in = r.partial_s + ((long)i * r.K + lane) * d.nblk * KA;
             const int nblk = shape_of<MX>(d, w).nblk;
             for (int b0 = 0; b0 < nblk; b0 += 16) {
                 double xb[16];
@@ -2797,7 +2797,7 @@ __device__ __attribute__((always_inline)) void resto_world_Vs_body(const NlpDev&
             }
         }
         const uint64_t u = __builtin_bit_cast(uint64_t, v);
-        for (int k = 0; k < d.K; k++) {
+        for (int k = 0; k < r.K; k++) {
             const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, k);
             const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), k);
             const double Vk = __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
@@ -2823,37 +2823,37 @@ __device__ __attribute__((always_inline)) void resto_world_Vs_body(const NlpDev&
         if (act) ws_copy(d.ws[w], S);
     }
     if (threadIdx.x != 0) return;
-    if (d.rl_app) {  // inside the interior-point loop: the phase list, published by resto_publish
-        if (valid && S.status == WS_RESTO) d.rl_app[atomicAdd(&d.cnt[12], 1u)] = w;
+    if (r.rl_app) {  // inside the interior-point loop: the phase list, published by resto_publish
+        if (valid && S.status == WS_RESTO) r.rl_app[atomicAdd(&d.cnt[CNT_RL], 1u)] = w;
         return;
     }
-    if (valid && S.status == WS_RESTO) d.wl_run[atomicAdd(&d.cnt[0], 1u)] = w;
+    if (valid && S.status == WS_RESTO) r.wl_run[atomicAdd(&d.cnt[CNT_RUN], 1u)] = w;
     __threadfence();
-    if (atomicAdd(&d.cnt[2], 1u) == gridDim.x - 1) {
+    if (atomicAdd(&d.cnt[CNT_TICKET], 1u) == gridDim.x - 1) {
         __threadfence();
-        const unsigned n = atomicAdd(&d.cnt[0], 0u);
-        *d.lrun_out = n;
-        *d.nrun_flag = (int)n;
-        d.cnt[0] = 0;
-        d.cnt[2] = 0;
+        const unsigned n = atomicAdd(&d.cnt[CNT_RUN], 0u);
+        *r.lrun_out = n;
+        *r.nrun_flag = (int)n;
+        d.cnt[CNT_RUN] = 0;
+        d.cnt[CNT_TICKET] = 0;
     }
 }
-__global__ __launch_bounds__(64) void resto_world_Vs(NlpDev d) { resto_world_Vs_body<false>(d); }
-__global__ __launch_bounds__(64) void resto_world_Vs_mx(NlpDev d) { resto_world_Vs_body<true>(d); }
+__global__ __launch_bounds__(64) void resto_world_Vs(NlpDev d, Round r) { resto_world_Vs_body<false>(d, r); }
+__global__ __launch_bounds__(64) void resto_world_Vs_mx(NlpDev d, Round r) { resto_world_Vs_body<true>(d, r); }
 
 // the phase list of the next phase iteration: the worlds appended since the last publish (failed
 // line searches, and the worlds the last phase iteration kept) moved from the append list `src` to
-// `dst`, its length into cnt[14] (the phase launches' lcount) and, for the host, into the mapped
+// `dst`, its length into cnt[CNT_PL] (the phase launches' lcount) and, for the host, into the mapped
 // flag `pflag` (null: none); the append list starts empty again
 __global__ __launch_bounds__(256) void resto_publish(NlpDev d, const int* src, int* dst, int* pflag) {
     __shared__ unsigned n;
-    if (threadIdx.x == 0) n = atomicAdd(&d.cnt[12], 0u);
+    if (threadIdx.x == 0) n = atomicAdd(&d.cnt[CNT_RL], 0u);
     __syncthreads();
     for (unsigned i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
     __syncthreads();
     if (threadIdx.x == 0) {
-        d.cnt[14] = n;
-        d.cnt[12] = 0;
+        d.cnt[CNT_PL] = n;
+        d.cnt[CNT_RL] = 0;
         if (pflag) *pflag = (int)n;
     }
 }

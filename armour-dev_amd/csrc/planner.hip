@@ -265,6 +265,8 @@ struct armour_planner {
     hipStream_t rstream2 = nullptr;
     hipEvent_t ev_ip = nullptr, ev_pub = nullptr, ev_rend = nullptr;
     size_t resto_soff = 0;
+    double *gs = nullptr, *fs = nullptr, *partial_s = nullptr;  // the speculative rows (spec_view)
+    int K0 = 0;                                                 // trials after round 0, max_ls - 1
     WorldState* h_ws = nullptr;
     double* h_f = nullptr;
     int* h_feas = nullptr;
@@ -561,7 +563,6 @@ static int init_solver(armour_planner* p) {
     if (p->cfg.max_iter > 0) d.opt.max_iter = p->cfg.max_iter;
     if (set.mu_strategy >= 0) d.opt.mu_strategy = set.mu_strategy;  // adaptive (default) or monotone
     if (set.resto_max >= 0) d.opt.resto_max = set.resto_max;        // restoration phases per solve (0: none)
-    d.resto = 0;
     d.armtd = p->armtd ? 1 : 0;
     d.nt = p->armtd ? 0 : NF * T;
     d.krange = nullptr;
@@ -590,15 +591,13 @@ static int init_solver(armour_planner* p) {
         (rc = p->alloc(&d.ws, (size_t)Wm)) ||
         (rc = p->alloc(&p->feas, (size_t)Wm)))
         return rc;
-    // the solver's counts for the host live in mapped host memory (NlpDev::flags: [0, 1] a round's
-    // running / searching worlds, [2, 8) the sync-free tail's lagged counts, [8, 10) the concurrent
-    // restoration's published list lengths): kernels store them, the host reads them after an
-    // event or a synchronised round (no fill or copy per round)
-    HIPCK(hipHostMalloc((void**)&p->h_flags, 12 * sizeof(int), hipHostMallocMapped));
+    // the solver's counts for the host live in mapped host memory (NlpDev::flags, FlagSlot): kernels
+    // store them, the host reads them after an event or a synchronised round (no fill or copy per round)
+    HIPCK(hipHostMalloc((void**)&p->h_flags, FLAG_LEN * sizeof(int), hipHostMallocMapped));
     HIPCK(hipHostGetDevicePointer((void**)&d.flags, p->h_flags, 0));
     // active-world lists: two per iteration (ping-pong), two per line-search round
     // (+ two for the restoration phases inside the interior-point loop)
-    if ((rc = p->alloc(&p->d_lists, 6 * (size_t)Wm)) || (rc = p->alloc(&d.cnt, 16))) return rc;
+    if ((rc = p->alloc(&p->d_lists, 6 * (size_t)Wm)) || (rc = p->alloc(&d.cnt, CNT_LEN))) return rc;
     // certified plane cache: one record pool sized for PC_K records per (link, obstacle) pair of
     // every (world, t) (ARMOUR_PC_K, 1..36); each (world, t) block takes its records from the pool
     // with one atomic (pcbase). The survey workload keeps 5.3 planes per pair on average. A build
@@ -623,11 +622,11 @@ static int init_solver(armour_planner* p) {
     }
     // speculative line-search slots (values only): every world x (max_ls - 1) trials. The speculative
     // round reads the plane cache (ARMOUR planner, fp64); otherwise the rounds run one by one.
-    d.K = d.opt.max_ls - 1;
-    p->spec = !set.no_spec && d.K > 0 && d.K <= EV_MAXK && d.pcache && !p->armtd && !set.eval_f32;
+    p->K0 = d.opt.max_ls - 1;
+    p->spec = !set.no_spec && p->K0 > 0 && p->K0 <= EV_MAXK && d.pcache && !p->armtd && !set.eval_f32;
     // The sync-free tail may search all max_ls trials of its (at most tail_worlds) running worlds in
     // one round (run_solver)
-    p->spec_all = p->spec && p->set.tail_search > 0 && (d.K + 1) * NJ * Om <= UB_FULL;
+    p->spec_all = p->spec && p->set.tail_search > 0 && (p->K0 + 1) * NJ * Om <= UB_FULL;
     // the restoration phase searches all max_ls trials of up to every world at once
     p->resto_spec = p->spec && d.opt.resto_max > 0 && d.opt.max_ls <= EV_MAXK + 1 && d.opt.max_ls * NJ * Om <= UB_FULL &&
                     !set.resto_rounds;
@@ -643,26 +642,14 @@ static int init_solver(armour_planner* p) {
         // rows of the speculative slots: the interior point's rounds use the first Wm x K (the
         // sync-free tail's one-round search the first nall); a restoration phase Wm x max_ls, after
         // the tail's rows when it runs concurrently with the tail (resto_soff)
-        const size_t nall = p->spec_all ? (size_t)std::min(Wm, std::max(p->set.tail_worlds, 0)) * (d.K + 1) : 0;
+        const size_t nall = p->spec_all ? (size_t)std::min(Wm, std::max(p->set.tail_worlds, 0)) * (p->K0 + 1) : 0;
         p->resto_soff = p->resto_conc ? nall : 0;
         const size_t nres = p->resto_spec ? (size_t)Wm * d.opt.max_ls + p->resto_soff : 0;
-        const size_t ns = std::max(std::max((size_t)Wm * d.K, nall), nres);
-        if ((rc = p->alloc(&d.gs, ns * mmax)) || (rc = p->alloc(&d.fs, ns)) || (rc = p->alloc(&d.partial_s, ns * nblk_max * KA)))
+        const size_t ns = std::max(std::max((size_t)Wm * p->K0, nall), nres);
+        if ((rc = p->alloc(&p->gs, ns * mmax)) || (rc = p->alloc(&p->fs, ns)) || (rc = p->alloc(&p->partial_s, ns * nblk_max * KA)))
             return rc;
     }
-    HIPCK(hipMemset(d.cnt, 0, 16 * sizeof(unsigned)));
-    d.rl_app = nullptr;
-    d.pend_flag = nullptr;
-    d.lcount = nullptr;
-    d.b_in_cs = 0;
-    d.bt_flag = nullptr;
-    d.lrun_out = nullptr;
-    d.nrun_flag = nullptr;
-    d.lcount_out = nullptr;
-    d.wl = nullptr;
-    d.wl_run = p->d_lists;
-    d.wl_search = p->d_lists + 2 * Wm;
-    d.ls0 = 0;
+    HIPCK(hipMemset(d.cnt, 0, CNT_LEN * sizeof(unsigned)));
     HIPCK(hipHostMalloc((void**)&p->h_ws, Wm * sizeof(WorldState)));
     HIPCK(hipHostMalloc((void**)&p->h_f, 2 * Wm * sizeof(double)));
     HIPCK(hipHostMalloc((void**)&p->h_feas, Wm * sizeof(int)));
@@ -1014,67 +1001,153 @@ static int nside_count(const armour_planner* p) {
 static bool eval_small_fits(const armour_planner* p) {
     return !p->set.eval_full && !p->armtd && !p->set.eval_f32 && p->mono_max[0] <= LM_S && p->mono_max[1] <= UM_S;
 }
-static void launch_eval(armour_planner* p, dim3 grid, const NlpDev& d, int mode, bool cached = true, hipStream_t s = nullptr) {
+static void launch_eval(armour_planner* p, dim3 grid, const NlpDev& d, const Round& r, int mode, bool cached = true, hipStream_t s = nullptr) {
     if (!s) s = p->stream;
     const bool c = cached && d.pcready && d.O > 0;
     if (c && eval_small_fits(p) && eval_pair_doubles(p->NJ * d.O) <= UB_S) {
-        hipLaunchKernelGGL(KSEL(eval_kernel_small), grid, dim3(EVAL_THREADS), 0, s, d, mode);
+        hipLaunchKernelGGL(KSEL(eval_kernel_small), grid, dim3(EVAL_THREADS), 0, s, d, r, mode);
         return;
     }
     if (d.Ow) {  // a mixed batch (fp64 ARMOUR planner: upload_worlds)
-        hipLaunchKernelGGL(c ? eval_kernel_mx<true> : eval_kernel_mx<false>, grid, dim3(EVAL_THREADS), 0, s, d, mode);
+        hipLaunchKernelGGL(c ? eval_kernel_mx<true> : eval_kernel_mx<false>, grid, dim3(EVAL_THREADS), 0, s, d, r, mode);
         return;
     }
     auto k = p->set.eval_f32 ? (d.armtd ? eval_kernel_t<float, true, false> : eval_kernel_t<float, false, false>)
                          : c ? (d.armtd ? eval_kernel_t<double, true, true> : eval_kernel_t<double, false, true>)
                              : (d.armtd ? eval_kernel_t<double, true, false> : eval_kernel_t<double, false, false>);
-    hipLaunchKernelGGL(k, grid, dim3(EVAL_THREADS), 0, s, d, mode);
+    hipLaunchKernelGGL(k, grid, dim3(EVAL_THREADS), 0, s, d, r, mode);
 }
 // the values of the K remaining trials of n listed worlds (eval_trials_kernel), from the small-capacity
 // kernel when the (trial, pair) keys fit its buffer too
-static void launch_trials(armour_planner* p, int n, const NlpDev& d) {
-    const bool small = eval_small_fits(p) && d.K * p->NJ * d.O <= UB_TS;
-    hipLaunchKernelGGL(small ? KSEL(eval_trials_small) : KSEL(eval_trials_kernel), dim3(p->T, n), dim3(EVAL_THREADS), 0, p->stream, d);
+static void launch_trials(armour_planner* p, int n, const NlpDev& d, const Round& r) {
+    const bool small = eval_small_fits(p) && r.K * p->NJ * d.O <= UB_TS;
+    hipLaunchKernelGGL(small ? KSEL(eval_trials_small) : KSEL(eval_trials_kernel), dim3(p->T, n), dim3(EVAL_THREADS), 0, p->stream, d, r);
 }
 
-// One speculative line-search round over n list entries: the values of ds.K trials of every listed
+// One speculative line-search round over n list entries: the values of r.K trials of every listed
 // world, their row sums, the acceptance tests in trial order, then the chosen trial in full. `all`:
 // the sync-free tail's one-round form over all max_ls trials, round 0's included (eval_trials_all,
 // ipm_world_Cs_all with pass B's world step); else the K trials that remain after round 0.
-static void launch_spec_round(armour_planner* p, int n, const NlpDev& ds, bool all) {
+static void launch_spec_round(armour_planner* p, int n, const NlpDev& d, const Round& r, bool all) {
     if (all)
-        hipLaunchKernelGGL(KSEL(eval_trials_all), dim3(p->T, n), dim3(EVAL_THREADS), 0, p->stream, ds);
+        hipLaunchKernelGGL(KSEL(eval_trials_all), dim3(p->T, n), dim3(EVAL_THREADS), 0, p->stream, d, r);
     else
-        launch_trials(p, n, ds);
-    hipLaunchKernelGGL(KSEL(ipm_rows_Cs), dim3(ds.nblk, n * ds.K), dim3(ROW_THREADS), 0, p->stream, ds);
-    hipLaunchKernelGGL(all ? KSEL(ipm_world_Cs_all) : KSEL(ipm_world_Cs), dim3(n), dim3(64), 0, p->stream, ds);
-    launch_eval(p, dim3(p->T, n), ds, 5);
+        launch_trials(p, n, d, r);
+    hipLaunchKernelGGL(KSEL(ipm_rows_Cs), dim3(d.nblk, n * r.K), dim3(ROW_THREADS), 0, p->stream, d, r);
+    hipLaunchKernelGGL(all ? KSEL(ipm_world_Cs_all) : KSEL(ipm_world_Cs), dim3(n), dim3(64), 0, p->stream, d, r);
+    launch_eval(p, dim3(p->T, n), d, r, EVAL_CHOSEN);
 }
 
 // One restoration-phase iteration in its one-round form, over nb list entries on stream s: the
-// Gauss-Newton pass and world step, the values of all dr.K = max_ls trials, their sums, the tests in
+// Gauss-Newton pass and world step, the values of all r.K = max_ls trials, their sums, the tests in
 // trial order (resto_world_Vs), then the chosen trial in full.
-static void launch_resto_round(armour_planner* p, hipStream_t s, int nb, const NlpDev& dr) {
-    hipLaunchKernelGGL(KSEL(resto_rows_G), dim3(dr.nblk, nb), dim3(ROW_THREADS), 0, s, dr);
-    hipLaunchKernelGGL(KSEL(resto_world_G), dim3(nb), dim3(64), 0, s, dr);
-    hipLaunchKernelGGL(KSEL(eval_trials_all), dim3(p->T, nb), dim3(EVAL_THREADS), 0, s, dr);
-    hipLaunchKernelGGL(KSEL(resto_rows_Vs), dim3(dr.nblk, nb * dr.K), dim3(ROW_THREADS), 0, s, dr);
-    hipLaunchKernelGGL(KSEL(resto_world_Vs), dim3(nb), dim3(64), 0, s, dr);
-    launch_eval(p, dim3(p->T, nb), dr, 5, true, s);
+static void launch_resto_round(armour_planner* p, hipStream_t s, int nb, const NlpDev& d, const Round& r) {
+    hipLaunchKernelGGL(KSEL(resto_rows_G), dim3(d.nblk, nb), dim3(ROW_THREADS), 0, s, d, r);
+    hipLaunchKernelGGL(KSEL(resto_world_G), dim3(nb), dim3(64), 0, s, d, r);
+    hipLaunchKernelGGL(KSEL(eval_trials_all), dim3(p->T, nb), dim3(EVAL_THREADS), 0, s, d, r);
+    hipLaunchKernelGGL(KSEL(resto_rows_Vs), dim3(d.nblk, nb * r.K), dim3(ROW_THREADS), 0, s, d, r);
+    hipLaunchKernelGGL(KSEL(resto_world_Vs), dim3(nb), dim3(64), 0, s, d, r);
+    launch_eval(p, dim3(p->T, nb), d, r, EVAL_CHOSEN, true, s);
+}
+
+// The Round (nlp.h) of each launch family. A field a function does not name keeps Round{}'s value.
+static unsigned* cnt_at(const armour_planner* p, int base, int parity = 0) { return p->d.cnt + slot(base, parity); }
+static int* flag_at(const armour_planner* p, int base, int parity = 0) { return p->d.flags + slot(base, parity); }
+// K trials per list entry in the speculative rows; a phase iteration beside the tail (conc) takes
+// the rows after the tail's. The one place resto_soff is applied.
+static void spec_view(const armour_planner* p, Round& r, int K, bool conc = false) {
+    const size_t off = conc ? p->resto_soff : 0;
+    r.K = K;
+    r.gs = p->gs + off * (size_t)p->d.m;
+    r.fs = p->fs + off;
+    r.partial_s = p->partial_s + off * (size_t)p->d.nblk * KA;
+}
+// (Round{wl, lcount} alone: passes A / DA / B of an iteration; Round{wl}: a restart's ipm_rows_init)
+// what the line-search rounds of iteration `it` share: a failed search is appended to RL (null:
+// phases run after the loop), whose length the round's last world kernel stores for the host
+static Round round_search(const armour_planner* p, int it, int* RL, const int* wl, const unsigned* lcount) {
+    Round r{wl, lcount};
+    r.rl_app = RL;
+    r.pend_flag = RL ? flag_at(p, FLAG_PEND, it) : nullptr;
+    return r;
+}
+// round 0: the running worlds into wl_run, the searching ones into wl_search, both lengths to the
+// host and to the next launches; tl: sync-free, wl's length from the device, lagged counts to the host
+static Round round_first(const armour_planner* p, int it, int* RL, bool tl, const int* wl, int* wl_run, int* wl_search) {
+    Round r = round_search(p, it, RL, wl, tl ? cnt_at(p, CNT_ITER, it) : nullptr);
+    r.wl_run = wl_run;
+    r.wl_search = wl_search;
+    r.ls0 = 1;
+    r.lcount_out = cnt_at(p, CNT_LS, 1);
+    r.lrun_out = cnt_at(p, CNT_ITER, it + 1);
+    r.nrun_flag = tl ? flag_at(p, FLAG_NRUN, it) : nullptr;
+    r.bt_flag = tl ? flag_at(p, FLAG_BT, it) : nullptr;
+    return r;
+}
+// sequential round ls >= 1: the searching list Ls[ls & 1] into the other one
+static Round round_next(const armour_planner* p, int it, int* RL, int ls, int* const* Ls) {
+    Round r = round_search(p, it, RL, Ls[ls & 1], cnt_at(p, CNT_LS, ls));
+    r.wl_search = Ls[(ls + 1) & 1];
+    r.lcount_out = cnt_at(p, CNT_LS, ls + 1);
+    return r;
+}
+// the speculative round over round 0's searching list (tl: its length read from the device)
+static Round round_spec(const armour_planner* p, int it, int* RL, bool tl, const int* wl) {
+    Round r = round_search(p, it, RL, wl, tl ? cnt_at(p, CNT_LS, 1) : nullptr);
+    spec_view(p, r, p->K0);
+    return r;
+}
+// the tail's one-round search: all max_ls trials of the iteration list, round 0's outputs
+static Round round_tail_all(const armour_planner* p, int it, int* RL, const int* wl, int* wl_run) {
+    Round r = round_search(p, it, RL, wl, cnt_at(p, CNT_ITER, it));
+    r.wl_run = wl_run;
+    r.b_in_cs = 1;  // pass B's world step in ipm_world_Cs_all
+    r.lrun_out = cnt_at(p, CNT_ITER, it + 1);
+    r.nrun_flag = flag_at(p, FLAG_NRUN, it);
+    r.bt_flag = flag_at(p, FLAG_BT, it);
+    spec_view(p, r, p->K0 + 1);
+    return r;
+}
+// a one-round restoration-phase iteration inside the interior-point loop: the published list PL,
+// kept worlds appended to RL (conc: on the second stream, beside the tail)
+static Round round_resto_inline(const armour_planner* p, const int* PL, int* RL, bool conc) {
+    Round r{PL, cnt_at(p, CNT_PL)};
+    r.resto = 1;
+    r.rl_app = RL;
+    spec_view(p, r, p->d.opt.max_ls, conc);
+    return r;
+}
+// iteration k of run_resto's one-round form: list L[k & 1], kept worlds into the other, its length
+// to CNT_ITER of k + 1 (the next launches' lcount) and FLAG_NRUN of k (the host reads it one later)
+static Round round_resto_iter(const armour_planner* p, int k, int* const* L) {
+    Round r{L[k & 1], k == 0 ? nullptr : cnt_at(p, CNT_ITER, k)};
+    r.resto = 1;
+    r.wl_run = L[(k + 1) & 1];
+    r.lrun_out = cnt_at(p, CNT_ITER, k + 1);
+    r.nrun_flag = flag_at(p, FLAG_NRUN, k);
+    spec_view(p, r, p->d.opt.max_ls);
+    return r;
+}
+// run_resto's sequential form: the whole list every round, counts to FLAG_RUN / FLAG_SEARCH
+static Round round_resto_seq(const int* list) {
+    Round r{list};
+    r.resto = 1;
+    r.rflag = FLAG_RUN;
+    return r;
 }
 
 // The interior-point loop over the nrun worlds listed in the first iteration list (d_lists[0..]):
 // every world there starts an iteration with pass A at its current point (a fresh solve, or a
 // restart after a restoration phase).
 static int ipm_loop(armour_planner* p, int nrun) {
-    NlpDev& d = p->d;
+    const NlpDev& d = p->d;
     int* Li[2] = {p->d_lists, p->d_lists + p->Wmax};                  // worlds of an iteration
     int* Ls[2] = {p->d_lists + 2 * p->Wmax, p->d_lists + 3 * p->Wmax};  // worlds of a line-search round
     const int ns = nside_count(p);
     // Restoration phases inside the loop (with the speculative machinery): after an iteration's
     // interior-point launches, one phase iteration (run_resto's one-round form) for the worlds whose
     // line search failed and are still in their phase. Failures (accept_trial) and the worlds a
-    // phase iteration keeps are appended to one list RL (cnt[12]); resto_publish moves it into the
+    // phase iteration keeps are appended to one list RL (CNT_RL); resto_publish moves it into the
     // phase list PL of the next phase iteration, so an iteration may launch no phase work at all
     // and the appends wait for the next one that does. The host decides from the list length the
     // round's last world kernel stores (pend_flag): in a synchronised iteration exactly (the length
@@ -1085,28 +1158,41 @@ static int ipm_loop(armour_planner* p, int nrun) {
     // does a restarted world's interior point (the next ipm_loop). A loop over one world runs its
     // phases after the loop: there is no other world's iteration to overlap them with.
     const bool inl = p->resto_inline && d.pcready && nrun > 1;
-    int* RL = p->d_lists + 4 * p->Wmax;
-    int* PL = p->d_lists + 5 * p->Wmax;
+    int* const RL = inl ? p->d_lists + 4 * p->Wmax : nullptr;
+    int* const PL = p->d_lists + 5 * p->Wmax;
     volatile int* flr = p->h_flags;
     const int W0 = nrun;
     int pend_known = 0;  // the latest list length the host has read
     int ub = 0;          // an upper bound of the list's length now: the last phase grid, plus every
                          // interior-point world launched since (each could have failed)
-    if (inl) HIPCK(hipMemsetAsync(d.cnt + 12, 0, sizeof(unsigned), p->stream));
+    if (inl) HIPCK(hipMemsetAsync(cnt_at(p, CNT_RL), 0, sizeof(unsigned), p->stream));
     // conc: this phase iteration runs on the second stream, concurrently with the next
     // interior-point iteration (sync-free tail, p->resto_conc). The phase's worlds are not the
     // interior point's (an iteration's list may still name a world that failed after the list was
     // formed: the world kernels write back only the worlds they work on, nlp_kernels.hip ws_copy),
     // and its speculative rows start resto_soff rows in (after the tail's); the
-    // one shared structure is the append list RL (cnt[12]): interior-point failures and the phase's
+    // one shared structure is the append list RL (CNT_RL): interior-point failures and the phase's
     // kept worlds append to it with atomics, and resto_publish moves it to the phase list. So the
     // publish waits for the interior-point iteration that appended (ev_ip), and the next
     // interior-point iteration waits for the publish (ev_pub), not for the phase iteration. An
     // interior-point iteration's snapshot of the list (pend_flag) may then miss the worlds the
     // concurrent phase iteration keeps, so the host also reads the length each publish moved
-    // (flags[8 + (it & 1)], pub_known): a phase iteration that had worlds is followed by another at
+    // (FLAG_PUB, pub_known): a phase iteration that had worlds is followed by another at
     // most two iterations later, as long as the loop runs.
-    bool conc_used = false;
+    // Once work is queued on the second stream, every way out of this function joins it before
+    // anything reads the phase's worlds or reuses PL: the normal exit reports join()'s error, any
+    // other return runs it from the destructor and keeps the first error.
+    struct Join {
+        armour_planner* p;
+        bool queued = false;
+        hipError_t operator()() {
+            if (!queued) return hipSuccess;
+            queued = false;
+            const hipError_t e = hipEventRecord(p->ev_rend, p->rstream2);
+            return e != hipSuccess ? e : hipStreamWaitEvent(p->stream, p->ev_rend, 0);
+        }
+        ~Join() { (void)(*this)(); }
+    } join{p};
     bool pub_launched[2] = {false, false};
     int pub_known = 0;
     auto resto_iter = [&](int it, int bound, bool conc) -> int {
@@ -1116,11 +1202,11 @@ static int ipm_loop(armour_planner* p, int nrun) {
         if (conc) {
             s = p->rstream2;
             HIPCK(hipEventRecord(p->ev_ip, p->stream));
+            join.queued = true;
             HIPCK(hipStreamWaitEvent(s, p->ev_ip, 0));
-            conc_used = true;
         }
         hipLaunchKernelGGL(resto_publish, dim3(1), dim3(256), 0, s, d, (const int*)RL, PL,
-                           conc ? d.flags + 8 + (it & 1) : nullptr);
+                           conc ? flag_at(p, FLAG_PUB, it) : nullptr);
         pub_launched[it & 1] = conc;
         if (conc) {
             HIPCK(hipEventRecord(p->ev_pub, s));
@@ -1128,24 +1214,10 @@ static int ipm_loop(armour_planner* p, int nrun) {
         }
         const int nb = std::min(W0, bound);
         ub = nb;  // the phase keeps at most the worlds it took
-        NlpDev dr = d;
-        dr.resto = 1;
-        dr.K = d.opt.max_ls;
-        dr.b_in_cs = 0;
-        dr.rflag = -1;
-        dr.wl = PL;
-        dr.lcount = d.cnt + 14;
-        dr.rl_app = RL;
-        dr.pend_flag = nullptr;
-        if (conc) {
-            dr.gs = d.gs + p->resto_soff * (size_t)d.m;
-            dr.fs = d.fs + p->resto_soff;
-            dr.partial_s = d.partial_s + p->resto_soff * (size_t)d.nblk * KA;
-        }
-        launch_resto_round(p, s, nb, dr);
+        launch_resto_round(p, s, nb, d, round_resto_inline(p, PL, RL, conc));
         return 0;
     };
-    // Launches cover the active worlds only (NlpDev::wl): every line-search round's ipm_world_C
+    // Launches cover the active worlds only (Round::wl): every line-search round's ipm_world_C
     // compacts the worlds still running / still searching into the next lists and publishes the
     // counts in mapped host memory, read after the round's one host synchronisation. Inactive
     // worlds in a list (finished by ipm_world_A / _D since) exit at once. A world's arithmetic does
@@ -1153,9 +1225,9 @@ static int ipm_loop(armour_planner* p, int nrun) {
     // Sync-free tail: once at most tail_worlds worlds run (and the speculative round is available),
     // an iteration is launched without waiting for the previous one. Grids are sized by the last
     // known running count (an upper bound: the count only falls), every launch reads the true list
-    // lengths from device memory (the running count of iteration it in cnt[8 + (it & 1)], the
-    // searching count in cnt[5]), and the host learns iteration it's running count one iteration
-    // later (event tev[it & 1], flags[2 + (it & 1)]). Blocks past a list's length exit at once, so a
+    // lengths from device memory (the running count of iteration it in CNT_ITER, the
+    // searching count in CNT_LS), and the host learns iteration it's running count one iteration
+    // later (event tev[it & 1], FLAG_NRUN). Blocks past a list's length exit at once, so a
     // world's arithmetic is that of the synchronised loop.
     int cur = 0;
     bool tail = false;       // iteration it - 1 ran sync-free (its running count not yet read)
@@ -1177,10 +1249,10 @@ static int ipm_loop(armour_planner* p, int nrun) {
         cur = 1 - cur;
         if (tail) {
             HIPCK(hipEventSynchronize(p->tev[(it - 1) & 1]));
-            if (inl) pend_known = flr[6 + ((it - 1) & 1)];
-            pub_known = pub_launched[(it - 1) & 1] ? flr[8 + ((it - 1) & 1)] : 0;
-            const int prev = flr[2 + ((it - 1) & 1)];
-            backtracked = flr[4 + ((it - 1) & 1)];
+            if (inl) pend_known = flr[slot(FLAG_PEND, it - 1)];
+            pub_known = pub_launched[(it - 1) & 1] ? flr[slot(FLAG_PUB, it - 1)] : 0;
+            const int prev = flr[slot(FLAG_NRUN, it - 1)];
+            backtracked = flr[slot(FLAG_BT, it - 1)];
             if (prev == 0) {
                 done = true;
                 return 0;
@@ -1192,106 +1264,63 @@ static int ipm_loop(armour_planner* p, int nrun) {
     };
     for (int it = 0; it <= d.opt.max_iter && nrun > 0; it++) {
         const bool tl = it > 0 && p->spec && d.pcready && nrun <= p->set.tail_worlds;
-        // this iteration's failed line searches, and the list length its last world kernel reports
-        d.rl_app = inl ? RL : nullptr;
-        d.pend_flag = inl ? d.flags + 6 + (it & 1) : nullptr;
-        NlpDev di = d;
-        di.wl = Li[cur];
-        if (tl) di.lcount = d.cnt + 8 + (it & 1);
+        const Round di{Li[cur], tl ? cnt_at(p, CNT_ITER, it) : nullptr};
         // pass D of the previous iteration (accept its trial point) shares one sweep over the rows
         // with this iteration's pass A
         if (it == 0) {
-            hipLaunchKernelGGL(KSEL(ipm_rows_A), dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, di);
-            hipLaunchKernelGGL(KSEL(ipm_world_A), dim3(nrun), dim3(64), 0, p->stream, di, ns);
+            hipLaunchKernelGGL(KSEL(ipm_rows_A), dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, d, di);
+            hipLaunchKernelGGL(KSEL(ipm_world_A), dim3(nrun), dim3(64), 0, p->stream, d, di, ns);
         } else {
             // the LDS-accumulator form for grids of several blocks per CU (nlp_kernels.hip rows_DA_body)
             const bool wide = p->set.da_lds && (long)d.nblk * nrun >= 4L * p->ncu;
-            hipLaunchKernelGGL(wide ? KSEL(ipm_rows_DA_lds) : KSEL(ipm_rows_DA), dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, di);
-            hipLaunchKernelGGL(KSEL(ipm_world_DA), dim3(nrun), dim3(64), 0, p->stream, di, ns);
+            hipLaunchKernelGGL(wide ? KSEL(ipm_rows_DA_lds) : KSEL(ipm_rows_DA), dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, d, di);
+            hipLaunchKernelGGL(KSEL(ipm_world_DA), dim3(nrun), dim3(64), 0, p->stream, d, di, ns);
         }
         const bool one = tl && p->spec_all && (p->set.tail_search == 2 || backtracked > 0);
-        hipLaunchKernelGGL(KSEL(ipm_rows_B), dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, di);
-        if (!one) hipLaunchKernelGGL(KSEL(ipm_world_B), dim3(nrun), dim3(64), 0, p->stream, di);
-        if (one) {
-            // The tail's line search in one round: the values of all max_ls trials of every running
-            // world at once (round 0's included, the step taken from pass B's partials), then pass
-            // B's world step, the acceptance tests in trial order and round 0's running list and
-            // counts (ipm_world_Cs_all), then the chosen trial in full. Four launches where pass B's
-            // world step and round 0 took four and the speculative round four more; the tests, and
-            // so the plans, are those of sequential rounds.
-            NlpDev ds = d;
-            ds.K = d.K + 1;
-            ds.b_in_cs = 1;  // pass B's world step in ipm_world_Cs_all
-            ds.wl = Li[cur];
-            ds.wl_run = Li[1 - cur];
-            ds.lcount = di.lcount;
-            ds.lrun_out = d.cnt + 8 + ((it + 1) & 1);
-            ds.nrun_flag = d.flags + 2 + (it & 1);
-            ds.bt_flag = d.flags + 4 + (it & 1);
-            launch_spec_round(p, nrun, ds, true);
-            bool done = false;
-            if (int rc = tail_end(it, done)) return rc;
-            if (done) break;
-            continue;
-        }
+        hipLaunchKernelGGL(KSEL(ipm_rows_B), dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, d, di);
+        if (!one) hipLaunchKernelGGL(KSEL(ipm_world_B), dim3(nrun), dim3(64), 0, p->stream, d, di);
         // Round 0 of the line search for every running world, then one host synchronisation. The
         // worlds still searching after it (the tail of the backtracking) run the remaining rounds
         // without one: a few of them all remaining trials at once (speculative round, ipm_world_Cs),
         // more of them round by round with grids sized by round 0's count and the list lengths in
-        // device memory (cnt[4 + r & 1]). Either way the arithmetic is that of sequential rounds.
-        int nnext = 0, nsearch = 0;
-        {
-            NlpDev dc = d;
-            dc.wl = Li[cur];
-            dc.wl_run = Li[1 - cur];
-            dc.wl_search = Ls[1];
-            dc.ls0 = 1;
-            dc.lcount_out = d.cnt + 5;
-            dc.lrun_out = d.cnt + 8 + ((it + 1) & 1);
-            if (tl) {
-                dc.lcount = di.lcount;
-                dc.nrun_flag = d.flags + 2 + (it & 1);
-                dc.bt_flag = d.flags + 4 + (it & 1);
-            }
-            launch_eval(p, dim3(p->T, nrun), dc, 1);
-            hipLaunchKernelGGL(KSEL(ipm_rows_C), dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, dc);
-            hipLaunchKernelGGL(KSEL(ipm_world_C), dim3(nrun), dim3(64), 0, p->stream, dc);
-            if (!tl) {
-                HIPCK(hipStreamSynchronize(p->stream));
-                nnext = ((volatile int*)p->h_flags)[0];
-                nsearch = ((volatile int*)p->h_flags)[1];
-                backtracked = nsearch;
-                if (inl) pend_known = flr[6 + (it & 1)];  // after round 0 (ipm_world_C's last block)
-            }
+        // device memory (CNT_LS). Either way the arithmetic is that of sequential rounds.
+        if (!one) {
+            const Round dc = round_first(p, it, RL, tl, Li[cur], Li[1 - cur], Ls[1]);
+            launch_eval(p, dim3(p->T, nrun), d, dc, EVAL_TRIAL);
+            hipLaunchKernelGGL(KSEL(ipm_rows_C), dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, d, dc);
+            hipLaunchKernelGGL(KSEL(ipm_world_C), dim3(nrun), dim3(64), 0, p->stream, d, dc);
         }
         if (tl) {
-            // the speculative round over at most nrun list entries, then the iteration's end event
-            NlpDev ds = d;
-            ds.wl = Ls[1];
-            ds.lcount = d.cnt + 5;
-            launch_spec_round(p, nrun, ds, false);
+            // Sync-free: the speculative round over at most nrun entries of round 0's searching list,
+            // or (one) the whole line search in one round: the values of all max_ls trials of every
+            // running world (round 0's included, the step taken from pass B's partials), then pass B's
+            // world step, the tests in trial order and round 0's running list and counts
+            // (ipm_world_Cs_all), then the chosen trial in full. Four launches where pass B's world
+            // step and round 0 took four and the speculative round four more; the tests, and so the
+            // plans, are those of sequential rounds. Then the iteration's end.
+            if (one)
+                launch_spec_round(p, nrun, d, round_tail_all(p, it, RL, Li[cur], Li[1 - cur]), true);
+            else
+                launch_spec_round(p, nrun, d, round_spec(p, it, RL, true, Ls[1]), false);
             bool done = false;
             if (int rc = tail_end(it, done)) return rc;
             if (done) break;
             continue;
         }
+        HIPCK(hipStreamSynchronize(p->stream));
+        const int nnext = flr[FLAG_RUN], nsearch = flr[FLAG_SEARCH];
+        backtracked = nsearch;
+        if (inl) pend_known = flr[slot(FLAG_PEND, it)];  // after round 0 (ipm_world_C's last block)
         if (nsearch > 0 && p->spec && d.pcready) {
             // the worlds still searching: the values of all remaining trials at once, the acceptance
             // tests in trial order, then the chosen trial in full
-            NlpDev ds = d;
-            ds.wl = Ls[1];
-            launch_spec_round(p, nsearch, ds, false);
+            launch_spec_round(p, nsearch, d, round_spec(p, it, RL, false, Ls[1]), false);
         } else if (nsearch > 0) {
             for (int ls = 1; ls < d.opt.max_ls; ls++) {
-                NlpDev dc = d;
-                dc.wl = Ls[ls & 1];
-                dc.lcount = d.cnt + 4 + (ls & 1);
-                dc.wl_search = Ls[(ls + 1) & 1];
-                dc.lcount_out = d.cnt + 4 + ((ls + 1) & 1);
-                dc.ls0 = 0;
-                launch_eval(p, dim3(p->T, nsearch), dc, 1);
-                hipLaunchKernelGGL(KSEL(ipm_rows_C), dim3(d.nblk, nsearch), dim3(ROW_THREADS), 0, p->stream, dc);
-                hipLaunchKernelGGL(KSEL(ipm_world_C), dim3(nsearch), dim3(64), 0, p->stream, dc);
+                const Round dc = round_next(p, it, RL, ls, Ls);
+                launch_eval(p, dim3(p->T, nsearch), d, dc, EVAL_TRIAL);
+                hipLaunchKernelGGL(KSEL(ipm_rows_C), dim3(d.nblk, nsearch), dim3(ROW_THREADS), 0, p->stream, d, dc);
+                hipLaunchKernelGGL(KSEL(ipm_world_C), dim3(nsearch), dim3(64), 0, p->stream, d, dc);
             }
         }
         // (the phase list's bound: its length after round 0, plus the worlds that searched past
@@ -1303,12 +1332,7 @@ static int ipm_loop(armour_planner* p, int nrun) {
         cur = 1 - cur;
         nrun = nnext;
     }
-    if (conc_used) {  // the last phase iteration, before anything reads its worlds or reuses PL
-        HIPCK(hipEventRecord(p->ev_rend, p->rstream2));
-        HIPCK(hipStreamWaitEvent(p->stream, p->ev_rend, 0));
-    }
-    d.rl_app = nullptr;
-    d.pend_flag = nullptr;
+    HIPCK(join());  // the last phase iteration
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -1318,41 +1342,25 @@ static int ipm_loop(armour_planner* p, int nrun) {
 // (p->resto_spec) the search is one round — the values of all max_ls trials, their sums, the tests
 // in trial order and the chosen trial's full evaluation — and iterations are launched without a
 // host synchronisation: the host reads iteration k - 1's count of worlds still in the phase (mapped
-// flags[2 + (k - 1) & 1], written by resto_world_G) after launching iteration k, so at most one
+// FLAG_NRUN of k - 1, written by resto_world_Vs) after launching iteration k, so at most one
 // empty iteration is launched. Otherwise one trial per round (a full evaluation each; rounds after
 // the first launched without a synchronisation, their blocks exit for worlds that stopped). The
 // worlds leave with status 0 (every row within its bounds: restart), 2 (iteration cap) or 5 (local
 // infeasibility). Either way the arithmetic and decisions are the oracle's sequential ones.
 static int run_resto(armour_planner* p, const int* list, int n) {
-    NlpDev dr = p->d;
-    dr.wl = list;
-    dr.resto = 1;
-    dr.lcount = nullptr;
-    dr.b_in_cs = 0;
+    const NlpDev& d = p->d;
     const volatile int* fl = p->h_flags;
-    const int guard = 4 * (dr.opt.max_iter + 1);
-    if (p->resto_spec && p->d.pcready) {
-        // iteration k works on list L[k & 1] (the first: `list`, n entries); resto_world_Vs appends
-        // the worlds still in the phase to L[(k + 1) & 1] and stores its length in cnt[8 + ((k + 1) & 1)]
-        // (the next launches' lcount) and flags[2 + (k & 1)] (read by the host after iteration k + 1
-        // is launched: the grid bound of iteration k + 2, or the end)
+    const int guard = 4 * (d.opt.max_iter + 1);
+    if (p->resto_spec && d.pcready) {
         int* L[2] = {const_cast<int*>(list), p->d_lists + 3 * p->Wmax};
-        dr.K = dr.opt.max_ls;
-        dr.rflag = -1;
         int nb = n;  // grid bound: the last count the host knows (counts only fall)
         for (int k = 0; k < guard; k++) {
-            NlpDev di = dr;
-            di.wl = L[k & 1];
-            di.wl_run = L[(k + 1) & 1];
-            di.lcount = k == 0 ? nullptr : p->d.cnt + 8 + (k & 1);
-            di.lrun_out = p->d.cnt + 8 + ((k + 1) & 1);
-            di.nrun_flag = p->d.flags + 2 + (k & 1);
-            launch_resto_round(p, p->stream, nb, di);
+            launch_resto_round(p, p->stream, nb, d, round_resto_iter(p, k, L));
             HIPCK(hipEventRecord(p->tev[k & 1], p->stream));
             HIPCK(hipGetLastError());
             if (k > 0) {
                 HIPCK(hipEventSynchronize(p->tev[(k - 1) & 1]));
-                const int prev = fl[2 + ((k - 1) & 1)];  // worlds iteration k was launched for
+                const int prev = fl[slot(FLAG_NRUN, k - 1)];  // worlds iteration k was launched for
                 if (prev == 0) break;
                 nb = prev < nb ? prev : nb;
             }
@@ -1360,20 +1368,19 @@ static int run_resto(armour_planner* p, const int* list, int n) {
         HIPCK(hipStreamSynchronize(p->stream));
         return 0;
     }
-    dr.rflag = 0;
-    dr.lrun_out = nullptr;
+    const Round dr = round_resto_seq(list);
     for (int k = 0; k < guard; k++) {
-        hipLaunchKernelGGL(KSEL(resto_rows_G), dim3(dr.nblk, n), dim3(ROW_THREADS), 0, p->stream, dr);
-        hipLaunchKernelGGL(KSEL(resto_world_G), dim3(n), dim3(64), 0, p->stream, dr);
+        hipLaunchKernelGGL(KSEL(resto_rows_G), dim3(d.nblk, n), dim3(ROW_THREADS), 0, p->stream, d, dr);
+        hipLaunchKernelGGL(KSEL(resto_world_G), dim3(n), dim3(64), 0, p->stream, d, dr);
         HIPCK(hipStreamSynchronize(p->stream));
-        if (fl[0] == 0) break;
-        for (int ls = 0; ls < dr.opt.max_ls; ls++) {
-            launch_eval(p, dim3(p->T, n), dr, 1);
-            hipLaunchKernelGGL(KSEL(resto_rows_V), dim3(dr.nblk, n), dim3(ROW_THREADS), 0, p->stream, dr);
-            hipLaunchKernelGGL(KSEL(resto_world_V), dim3(n), dim3(64), 0, p->stream, dr);
+        if (fl[FLAG_RUN] == 0) break;
+        for (int ls = 0; ls < d.opt.max_ls; ls++) {
+            launch_eval(p, dim3(p->T, n), d, dr, EVAL_TRIAL);
+            hipLaunchKernelGGL(KSEL(resto_rows_V), dim3(d.nblk, n), dim3(ROW_THREADS), 0, p->stream, d, dr);
+            hipLaunchKernelGGL(KSEL(resto_world_V), dim3(n), dim3(64), 0, p->stream, d, dr);
             if (ls == 0) {
                 HIPCK(hipStreamSynchronize(p->stream));
-                if (fl[1] == 0) break;
+                if (fl[FLAG_SEARCH] == 0) break;
             }
         }
         HIPCK(hipGetLastError());
@@ -1382,18 +1389,16 @@ static int run_resto(armour_planner* p, const int* list, int n) {
 }
 
 static int run_solver(armour_planner* p) {
-    NlpDev& d = p->d;
     const int W = p->W;
     int* Li0 = p->d_lists;                  // the interior-point loop's first list
     int* Lr = p->d_lists + 2 * p->Wmax;     // worlds of a restoration phase
-    d.wl = nullptr;
-    d.wl_run = Li0;
-    d.ls0 = 0;
-    d.resto = 0;
     ensure_plane_cache(p);
-    hipLaunchKernelGGL(ipm_world_init, dim3((W + 63) / 64), dim3(64), 0, p->stream, d);
-    launch_eval(p, dim3(p->T, W), d, 0);
-    hipLaunchKernelGGL(KSEL(ipm_rows_init), dim3(d.nblk, W), dim3(ROW_THREADS), 0, p->stream, d);
+    const NlpDev& d = p->d;
+    Round r0;  // ipm_world_init fills the first iteration list with every world
+    r0.wl_run = Li0;
+    hipLaunchKernelGGL(ipm_world_init, dim3((W + 63) / 64), dim3(64), 0, p->stream, d, r0);
+    launch_eval(p, dim3(p->T, W), d, Round{}, EVAL_POINT);
+    hipLaunchKernelGGL(KSEL(ipm_rows_init), dim3(d.nblk, W), dim3(ROW_THREADS), 0, p->stream, d, Round{});
     HIPCK(hipGetLastError());
     int rc = ipm_loop(p, W);
     // Restoration phases: the worlds whose line search failed left the loop with
@@ -1402,20 +1407,18 @@ static int run_solver(armour_planner* p) {
     // most resto_max phases per world, S.nresto).
     const volatile int* fl = p->h_flags;
     while (rc == 0 && d.opt.resto_max > 0) {
-        hipLaunchKernelGGL(ipm_collect, dim3(1), dim3(1024), 0, p->stream, d, (const int*)nullptr, W, WS_RESTO, Lr, 0, -1);
+        hipLaunchKernelGGL(ipm_collect, dim3(1), dim3(1024), 0, p->stream, d, (const int*)nullptr, W, WS_RESTO, Lr, FLAG_RUN, -1);
         HIPCK(hipStreamSynchronize(p->stream));
-        const int nr = fl[0];
+        const int nr = fl[FLAG_RUN];
         if (nr > 0 && (rc = run_resto(p, Lr, nr))) break;
         // the restarted worlds (WS_RESTART), running again from here. Collected whether or not a
         // phase ran just now: a phase that ran inside ipm_loop may have restarted a world while
         // other worlds were still iterating, and the loop never takes such a world back itself.
-        hipLaunchKernelGGL(ipm_collect, dim3(1), dim3(1024), 0, p->stream, d, (const int*)nullptr, W, WS_RESTART, Li0, 0, 0);
+        hipLaunchKernelGGL(ipm_collect, dim3(1), dim3(1024), 0, p->stream, d, (const int*)nullptr, W, WS_RESTART, Li0, FLAG_RUN, 0);
         HIPCK(hipStreamSynchronize(p->stream));
-        const int ni = fl[0];
+        const int ni = fl[FLAG_RUN];
         if (ni == 0) break;
-        NlpDev di = d;
-        di.wl = Li0;
-        hipLaunchKernelGGL(KSEL(ipm_rows_init), dim3(d.nblk, ni), dim3(ROW_THREADS), 0, p->stream, di);
+        hipLaunchKernelGGL(KSEL(ipm_rows_init), dim3(d.nblk, ni), dim3(ROW_THREADS), 0, p->stream, d, Round{Li0});
         rc = ipm_loop(p, ni);
     }
     if (rc) return rc;
@@ -1764,7 +1767,7 @@ int armour_eval_constraints(armour_planner* p, int w, const double* x, double* g
     if (!p || !x || !g) return fail(ARMOUR_E_ARG, "null argument");
     if (!p->reached) return fail(ARMOUR_E_STATE, "no reach set: call armour_reach_batch or armour_plan_batch first");
     if (w < 0 || w >= p->W) return fail(ARMOUR_E_ARG, "world index out of range");
-    NlpDev& d = p->d;
+    const NlpDev& d = p->d;
     // evaluate every world of the batch at x in slot 0 (ws.x is the solver's start/end point, so
     // a subsequent query of solver outputs must re-plan)
     // (on the planner's stream, so the copies are ordered with its kernels)
@@ -1780,7 +1783,7 @@ int armour_eval_constraints(armour_planner* p, int w, const double* x, double* g
     ensure_plane_cache(p);
     bool inbox = true;
     for (int j = 0; j < NF; j++) inbox = inbox && std::fabs(x[j]) <= PC_XBOX;
-    launch_eval(p, dim3(p->T, p->W), d, 0, inbox);
+    launch_eval(p, dim3(p->T, p->W), d, Round{}, EVAL_POINT, inbox);
     HIPCK(hipGetLastError());
     // world w's own m values (a mixed batch: the first m_w of its slab, which holds them compactly)
     const size_t mw = (size_t)armour_num_constraints(p, p->Ow[w]);
@@ -1818,7 +1821,7 @@ int armour_eval_candidates(armour_planner* p, int N, const double* x, double* co
     // the plane cache is certified for the box |x_i| <= 1 only
     for (size_t i = 0; i < n * NF; i++)
         if (!(std::fabs(x[i]) <= 1.0)) return fail(ARMOUR_E_ARG, "every candidate must be finite and inside [-1, 1]");
-    NlpDev& d = p->d;
+    const NlpDev& d = p->d;
     ensure_plane_cache(p);
     if (d.O > 0 && !d.pcready)
         return fail(ARMOUR_E_STATE, d.pcache ? "the certified plane cache is unavailable (its build did not fit a pool); "
@@ -2327,7 +2330,7 @@ int armour_get_link_centers(armour_planner* p, int w, double* c) {
     if (!p->planned && !p->evaluated) return fail(ARMOUR_E_STATE, "no plan and no evaluated point");
     if (w < 0 || w >= p->W) return fail(ARMOUR_E_ARG, "world index out of range");
     // after a plan: slot 2 (feasible_kernel's copy of the final iterate's centres); after
-    // armour_eval_constraints: slot 0, where eval_kernel_t in mode 0 wrote those of its point
+    // armour_eval_constraints: slot 0, where eval_kernel_t (EVAL_POINT) wrote those of its point
     const int slot = p->planned ? 2 : 0;
     HIPCK(hipMemcpy(c, p->d.link_c + slot * p->d.lcs + (size_t)w * p->T * p->NJ * 3, sizeof(double) * p->T * p->NJ * 3, hipMemcpyDeviceToHost));
     return 0;
@@ -2418,7 +2421,7 @@ int armour_get_plane_cache_stats(armour_planner* p, long long* out, int n) {
     DeviceScope device_scope(p);
     if (!p) return fail(ARMOUR_E_ARG, "null planner");
     if (!p->reached) return fail(ARMOUR_E_STATE, "no reach set");
-    NlpDev& d = p->d;
+    const NlpDev& d = p->d;
     if (!d.pcache || p->set.eval_f32 || d.O == 0) return fail(ARMOUR_E_STATE, "plane cache off (ARMOUR_PLANE_CACHE=0, float study or no obstacles)");
     ensure_plane_cache(p);
     const size_t blocks = (size_t)p->W * p->T, NP = (size_t)p->NJ * d.O;
@@ -2440,7 +2443,7 @@ int armour_get_plane_cache_stats(armour_planner* p, long long* out, int n) {
     }
     for (unsigned char v : ok) nok += v;
     unsigned miss = 0;
-    HIPCK(hipMemcpy(&miss, d.cnt + 7, sizeof(unsigned), hipMemcpyDeviceToHost));
+    HIPCK(hipMemcpy(&miss, cnt_at(p, CNT_PC_MISS), sizeof(unsigned), hipMemcpyDeviceToHost));
     const long long st[ARMOUR_PC_COUNT] = {kept, pairs, nok, (long long)blocks, mx, d.pc_pool, miss};
     for (int k = 0; k < n && k < ARMOUR_PC_COUNT; k++) out[k] = st[k];
     return ARMOUR_PC_COUNT;

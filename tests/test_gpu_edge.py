@@ -192,6 +192,42 @@ def test_concurrent_restoration_matches_serial(tail):
         assert np.array_equal(planners[0].constraints(w), planners[1].constraints(w))
 
 
+@pytest.mark.parametrize("conc", [None, "0"])
+def test_solve_leaves_nothing_for_later_launches(conc):
+    """Nothing a solve did reaches a later launch: the evaluations at a caller's point and the
+    candidate evaluations after plan() (planner B) are bitwise those after reach() alone (planner
+    A), with the restoration phases' iterations on the second stream (the default) and on the
+    solver's (ARMOUR_RESTO_CONCURRENT=0). The small boundary set covers both paths that describe
+    their launches most elaborately: its 12 worlds are at most the 16 of the sync-free tail, so
+    every iteration after the first runs there, and several worlds run restoration phases inside
+    the interior-point loop (two or more worlds run, the plane cache is built)."""
+    import os
+
+    fx = dict(np.load(os.path.join(os.path.dirname(__file__), "golden", "boundary_small_T20_O6.npz")))
+    T, O = int(fx["T"]), fx["obstacles"].shape[1]
+    worlds = [(fx["q0"][w], fx["qd0"][w], fx["qdd0"][w], fx["q_des"][w], fx["obstacles"][w])
+              for w in range(len(fx["kinds"]))]
+    if conc is not None:
+        os.environ["ARMOUR_RESTO_CONCURRENT"] = conc
+    try:
+        PA = A.Planner(T=T, max_obstacles=O, max_worlds=len(worlds))
+        PB = A.Planner(T=T, max_obstacles=O, max_worlds=len(worlds))
+    finally:
+        os.environ.pop("ARMOUR_RESTO_CONCURRENT", None)
+    x = np.linspace(-0.6, 0.7, 7)                                    # inside the certified box |x_i| <= 1
+    cand = np.random.default_rng(5).uniform(-1.0, 1.0, size=(6, 7))
+    PA.reach(worlds)
+    res, _ = PB.plan(worlds)
+    assert 1 < len(worlds) <= 16 and max(r["iterations"] for r in res) > 1, "no iteration in the sync-free tail"
+    assert sum(r["status"] == 4 for r in res) >= 3, "too few worlds in the restoration phase"
+    for w in (1, 9):
+        (ga, Ja), (gb, Jb) = PA.eval_constraints(w, x), PB.eval_constraints(w, x)
+        assert np.array_equal(ga, gb) and np.array_equal(Ja, Jb), w
+    ca, cb = PA.eval_candidates(cand), PB.eval_candidates(cand)
+    for k in ("cost", "violation", "feasible", "best"):
+        assert np.array_equal(ca[k], cb[k]), k
+
+
 def test_inline_restart_after_other_worlds_finish():
     """A world whose restoration phase restarts the interior point inside ipm_loop (status
     WS_RESTART) while another world is still iterating, after which that other world converges and

@@ -13,7 +13,7 @@ import sys
 
 
 def short(name):
-    """armour::eval_kernel_t<double, false, true>(armour::NlpDev, int) -> eval_kernel_t<double, false, true>"""
+    """armour::eval_kernel_t<double, false, true>(armour::NlpDev, armour::Round, int) -> eval_kernel_t<double, false, true>"""
     name = re.sub(r"\.kd$", "", name)
     name = re.sub(r"^void\s+", "", name)
     depth = 0
