@@ -192,6 +192,10 @@ def lib():
         L.armour_get_joint_bounds.argtypes = [ctypes.c_void_p, _dp]
         L.armour_get_plane_cache_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong), ctypes.c_int]
         L.armour_get_reach_span.argtypes = [ctypes.c_void_p, _dp]
+        if hasattr(L, "armour_get_path_counts"):  # absent from older libraries loaded through ARMOUR_LIB
+            L.armour_get_path_counts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong), ctypes.c_int]
+            L.armour_path_name.restype = ctypes.c_char_p
+            L.armour_path_name.argtypes = [ctypes.c_int]
         L.armour_get_reach_dump.argtypes = [ctypes.c_void_p, _dp, ctypes.c_int]
         L.armour_get_reach_profile.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int]
         for name in ("armour_get_constraints", "armour_get_link_centers", "armour_get_link_generators",
@@ -215,7 +219,8 @@ ABI_SYMBOLS = ["armour_copy_bandwidth", "armour_create", "armour_create_robot", 
                "armour_plan_batch_mixed", "armour_reach_batch_mixed", "armour_world_num_obstacles",
                "armour_eval_candidates", "armour_sq_selfcheck", "armour_check_world", "armour_check_armtd_world",
                "armour_check_motion", "armour_episode_begin", "armour_episode_step", "armour_episode_get",
-               "armour_track", "armour_track_motion", "armour_episode_track", "armour_episode_get_tracked"]
+               "armour_track", "armour_track_motion", "armour_episode_track", "armour_episode_get_tracked",
+               "armour_get_path_counts", "armour_path_name"]
 
 
 def default_batch(T: int, device: int = 0, waves: int = 2) -> int:
@@ -751,10 +756,21 @@ class Planner:
         return {k: (int(used[i]), int(caps[i])) for i, k in enumerate(self.OCCUPANCY)}
 
     def reach_span_ms(self):
-        """device-clock execution span of the last reach launch, ms (armour_get_reach_span)"""
+        """device-clock execution span of the last batch's first reach launch, ms (armour_get_reach_span;
+        a capacity retry's launch is not included)"""
         v = ctypes.c_double()
         _check(lib().armour_get_reach_span(self.h, ctypes.byref(v)))
         return v.value
+
+    def path_counts(self):
+        """{name: launches or iterations since creation} of every host-side dispatch branch
+        (armour_get_path_counts, with the library's own names: armour_path_name)"""
+        L = lib()
+        n = L.armour_get_path_counts(self.h, None, 0)
+        _check(min(0, n))
+        out = (ctypes.c_longlong * n)()
+        _check(min(0, L.armour_get_path_counts(self.h, out, n)))
+        return {L.armour_path_name(i).decode(): int(out[i]) for i in range(n)}
 
     def plane_cache_stats(self):
         """certified plane cache of the current reach sets (armour_get_plane_cache_stats)"""

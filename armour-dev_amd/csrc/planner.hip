@@ -92,6 +92,45 @@ struct GrowSet {
 // whether the GPU is shared (lane_shape_for)
 static std::atomic<int> g_planners[64];
 
+// The path census (include/armour_hip.h, armour_get_path_counts): one counter per branch of every
+// host-side dispatch decision, incremented where the host makes the choice, from what it knows there.
+// Plain integers on the handle, cumulative since creation; nothing on the device sees them.
+#define ARMOUR_PATHS(X)                                                                            \
+    X(BATCH_UNIFORM, "batch_uniform") X(BATCH_MIXED, "batch_mixed")                                \
+    X(REACH_JOB_256, "reach_job_256") X(REACH_JOB_128, "reach_job_128")                            \
+    X(REACH_LANE_WIDE, "reach_lane_wide") X(REACH_LANE_DENSE, "reach_lane_dense")                  \
+    X(REACH_RETRY, "reach_retry") X(REACH_SQ, "reach_sq") X(REACH_SQRT, "reach_sqrt")              \
+    X(REACH_CU_MASKED, "reach_cu_masked")                                                          \
+    X(EVAL_SMALL, "eval_small") X(EVAL_F64, "eval_f64") X(EVAL_F32, "eval_f32")                    \
+    X(EVAL_ARMTD_F64, "eval_armtd_f64") X(EVAL_ARMTD_F32, "eval_armtd_f32") X(EVAL_MX, "eval_mx")  \
+    X(EVAL_CACHED, "eval_cached") X(EVAL_FULL_SCAN, "eval_full_scan")                              \
+    X(TRIALS_SMALL, "trials_small") X(TRIALS_FULL, "trials_full") X(TRIALS_ALL, "trials_all")      \
+    X(DA_LDS, "da_lds") X(DA_REGS, "da_regs")                                                      \
+    X(IPM_ITER_SYNC, "ipm_iter_sync") X(IPM_ITER_TAIL, "ipm_iter_tail")                            \
+    X(LS_SEQUENTIAL, "ls_sequential") X(LS_SPECULATIVE, "ls_speculative") X(LS_ONE_ROUND, "ls_one_round") \
+    X(RESTO_INLINE, "resto_inline") X(RESTO_AFTER_LOOP, "resto_after_loop")                        \
+    X(RESTO_ONE_ROUND, "resto_one_round") X(RESTO_ROUNDS, "resto_rounds")                          \
+    X(RESTO_SECOND_STREAM, "resto_second_stream") X(RESTO_SOLVER_STREAM, "resto_solver_stream")    \
+    X(IPM_RESTARTS, "ipm_restarts") X(SOLVE_MONOTONE, "solve_monotone") X(SOLVE_ADAPTIVE, "solve_adaptive") \
+    X(PC_BUILDS, "pc_builds") X(PC_REGROWS, "pc_regrows") X(PC_FALLBACKS, "pc_fallbacks")          \
+    X(CAND_SMALL, "cand_small") X(CAND_FULL, "cand_full") X(CAND_CHUNKS, "cand_chunks")            \
+    X(MOTION_CHUNKS, "motion_chunks")                                                              \
+    X(TRACK_ROW, "track_row") X(TRACK_ROW_REC, "track_row_rec") X(TRACK_ROW_EPISODE, "track_row_episode") \
+    X(TRACK_SERIAL, "track_serial") X(TRACK_SERIAL_REC, "track_serial_rec")                        \
+    X(TRACK_SERIAL_EPISODE, "track_serial_episode")
+enum PathId {
+#define X(id, name) PATH_##id,
+    ARMOUR_PATHS(X)
+#undef X
+    PATH_N
+};
+static const char* const PATH_NAMES[] = {
+#define X(id, name) name,
+    ARMOUR_PATHS(X)
+#undef X
+};
+static_assert(PATH_N == ARMOUR_PATH_COUNT, "include/armour_hip.h documents every path counter");
+
 // capacity retry: a quarter of the workgroups, each with four workgroups' buffers
 constexpr int RETRY_SCALE = 4;
 
@@ -213,7 +252,7 @@ struct armour_planner {
     unsigned long long* d_prof = nullptr;  // per-op [cycles, terms] (Settings::profile)
     double* d_dump = nullptr;              // op-by-op state of job 0 (Settings::dump_ops)
     double last_kernel_ms = 0, last_bytes = 0;
-    double last_span_ms = -1;  // device-clock execution span of the last reach launch (armour_get_reach_span)
+    double last_span_ms = -1;  // device-clock execution span of the last batch's first reach launch (armour_get_reach_span)
     int wall_khz = 0;          // hipDeviceAttributeWallClockRate
     unsigned long long* d_occ = nullptr;   // [8] reach capacity use of the last launch (ReachCounters)
     unsigned* d_done = nullptr;            // workgroups finished in the current reach launch
@@ -316,6 +355,8 @@ struct armour_planner {
     bool ept_scaled = false;
     GrowSet ep_tracked;
     std::vector<void*> allocs;
+    long long paths[PATH_N] = {};  // the path census (armour_get_path_counts)
+    void took(PathId c, long long n = 1) { paths[c] += n; }
 
     template <class T>
     int alloc(T** p, size_t n) {
@@ -763,7 +804,8 @@ static int upload_worlds(armour_planner* p, int W, const armour_world* worlds, b
     NlpDev& d = p->d;
     d.W = W;
     d.O = O;
-    d.Ow = mixed ? p->d_Ow : nullptr;
+    d.Ow = mixed ? p->d_Ow : nullptr;  // (what KSEL reads: every solver kernel of this batch is of this kind)
+    p->took(mixed ? PATH_BATCH_MIXED : PATH_BATCH_UNIFORM);
     d.pcready = 0;
     d.m = d.nt + p->T * p->NJ * O + NF * 4;
     d.R = d.m + NF;
@@ -812,8 +854,11 @@ static int lane_shape_for(armour_planner* p, long bundles) {
     p->last_shape = shape;
     return shape;
 }
-static void launch_lane(int shape, bool sq, int grid, hipStream_t s, const RobotParams* rp, const lane::LaneArgs& la,
-                        const ReachOut& ro) {
+static void launch_lane(armour_planner* p, int shape, bool sq, int grid, hipStream_t s, const RobotParams* rp,
+                        const lane::LaneArgs& la, const ReachOut& ro) {
+    p->took(shape == 1 ? PATH_REACH_LANE_DENSE : PATH_REACH_LANE_WIDE);
+    p->took(sq ? PATH_REACH_SQ : PATH_REACH_SQRT);
+    if (s != p->stream) p->took(PATH_REACH_CU_MASKED);
     auto k = shape == 1 ? (sq ? lane::lane_reach_kernel<lane::LaneDense> : lane::lane_reach_kernel<lane::LaneDenseSqrt>)
                         : (sq ? lane::lane_reach_kernel<lane::LaneWide> : lane::lane_reach_kernel<lane::LaneWideSqrt>);
     hipLaunchKernelGGL(k, dim3(grid), dim3(lane::LT), 0, s, rp, la, ro);
@@ -856,12 +901,15 @@ static int run_reach(armour_planner* p) {
         const int shape = lane_shape_for(p, bundles);
         const long slots = std::min<long>(p->lane_slots[shape], p->lane_grid);
         const int lg = (int)(bundles < slots ? bundles : slots);
-        launch_lane(shape, p->sq, lg, rs, p->d_rp, la, p->ro);
+        launch_lane(p, shape, p->sq, lg, rs, p->d_rp, la, p->ro);
     } else {
         // a batch that fits the chip in one round at two jobs per CU takes the wide kernel
         const bool wide = jobs <= (long)REACH_WIDE_PER_CU * p->ncu && !p->set.job_narrow;
         auto k = wide ? (p->sq ? reach_kernel<REACH_WIDE_THREADS, true> : reach_kernel<REACH_WIDE_THREADS, false>)
                       : (p->sq ? reach_kernel<REACH_THREADS, true> : reach_kernel<REACH_THREADS, false>);
+        p->took(wide ? PATH_REACH_JOB_256 : PATH_REACH_JOB_128);
+        p->took(p->sq ? PATH_REACH_SQ : PATH_REACH_SQRT);
+        if (rs != p->stream) p->took(PATH_REACH_CU_MASKED);
         hipLaunchKernelGGL(k, dim3(grid), dim3(wide ? REACH_WIDE_THREADS : REACH_THREADS), 0, rs, p->d_rp, ra, p->ro);
     }
     HIPCK(hipGetLastError());
@@ -913,7 +961,8 @@ static int run_reach(armour_planner* p) {
         HIPCK(hipMemsetAsync(p->ro.err, 0, sizeof(int) * p->W, rs));
         const long bundles = ((long)retry.size() * p->T + lane::LG - 1) / lane::LG;
         const long g = std::max(p->lane_grid, RETRY_SCALE) / RETRY_SCALE;
-        launch_lane(p->last_shape, p->sq, (int)(bundles < g ? bundles : g), rs, p->d_rp, la, p->ro);
+        p->took(PATH_REACH_RETRY);
+        launch_lane(p, p->last_shape, p->sq, (int)(bundles < g ? bundles : g), rs, p->d_rp, la, p->ro);
         HIPCK(hipGetLastError());
         HIPCK(hipEventRecord(p->ev[5], rs));
         HIPCK(hipEventSynchronize(p->ev[5]));
@@ -960,6 +1009,7 @@ static void ensure_plane_cache(armour_planner* p) {
     // speculative searches that read only the cache (run_solver, ipm_loop, run_resto).
     bool fits = false;
     for (int attempt = 0; attempt < 3; attempt++) {
+        p->took(attempt == 0 ? PATH_PC_BUILDS : PATH_PC_REGROWS);
         hipLaunchKernelGGL(KSEL(plane_cache_kernel), dim3(p->T, p->W), dim3(EVAL_THREADS), 0, p->stream, d);
         if (hipMemcpyAsync(p->h_pcnext, d.pcnext, sizeof(unsigned), hipMemcpyDeviceToHost, p->stream) != hipSuccess ||
             hipStreamSynchronize(p->stream) != hipSuccess)
@@ -985,6 +1035,7 @@ static void ensure_plane_cache(armour_planner* p) {
         d.pc_pool = grow;
     }
     d.pcready = fits ? 1 : 0;
+    if (!fits) p->took(PATH_PC_FALLBACKS);
 }
 
 static int nside_count(const armour_planner* p) {
@@ -1004,23 +1055,28 @@ static bool eval_small_fits(const armour_planner* p) {
 static void launch_eval(armour_planner* p, dim3 grid, const NlpDev& d, const Round& r, int mode, bool cached = true, hipStream_t s = nullptr) {
     if (!s) s = p->stream;
     const bool c = cached && d.pcready && d.O > 0;
+    p->took(c ? PATH_EVAL_CACHED : PATH_EVAL_FULL_SCAN);
     if (c && eval_small_fits(p) && eval_pair_doubles(p->NJ * d.O) <= UB_S) {
+        p->took(PATH_EVAL_SMALL);
         hipLaunchKernelGGL(KSEL(eval_kernel_small), grid, dim3(EVAL_THREADS), 0, s, d, r, mode);
         return;
     }
     if (d.Ow) {  // a mixed batch (fp64 ARMOUR planner: upload_worlds)
+        p->took(PATH_EVAL_MX);
         hipLaunchKernelGGL(c ? eval_kernel_mx<true> : eval_kernel_mx<false>, grid, dim3(EVAL_THREADS), 0, s, d, r, mode);
         return;
     }
     auto k = p->set.eval_f32 ? (d.armtd ? eval_kernel_t<float, true, false> : eval_kernel_t<float, false, false>)
                          : c ? (d.armtd ? eval_kernel_t<double, true, true> : eval_kernel_t<double, false, true>)
                              : (d.armtd ? eval_kernel_t<double, true, false> : eval_kernel_t<double, false, false>);
+    p->took(p->set.eval_f32 ? (d.armtd ? PATH_EVAL_ARMTD_F32 : PATH_EVAL_F32) : (d.armtd ? PATH_EVAL_ARMTD_F64 : PATH_EVAL_F64));
     hipLaunchKernelGGL(k, grid, dim3(EVAL_THREADS), 0, s, d, r, mode);
 }
 // the values of the K remaining trials of n listed worlds (eval_trials_kernel), from the small-capacity
 // kernel when the (trial, pair) keys fit its buffer too
 static void launch_trials(armour_planner* p, int n, const NlpDev& d, const Round& r) {
     const bool small = eval_small_fits(p) && r.K * p->NJ * d.O <= UB_TS;
+    p->took(small ? PATH_TRIALS_SMALL : PATH_TRIALS_FULL);
     hipLaunchKernelGGL(small ? KSEL(eval_trials_small) : KSEL(eval_trials_kernel), dim3(p->T, n), dim3(EVAL_THREADS), 0, p->stream, d, r);
 }
 
@@ -1029,10 +1085,13 @@ static void launch_trials(armour_planner* p, int n, const NlpDev& d, const Round
 // the sync-free tail's one-round form over all max_ls trials, round 0's included (eval_trials_all,
 // ipm_world_Cs_all with pass B's world step); else the K trials that remain after round 0.
 static void launch_spec_round(armour_planner* p, int n, const NlpDev& d, const Round& r, bool all) {
-    if (all)
+    p->took(all ? PATH_LS_ONE_ROUND : PATH_LS_SPECULATIVE);
+    if (all) {
+        p->took(PATH_TRIALS_ALL);
         hipLaunchKernelGGL(KSEL(eval_trials_all), dim3(p->T, n), dim3(EVAL_THREADS), 0, p->stream, d, r);
-    else
+    } else {
         launch_trials(p, n, d, r);
+    }
     hipLaunchKernelGGL(KSEL(ipm_rows_Cs), dim3(d.nblk, n * r.K), dim3(ROW_THREADS), 0, p->stream, d, r);
     hipLaunchKernelGGL(all ? KSEL(ipm_world_Cs_all) : KSEL(ipm_world_Cs), dim3(n), dim3(64), 0, p->stream, d, r);
     launch_eval(p, dim3(p->T, n), d, r, EVAL_CHOSEN);
@@ -1042,6 +1101,9 @@ static void launch_spec_round(armour_planner* p, int n, const NlpDev& d, const R
 // Gauss-Newton pass and world step, the values of all r.K = max_ls trials, their sums, the tests in
 // trial order (resto_world_Vs), then the chosen trial in full.
 static void launch_resto_round(armour_planner* p, hipStream_t s, int nb, const NlpDev& d, const Round& r) {
+    p->took(PATH_RESTO_ONE_ROUND);
+    p->took(s != p->stream ? PATH_RESTO_SECOND_STREAM : PATH_RESTO_SOLVER_STREAM);
+    p->took(PATH_TRIALS_ALL);
     hipLaunchKernelGGL(KSEL(resto_rows_G), dim3(d.nblk, nb), dim3(ROW_THREADS), 0, s, d, r);
     hipLaunchKernelGGL(KSEL(resto_world_G), dim3(nb), dim3(64), 0, s, d, r);
     hipLaunchKernelGGL(KSEL(eval_trials_all), dim3(p->T, nb), dim3(EVAL_THREADS), 0, s, d, r);
@@ -1214,6 +1276,7 @@ static int ipm_loop(armour_planner* p, int nrun) {
         }
         const int nb = std::min(W0, bound);
         ub = nb;  // the phase keeps at most the worlds it took
+        p->took(PATH_RESTO_INLINE);
         launch_resto_round(p, s, nb, d, round_resto_inline(p, PL, RL, conc));
         return 0;
     };
@@ -1265,6 +1328,7 @@ static int ipm_loop(armour_planner* p, int nrun) {
     for (int it = 0; it <= d.opt.max_iter && nrun > 0; it++) {
         const bool tl = it > 0 && p->spec && d.pcready && nrun <= p->set.tail_worlds;
         const Round di{Li[cur], tl ? cnt_at(p, CNT_ITER, it) : nullptr};
+        p->took(tl ? PATH_IPM_ITER_TAIL : PATH_IPM_ITER_SYNC);
         // pass D of the previous iteration (accept its trial point) shares one sweep over the rows
         // with this iteration's pass A
         if (it == 0) {
@@ -1273,6 +1337,7 @@ static int ipm_loop(armour_planner* p, int nrun) {
         } else {
             // the LDS-accumulator form for grids of several blocks per CU (nlp_kernels.hip rows_DA_body)
             const bool wide = p->set.da_lds && (long)d.nblk * nrun >= 4L * p->ncu;
+            p->took(wide ? PATH_DA_LDS : PATH_DA_REGS);
             hipLaunchKernelGGL(wide ? KSEL(ipm_rows_DA_lds) : KSEL(ipm_rows_DA), dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, d, di);
             hipLaunchKernelGGL(KSEL(ipm_world_DA), dim3(nrun), dim3(64), 0, p->stream, d, di, ns);
         }
@@ -1318,6 +1383,7 @@ static int ipm_loop(armour_planner* p, int nrun) {
         } else if (nsearch > 0) {
             for (int ls = 1; ls < d.opt.max_ls; ls++) {
                 const Round dc = round_next(p, it, RL, ls, Ls);
+                p->took(PATH_LS_SEQUENTIAL);
                 launch_eval(p, dim3(p->T, nsearch), d, dc, EVAL_TRIAL);
                 hipLaunchKernelGGL(KSEL(ipm_rows_C), dim3(d.nblk, nsearch), dim3(ROW_THREADS), 0, p->stream, d, dc);
                 hipLaunchKernelGGL(KSEL(ipm_world_C), dim3(nsearch), dim3(64), 0, p->stream, d, dc);
@@ -1355,6 +1421,7 @@ static int run_resto(armour_planner* p, const int* list, int n) {
         int* L[2] = {const_cast<int*>(list), p->d_lists + 3 * p->Wmax};
         int nb = n;  // grid bound: the last count the host knows (counts only fall)
         for (int k = 0; k < guard; k++) {
+            p->took(PATH_RESTO_AFTER_LOOP);
             launch_resto_round(p, p->stream, nb, d, round_resto_iter(p, k, L));
             HIPCK(hipEventRecord(p->tev[k & 1], p->stream));
             HIPCK(hipGetLastError());
@@ -1370,6 +1437,9 @@ static int run_resto(armour_planner* p, const int* list, int n) {
     }
     const Round dr = round_resto_seq(list);
     for (int k = 0; k < guard; k++) {
+        p->took(PATH_RESTO_AFTER_LOOP);
+        p->took(PATH_RESTO_ROUNDS);
+        p->took(PATH_RESTO_SOLVER_STREAM);
         hipLaunchKernelGGL(KSEL(resto_rows_G), dim3(d.nblk, n), dim3(ROW_THREADS), 0, p->stream, d, dr);
         hipLaunchKernelGGL(KSEL(resto_world_G), dim3(n), dim3(64), 0, p->stream, d, dr);
         HIPCK(hipStreamSynchronize(p->stream));
@@ -1394,6 +1464,7 @@ static int run_solver(armour_planner* p) {
     int* Lr = p->d_lists + 2 * p->Wmax;     // worlds of a restoration phase
     ensure_plane_cache(p);
     const NlpDev& d = p->d;
+    p->took(d.opt.mu_strategy == 0 ? PATH_SOLVE_MONOTONE : PATH_SOLVE_ADAPTIVE);
     Round r0;  // ipm_world_init fills the first iteration list with every world
     r0.wl_run = Li0;
     hipLaunchKernelGGL(ipm_world_init, dim3((W + 63) / 64), dim3(64), 0, p->stream, d, r0);
@@ -1418,6 +1489,7 @@ static int run_solver(armour_planner* p) {
         HIPCK(hipStreamSynchronize(p->stream));
         const int ni = fl[FLAG_RUN];
         if (ni == 0) break;
+        p->took(PATH_IPM_RESTARTS, ni);
         hipLaunchKernelGGL(KSEL(ipm_rows_init), dim3(d.nblk, ni), dim3(ROW_THREADS), 0, p->stream, d, Round{Li0});
         rc = ipm_loop(p, ni);
     }
@@ -1833,6 +1905,8 @@ int armour_eval_candidates(armour_planner* p, int N, const double* x, double* co
     c.N = N;
     HIPCK(hipMemcpyAsync(const_cast<double*>(c.x), x, sizeof(double) * n * NF, hipMemcpyHostToDevice, p->stream));
     const dim3 grid(p->T, W, (N + CAND_KC - 1) / CAND_KC);
+    p->took(eval_small_fits(p) ? PATH_CAND_SMALL : PATH_CAND_FULL);
+    p->took(PATH_CAND_CHUNKS, grid.z);
     if (eval_small_fits(p))
         hipLaunchKernelGGL(KSEL(cand_rows_small), grid, dim3(EVAL_THREADS), 0, p->stream, d, c);
     else
@@ -1875,6 +1949,7 @@ static void launch_motion(armour_planner* p, const double* traj, const double* w
     a.t1 = t1;
     a.pval = p->mo_pval;
     a.pidx = p->mo_pidx;
+    p->took(PATH_MOTION_CHUNKS, S);
     hipLaunchKernelGGL(motion_check_kernel, dim3(S, p->W), dim3(MOTION_THREADS), 0, p->stream, a);
     hipLaunchKernelGGL(motion_finish_kernel, dim3(p->W), dim3(64), 0, p->stream, a, p->mo_clear, p->mo_where);
 }
@@ -1956,6 +2031,8 @@ static int track_launch(armour_planner* p, TrackArgs a, const TrackExtra& x) {
     const dim3 grid((unsigned)(serial ? (NR + TRACK_THREADS - 1) / TRACK_THREADS : (NR + TRACK_ROWS - 1) / TRACK_ROWS));
     const dim3 block(TRACK_THREADS);
     HIPCK(hipEventRecord(p->tr_ev[0], p->stream));
+    p->took(x.win ? (serial ? PATH_TRACK_SERIAL_EPISODE : PATH_TRACK_ROW_EPISODE)
+            : x.rec ? (serial ? PATH_TRACK_SERIAL_REC : PATH_TRACK_ROW_REC) : (serial ? PATH_TRACK_SERIAL : PATH_TRACK_ROW));
     if (x.win && serial)
         hipLaunchKernelGGL(track_serial_episode_kernel, grid, block, 0, p->stream, a, x);
     else if (x.win)
@@ -2466,6 +2543,14 @@ int armour_get_reach_occupancy(armour_planner* p, long long* used, long long* ca
     }
     return ARMOUR_OCC_COUNT;
 }
+
+int armour_get_path_counts(armour_planner* p, long long* counts, int n) {
+    if (!p) return fail(ARMOUR_E_ARG, "null planner");
+    for (int k = 0; counts && k < n && k < PATH_N; k++) counts[k] = p->paths[k];
+    return PATH_N;
+}
+
+const char* armour_path_name(int i) { return i >= 0 && i < PATH_N ? PATH_NAMES[i] : nullptr; }
 
 int armour_get_reach_program(const armour_planner* p, int* codes, int capacity) {
     DeviceScope device_scope(p);

@@ -552,6 +552,42 @@ int armour_get_reach_program(const armour_planner* p, int* codes, int capacity);
 #define ARMOUR_OCC_COUNT 7
 int armour_get_reach_occupancy(armour_planner* p, long long* used, long long* caps, int n);
 int armour_get_reach_profile(armour_planner* p, unsigned long long* cycles_terms, int capacity);
+/* Path census: which kernels and loop forms the host chose, counted where it chooses (a setting alone
+ * does not decide: batch size, capacities found by the last reach, the plane cache and the CU count do
+ * too). armour_get_path_counts writes the first n counters (k < n, k < ARMOUR_PATH_COUNT) and returns
+ * ARMOUR_PATH_COUNT; armour_path_name(i) is counter i's name (null outside 0 .. ARMOUR_PATH_COUNT - 1).
+ * The counters are cumulative since the planner was created, host integers only (no device read, no
+ * synchronisation), and belong to the handle (one handle per thread). In index order:
+ *   batches           batch_uniform, batch_mixed (uploads; a mixed batch runs the _mx instantiation of every
+ *                     solver, candidate and plane-cache kernel, a uniform or ARMTD batch the plain one; an
+ *                     episode's batch is mixed)
+ *   reach launches    reach_job_256, reach_job_128 (per-job engine, 256 / 128 threads), reach_lane_wide,
+ *                     reach_lane_dense (bundle engine shapes, a retry included), reach_retry (capacity-retry
+ *                     launches), reach_sq, reach_sqrt (squared-norm / sqrt kernels), reach_cu_masked (launches
+ *                     on a CU-masked reach stream, ARMOUR_REACH_CU_RESERVE)
+ *   evaluations       eval_small (eval_kernel_small), eval_f64, eval_f32 (eval_kernel_t), eval_armtd_f64,
+ *                     eval_armtd_f32 (its ARMTD instantiations), eval_mx (eval_kernel_mx); and of all of
+ *                     them: eval_cached (read the plane cache), eval_full_scan (the 36-plane scan)
+ *   trial values      trials_small (eval_trials_small), trials_full (eval_trials_kernel), trials_all
+ *                     (eval_trials_all)
+ *   row pass DA       da_lds (ipm_rows_DA_lds), da_regs (ipm_rows_DA), per iteration after a loop's first
+ *   iterations        ipm_iter_sync (synchronised), ipm_iter_tail (sync-free tail)
+ *   line search       ls_sequential (rounds after round 0, one by one), ls_speculative (one round over the
+ *                     remaining K trials), ls_one_round (the tail's one round over all trials)
+ *   restoration       phase iterations: resto_inline (inside the interior-point loop), resto_after_loop;
+ *                     resto_one_round, resto_rounds (the search's form); resto_second_stream (queued beside
+ *                     an interior-point iteration), resto_solver_stream
+ *   restarts          ipm_restarts (worlds the host collected to restart the interior point)
+ *   solves            solve_monotone, solve_adaptive (the barrier strategy)
+ *   plane cache       pc_builds (first builds), pc_regrows (builds repeated on a larger pool), pc_fallbacks
+ *                     (builds that left the solve on the full scan)
+ *   candidates        cand_small, cand_full (calls by kernel), cand_chunks (candidate chunks, summed)
+ *   motion check      motion_chunks (sample blocks per world, summed over calls and episode steps)
+ *   tracking          track_row, track_row_rec, track_row_episode, track_serial, track_serial_rec,
+ *                     track_serial_episode (launches of the plain, recording and episode kernels) */
+#define ARMOUR_PATH_COUNT 50
+int armour_get_path_counts(armour_planner* p, long long* counts, int n);
+const char* armour_path_name(int i);
 /* Certified plane cache of the current reach sets, built on demand: for k < n
  * writes [0] planes kept over all (world, t, link, obstacle) pairs, [1] pairs, [2] (world, t) blocks
  * whose cache region held every kept plane, [3] blocks, [4] most planes kept for one pair,
@@ -560,10 +596,12 @@ int armour_get_reach_profile(armour_planner* p, unsigned long long* cycles_terms
  * After a mixed batch [0], [1] and [4] count only the pairs that exist (NJ * O_w per block of world w). */
 #define ARMOUR_PC_COUNT 7
 int armour_get_plane_cache_stats(armour_planner* p, long long* out, int n);
-/* Execution span of the last reach launch on the device clock (wall_clock64): from the first
- * workgroup's start to the last workgroup's end, the duration rocprofv3 --kernel-trace reports
- * for the kernel (the reach_kernel_ms of armour_timing, HIP events around the launch, also counts
- * the time the launch waits for CUs held by other planners' kernels). Milliseconds. */
+/* Execution span of the last batch's first reach launch on the device clock (wall_clock64): from
+ * the first workgroup's start to the last workgroup's end, the duration rocprofv3 --kernel-trace
+ * reports for the kernel (the reach_kernel_ms of armour_timing, HIP events around the launch, also
+ * counts the time the launch waits for CUs held by other planners' kernels). Milliseconds. When a
+ * capacity retry ran (occupancy [5] > 0), the span is still the first launch's, the one over the whole
+ * batch, as reach_kernel_ms and the occupancy are; the retry's own launch is not included. */
 int armour_get_reach_span(armour_planner* p, double* span_ms);
 /* op-by-op state of job 0 (world 0, t = 0) of the last reach: per op 8 doubles [monomial count,
  * block size, centre[0..2], nominal ind[0], interval ind[0], sum|m|[0]] of the op's output, when

@@ -28,6 +28,7 @@ ITEMS = ("link_generators", "torque_radius", "link_counts", "torque_counts", "g_
 # the third k is neither symmetric nor evenly spaced, so changes that cancel at the first two show
 XS = (np.zeros(7), np.linspace(-0.7, 0.7, 7), np.array([0.31, -0.52, 0.77, -0.13, 0.64, -0.9, 0.05]))
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+PATHS = {}  # (case, shape) -> the planner's path census when run_case closed it
 
 
 class env:
@@ -108,5 +109,6 @@ def run_case(case, shape):
     """(digests [len(ITEMS), 32] uint8, dump of lane 0 [nops, 8], reach_bytes, {item: array})"""
     P, worlds = planner(case, shape)
     out, nbytes = reach_outputs(P, worlds)
+    PATHS[case, shape] = P.path_counts()
     P.close()
     return digests(out), out["dump_lane0"], nbytes, out

@@ -22,6 +22,7 @@ CASES = {"t2": (1, 2, 2, 5300), "t66": (1, 66, 2, 5300), "b100": (3, 100, 20, 51
 VARIANTS = {"wide": ("lane", "wide"), "dense": ("lane", "dense"), "job": ("job", None)}
 ITEMS = C.ITEMS
 GOLDEN = C.GOLDEN
+PATHS = {}  # (case, variant, fallback) -> the planner's path census when run_case closed it
 
 
 def worlds_of(case):
@@ -38,6 +39,7 @@ def run_case(case, variant, fallback=False):
                ARMOUR_SQ_THRESHOLD="0" if fallback else None):
         P = A.Planner(T=T, max_obstacles=O, max_worlds=len(worlds))
     out, nbytes = C.reach_outputs(P, worlds)
+    PATHS[case, variant, fallback] = P.path_counts()
     P.close()
     return out, nbytes
 

@@ -50,6 +50,52 @@ def test_library_loads_and_binds(lib_path):
         assert hasattr(L, name)
 
 
+def test_path_census_names(lib_path):
+    """armour_path_name / armour_get_path_counts (no device needed): ARMOUR_PATH_COUNT unique names, null
+    outside the range, each documented by name in the header's one list, and Planner.path_counts builds
+    its dict from the library's names, not from a list of its own"""
+    import ctypes
+    import inspect
+
+    L = A.lib()
+    header = open(HEADER).read()
+    count = int(re.search(r"#define\s+ARMOUR_PATH_COUNT\s+(\d+)", header).group(1))
+    names = [L.armour_path_name(i) for i in range(count)]
+    assert all(n is not None for n in names)
+    names = [n.decode() for n in names]
+    assert len(set(names)) == count and all(re.fullmatch(r"[a-z][a-z0-9_]*", n) for n in names), names
+    assert L.armour_path_name(count) is None and L.armour_path_name(-1) is None
+    assert L.armour_get_path_counts(None, None, 0) == A.ARMOUR_E_ARG  # the count comes with a planner only
+    doc = re.search(r"/\* Path census.*?\*/", header, flags=re.S).group(0)
+    missing = [n for n in names if not re.search(r"\b%s\b" % n, doc)]
+    assert not missing, missing
+    src = inspect.getsource(A.Planner.path_counts)
+    assert "armour_path_name" in src and "armour_get_path_counts" in src
+    assert not any('"%s"' % n in src for n in names)
+
+    class FakeLib:  # the binding against a library that reports three counters
+        armour_last_error = staticmethod(lambda: b"")
+
+        @staticmethod
+        def armour_get_path_counts(h, out, n):
+            for i in range(min(n, 3)):
+                out[i] = 10 + i
+            return 3
+
+        @staticmethod
+        def armour_path_name(i):
+            return (b"a", b"b", b"c")[i]
+
+    P = A.Planner.__new__(A.Planner)
+    P.h = ctypes.c_void_p(1)
+    real, A._LIB = A._LIB, FakeLib
+    try:
+        assert A.Planner.path_counts(P) == {"a": 10, "b": 11, "c": 12}
+    finally:
+        P.h = None
+        A._LIB = real
+
+
 def test_no_cpu_fallback_in_product():
     """The product path never imports or links the oracle / emulation."""
     pkg = os.path.join(ROOT, "armour-dev_amd")

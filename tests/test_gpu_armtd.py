@@ -14,6 +14,7 @@ import armour_amd as A
 import boundary_worlds as B
 from conftest import engine
 from oracle import OracleArmtd
+from paths import assert_paths, engine_paths
 from test_armtd import load, world
 
 pytestmark = pytest.mark.gpu
@@ -53,6 +54,11 @@ def test_armtd_parity(eng):
         tol = 1e-8 if (r["status"] == 0 or r["feasible"]) else 1e-3
         np.testing.assert_allclose(r["k_opt"], ro["k_opt"], rtol=0, atol=tol, err_msg=f"world {w}")
         np.testing.assert_allclose(P.constraints(w), R.eval(r["k_opt"], jac=False), rtol=0, atol=1e-7)
+    # the ARMTD instantiation of the evaluation kernel alone, round-by-round searches (no speculative
+    # rounds on this planner), on the engine asked for
+    assert_paths(P.path_counts(), ran=("eval_armtd_f64", "batch_uniform") + engine_paths(eng)["ran"],
+                 not_ran=("eval_f64", "eval_f32", "eval_armtd_f32", "eval_small", "eval_mx", "trials_small", "trials_full",
+                          "trials_all", "ls_speculative", "ls_one_round", "ipm_iter_tail") + engine_paths(eng)["not_ran"])
 
 
 def write_armtd_in(path, q0, qd0, q_des, tables, k_range, obstacles):

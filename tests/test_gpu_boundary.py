@@ -18,6 +18,7 @@ import armour_amd as A
 import boundary_worlds as B
 from conftest import engine
 from oracle import OraclePlanner
+from paths import assert_paths, engine_paths
 from test_boundary import load, robot_name, world
 from test_gpu_drop_in import run, write_input
 
@@ -83,6 +84,7 @@ def compare_set(name, min_near, eng):
         assert r["feasible"] == bool(fx["feasible"][w]) and abs(r["iterations"] - int(fx["iterations"][w])) <= it_tol
         infeasible += not r["feasible"]
     assert infeasible >= W / 4
+    assert_paths(P.path_counts(), **engine_paths(eng))
     return near, infeasible
 
 

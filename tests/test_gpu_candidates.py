@@ -21,6 +21,7 @@ import boundary_worlds as B
 from armour_amd.robots import KINOVA
 from conftest import engine
 from oracle import OraclePlanner
+from paths import assert_paths, engine_paths
 from test_boundary import load, world
 
 pytestmark = pytest.mark.gpu
@@ -243,6 +244,9 @@ def test_full_size_and_both_variants():
             P = A.Planner(T=T, max_obstacles=O, max_worlds=1)
         P.reach([w0])
         outs.append(P.eval_candidates(X))
+        # 33 candidates: two chunks of 32, on the small kernels unless ARMOUR_EVAL_FULL asks for the full ones
+        mine, other = ("cand_small", "cand_full") if full == "0" else ("cand_full", "cand_small")
+        assert_paths(P.path_counts(), exactly={mine: 1, other: 0, "cand_chunks": 2, "pc_builds": 1})
         P.close()
         check_against_oracle(outs[-1], 0, ref, f"full={full}")
     for k in ("cost", "violation", "feasible", "best"):
@@ -262,6 +266,8 @@ def test_fetch_links():
     P.reach(worlds)
     assert P.NJ > 7
     out = P.eval_candidates(X)
+    assert_paths(P.path_counts(), ran=(("cand_small", "cand_full"),) + engine_paths("lane")["ran"],
+                 not_ran=engine_paths("lane")["not_ran"])
     for w in range(2):
         R = OraclePlanner(*worlds[w], T=T, threads=8, robot=rstruct)
         R.reach()
@@ -329,6 +335,7 @@ def test_errors(small):
     assert _raw(P, 4, X, W) == A.ARMOUR_E_STATE
     with pytest.raises(A.ArmourError, match="plane cache is unavailable"):
         P.eval_candidates(X)
+    assert_paths(P.path_counts(), not_ran=("pc_builds", "cand_small", "cand_full", "cand_chunks"))  # refused before any launch
     # without obstacles there is nothing to cache: the call works
     free = [w[:4] + (w[4][:0],) for w in worlds[:2]]
     P.reach(free)

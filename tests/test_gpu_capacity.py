@@ -8,6 +8,7 @@ import pytest
 
 import armour_amd as A
 from conftest import engine
+from paths import assert_paths, engine_paths
 
 pytestmark = pytest.mark.gpu
 DEBUG = (np.array([-1.0, -1, -1, -1, 1, 1, 1]), np.array([1.0, 1, 1, -1, -1, -1, -1]), np.full(7, 2.0))
@@ -39,6 +40,7 @@ def test_full_range_headroom():
             worst[k] = (max(u, worst.get(k, (0, c))[0]), c)
     print({k: f"{u}/{c}" for k, (u, c) in worst.items()})
     assert worst["worlds_retried"][0] == 0
+    assert_paths(P.path_counts(), ran=engine_paths("lane")["ran"], not_ran=engine_paths("lane")["not_ran"] + ("reach_retry",))
     for k in ("arena_hashes", "arena_rows", "operator_terms", "link_monomials", "torque_monomials"):
         assert worst[k][0] < 0.8 * worst[k][1], (k, worst[k])
 
@@ -51,6 +53,7 @@ def test_debug_state_headroom():
     occ = P.occupancy()
     print(occ)
     assert res[0]["error"] == 0 and occ["worlds_retried"][0] == 0
+    assert_paths(P.path_counts(), ran=engine_paths("lane")["ran"], not_ran=engine_paths("lane")["not_ran"] + ("reach_retry",))
     assert occ["arena_rows"][0] < 0.8 * occ["arena_rows"][1]
 
 
@@ -79,14 +82,21 @@ def test_retry_and_per_world_isolation():
     for w in worlds:
         P.plan([w])
         use.append(P.occupancy()["arena_rows"][0])
+    assert_paths(P.path_counts(), ran=engine_paths("lane")["ran"], not_ran=engine_paths("lane")["not_ran"] + ("reach_retry",))
     P.close()
     light, heavy = max(use[0], use[2]), use[1]
     assert all(r["error"] == 0 for r in ref)
 
     P = _planner(T, O, 3, ccap=light // 2)
-    res, _ = P.plan(worlds)
+    res, tm = P.plan(worlds)
     occ = P.occupancy()
     assert occ["worlds_retried"][0] == 3 and occ["worlds_failed"][0] == 0
+    # exactly one retry launch after the one first launch, and the span armour_get_reach_span reports is
+    # the first launch's (include/armour_hip.h): positive and within the reach phase, which held both
+    assert_paths(P.path_counts(), exactly={"reach_retry": 1, ("reach_lane_wide", "reach_lane_dense"): 2}, **engine_paths("lane"))
+    span = P.reach_span_ms()
+    assert span == tm["reach_span_ms"]
+    assert 0.0 < span <= tm["reach_ms"] + 0.05, (span, tm)
     for r, r0 in zip(res, ref):
         assert r["error"] == 0 and np.array_equal(r["k_opt"], r0["k_opt"]) and r["iterations"] == r0["iterations"]
     P.close()
@@ -97,6 +107,7 @@ def test_retry_and_per_world_isolation():
     res, _ = P.plan(worlds)
     occ = P.occupancy()
     assert occ["worlds_retried"][0] == 3 and occ["worlds_failed"][0] == 1
+    assert_paths(P.path_counts(), exactly={"reach_retry": 1}, **engine_paths("lane"))
     assert res[1]["error"] == A.ARMOUR_E_CAPACITY and not res[1]["feasible"] and res[1]["status"] == 3
     for w in (0, 2):
         assert res[w]["error"] == 0 and np.array_equal(res[w]["k_opt"], ref[w]["k_opt"])

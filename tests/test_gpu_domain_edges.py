@@ -17,6 +17,7 @@ import armour_amd as A
 import domain_edges as DE
 from conftest import engine
 from oracle import OraclePlanner
+from paths import assert_paths, engine_paths
 from test_domain_edges import IDENTITY, MARGIN, XS, check_identity, load_plans
 from test_oracle_containment import SLACK, containment, kinova
 
@@ -75,6 +76,7 @@ def test_multi_turn_and_branch_angles_against_the_oracle(eng):
         assert lw <= SLACK, f"{name}: a link point lies {lw:.3e} m outside its set"
         assert tw <= SLACK, f"{name}: a torque lies {tw:.3e} N m outside centre +- radius"
     print(f"{eng}: worst link excess {worst[0]:.3e} m, worst torque excess {worst[1]:.3e} N m")
+    assert_paths(P.path_counts(), **engine_paths(eng))
 
 
 class DeviceSets:
@@ -117,6 +119,7 @@ def test_shift_identity_on_the_device(eng):
         check_identity(base, DeviceSets(P, DE.shift(n)), n, report=lambda s: print(eng, s))
     for n in DE.SHIFTS:
         check_identity(base, DeviceSets(P, DE.goal_shift(n)), n, goal_only=True, report=lambda s: print(eng, s))
+    assert_paths(P.path_counts(), **engine_paths(eng))
 
 
 def _extremum_violation(P, g):
@@ -194,6 +197,7 @@ def test_limits_speeds_and_far_goals(eng):
         if forced:
             assert (out["violation"][w, :, 2] > 0).all() and not out["feasible"][w].any(), name
         assert out["feasible"][w, 0] == res[w]["feasible"], name
+    assert_paths(P.path_counts(), **engine_paths(eng))
 
 
 def _armtd_world(q_des_1):

@@ -5,6 +5,7 @@ import pytest
 
 import armour_amd as A
 from oracle import OraclePlanner
+from paths import assert_paths
 
 pytestmark = pytest.mark.gpu
 
@@ -119,6 +120,9 @@ def test_speculative_line_search_matches_sequential():
         del os.environ["ARMOUR_NO_SPEC"]
     res_q, _ = Q.plan(worlds)
     assert sum(r["evaluations"] - r["iterations"] > 1 for r in res_q) > 0, "no world backtracked"
+    assert_paths(P.path_counts(), ran=("ls_speculative", ("trials_small", "trials_full")), not_ran=("ls_sequential",))
+    assert_paths(Q.path_counts(), ran=("ls_sequential",),
+                 not_ran=("ls_speculative", "ls_one_round", "ipm_iter_tail", "trials_small", "trials_full", "trials_all"))
     for w, (a, b) in enumerate(zip(res_s, res_q)):
         assert np.array_equal(a["k_opt"], b["k_opt"]) and a["cost"] == b["cost"]
         assert (a["iterations"], a["evaluations"], a["status"], a["feasible"]) == \
@@ -156,6 +160,13 @@ def test_restoration_one_round_matches_rounds(variant, case):
         del os.environ[variant]
     res_q, _ = Q.plan(worlds)
     assert sum(r["status"] == 4 for r in res_q) >= (8 if case == "survey" else 3), "too few worlds in the restoration phase"
+    assert_paths(P.path_counts(), ran=("resto_inline", "resto_one_round"), not_ran=("resto_rounds",))
+    if variant == "ARMOUR_RESTO_ROUNDS":
+        assert_paths(Q.path_counts(), ran=("resto_rounds", "resto_after_loop"),
+                     not_ran=("resto_one_round", "resto_inline", "resto_second_stream"))
+    else:
+        assert_paths(Q.path_counts(), ran=("resto_one_round", "resto_after_loop"),
+                     not_ran=("resto_rounds", "resto_inline", "resto_second_stream"))
     for w, (a, b) in enumerate(zip(res_s, res_q)):
         assert np.array_equal(a["k_opt"], b["k_opt"]) and a["cost"] == b["cost"]
         assert (a["iterations"], a["evaluations"], a["status"], a["feasible"]) == \
@@ -185,6 +196,12 @@ def test_concurrent_restoration_matches_serial(tail):
             del os.environ["ARMOUR_RESTO_CONCURRENT"]
     (res_c, _), (res_s, _) = [P.plan(worlds) for P in planners]
     assert sum(r["status"] == 4 for r in res_s) >= 8, "too few worlds in the restoration phase"
+    # the concurrent planner queued phase iterations on its second stream, the serial one never did
+    conc, serial = planners[0].path_counts(), planners[1].path_counts()
+    assert_paths(conc, ran=("resto_second_stream", "resto_inline", "ipm_iter_tail"))
+    assert_paths(serial, ran=("resto_solver_stream", "resto_inline", "ipm_iter_tail"), not_ran=("resto_second_stream",))
+    if tail == "1000":
+        assert conc["resto_second_stream"] >= sum(r["status"] == 4 for r in res_c), conc
     for w, (a, b) in enumerate(zip(res_c, res_s)):
         assert np.array_equal(a["k_opt"], b["k_opt"]) and a["cost"] == b["cost"]
         assert (a["iterations"], a["evaluations"], a["status"], a["feasible"], a["error"]) == \
@@ -220,6 +237,12 @@ def test_solve_leaves_nothing_for_later_launches(conc):
     res, _ = PB.plan(worlds)
     assert 1 < len(worlds) <= 16 and max(r["iterations"] for r in res) > 1, "no iteration in the sync-free tail"
     assert sum(r["status"] == 4 for r in res) >= 3, "too few worlds in the restoration phase"
+    if conc is None:
+        assert_paths(PB.path_counts(), ran=("ipm_iter_tail", "resto_inline", "resto_second_stream"))
+    else:
+        assert_paths(PB.path_counts(), ran=("ipm_iter_tail", "resto_inline", "resto_solver_stream"),
+                     not_ran=("resto_second_stream",))
+    assert_paths(PA.path_counts(), not_ran=("ipm_iter_sync", "ipm_iter_tail"))  # reach alone
     for w in (1, 9):
         (ga, Ja), (gb, Jb) = PA.eval_constraints(w, x), PB.eval_constraints(w, x)
         assert np.array_equal(ga, gb) and np.array_equal(Ja, Jb), w
@@ -275,6 +298,14 @@ def test_sync_free_tail_matches_synchronised(tail, search):
                 del os.environ["ARMOUR_TAIL_WORLDS"]
                 del os.environ["ARMOUR_TAIL_SEARCH"]
         (res_s, _), (res_t, _) = [P.plan(worlds) for P in planners]
+        # the synchronised loop never ran a tail iteration or its one-round search; the other planner
+        # did (one world alone included), with the line search ARMOUR_TAIL_SEARCH asks for
+        assert_paths(planners[0].path_counts(), ran=("ipm_iter_sync",), not_ran=("ipm_iter_tail", "ls_one_round"))
+        either = (("ls_one_round", "ls_speculative"),)  # one world alone may never backtrack in the tail
+        ran = {"one": ("ls_one_round",), "rounds": ("ls_speculative",),
+               "adaptive": ("ls_one_round", "ls_speculative") if len(worlds) > 1 else either}[search]
+        assert_paths(planners[1].path_counts(), ran=("ipm_iter_tail",) + ran,
+                     not_ran=("ls_one_round",) if search == "rounds" else ())
         for w, (a, b) in enumerate(zip(res_s, res_t)):
             assert np.array_equal(a["k_opt"], b["k_opt"]) and a["cost"] == b["cost"]
             assert (a["iterations"], a["evaluations"], a["status"], a["feasible"]) == \
@@ -335,6 +366,9 @@ def test_row_pass_lds_accumulators_match_registers():
         finally:
             os.environ.pop("ARMOUR_DA_REGS", None)
     (res_l, _), (res_r, _) = [P.plan(worlds) for P in planners]
+    # (the late iterations run narrow grids, so the register form runs on both)
+    assert_paths(planners[0].path_counts(), ran=("da_lds", "da_regs"))
+    assert_paths(planners[1].path_counts(), ran=("da_regs",), not_ran=("da_lds",))
     for w, (a, b) in enumerate(zip(res_l, res_r)):
         assert np.array_equal(a["k_opt"], b["k_opt"]) and a["cost"] == b["cost"], w
         assert (a["iterations"], a["evaluations"], a["status"], a["feasible"]) == \

@@ -10,6 +10,7 @@ import pytest
 
 import armour_amd as A
 from armour_amd import robot_tables as RT
+from paths import assert_paths
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -27,7 +28,13 @@ def _eval(f32, T, O, W, seed0, robot=None, profile="default"):
             os.environ["ARMOUR_EVAL_F32"] = old
     P.reach([A.make_world(seed0 + s, O, profile=profile) for s in range(W)])
     x = np.linspace(-0.6, 0.6, 7)
-    return P, [P.eval_constraints(w, x) for w in range(W)]
+    out = [P.eval_constraints(w, x) for w in range(W)]
+    # the float instantiation on the full scan (it has no cached form) against the fp64 kernels on the cache
+    if f32:
+        assert_paths(P.path_counts(), ran=("eval_f32", "eval_full_scan"), not_ran=("eval_f64", "eval_small", "eval_cached", "pc_builds"))
+    else:
+        assert_paths(P.path_counts(), ran=(("eval_f64", "eval_small"), "eval_cached", "pc_builds"), not_ran=("eval_f32", "eval_full_scan"))
+    return P, out
 
 
 def _check(T, O, W, seed0, robot=None, torque_tol=3e-4, coll_median=1e-6, coll_max=None, profile="default"):

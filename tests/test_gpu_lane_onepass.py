@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import lane_onepass_cases as C
+from paths import assert_paths
 
 pytestmark = pytest.mark.gpu
 
@@ -23,7 +24,14 @@ def run(case, shape):
     """one run per (case, shape), shared by the tests below and left unchanged"""
     if (case, shape) not in _runs:
         _runs[case, shape] = C.run_case(case, shape)
+    assert_paths(C.PATHS[case, shape], **shape_paths(shape))
     return _runs[case, shape]
+
+
+def shape_paths(shape):
+    """assert_paths' arguments for a bundle-engine planner of one kernel shape"""
+    other = "dense" if shape == "wide" else "wide"
+    return dict(ran=("reach_lane_" + shape,), not_ran=("reach_lane_" + other, "reach_job_256", "reach_job_128"))
 
 
 @pytest.mark.parametrize("shape", C.SHAPES)
@@ -55,6 +63,7 @@ def test_capacity_retry_plans_bitwise(shape):
     P, worlds = C.planner("b", shape, dump=False)
     P.reach(worlds)
     occ = P.occupancy()
+    assert_paths(P.path_counts(), ran=shape_paths(shape)["ran"], not_ran=("reach_retry",))
     P.close()
     assert occ["worlds_retried"][0] == 0
     hcap, ccap = occ["arena_hashes"][0] // 4 + 64, occ["arena_rows"][0] // 4 + 64
@@ -63,8 +72,11 @@ def test_capacity_retry_plans_bitwise(shape):
     # it ran before the overflow, and where a bundle overflows depends on the arena size)
     out, _ = C.reach_outputs(P, worlds, dump=False)
     occ = P.occupancy()
+    # reach_outputs reaches once and plans once: one retry launch each, in the shape of the first launch
+    paths = P.path_counts()
     P.close()
     assert occ["worlds_retried"][0] == 3 and occ["worlds_failed"][0] == 0
+    assert_paths(paths, exactly={"reach_retry": 2, "reach_lane_" + shape: 4}, **shape_paths(shape))
     for k in C.ITEMS:
         if not k.startswith("dump"):
             np.testing.assert_array_equal(out[k], ref[k], err_msg=k)

@@ -21,6 +21,7 @@ import pytest
 import armour_amd as A
 import lane_onepass_cases as C
 from oracle import OraclePlanner
+from paths import assert_paths
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9  # test_gpu_parity.TOL
@@ -28,7 +29,7 @@ O = 2
 CASES = {"t2": (1, 2), "t66": (1, 66), "t66x2": (2, 66)}  # worlds, T
 SEED = 5300
 
-_gpu, _ref = {}, {}
+_gpu, _ref, _paths = {}, {}, {}
 
 
 def worlds_of(case):
@@ -49,8 +50,11 @@ def gpu(case, shape):
             for k, x in enumerate(C.XS):
                 rec[f"g_x{k}"], rec[f"J_x{k}"] = P.eval_constraints(w, x)
             out.append({k: np.array(v) for k, v in rec.items()})
+        _paths[case, shape] = P.path_counts()
         P.close()
         _gpu[case, shape] = out
+    other = "dense" if shape == "wide" else "wide"
+    assert_paths(_paths[case, shape], ran=("reach_lane_" + shape,), not_ran=("reach_lane_" + other, "reach_job_256", "reach_job_128"))
     return _gpu[case, shape]
 
 

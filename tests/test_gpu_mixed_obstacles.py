@@ -16,6 +16,7 @@ import pytest
 import armour_amd as A
 from conftest import engine
 from oracle import OraclePlanner
+from paths import assert_paths, engine_paths
 
 pytestmark = pytest.mark.gpu
 
@@ -65,6 +66,10 @@ def test_mixed_equals_uniform_batches_bitwise(batch_a):
     worlds, P, res = batch_a
     assert [P.world_obstacles(w) for w in range(len(worlds))] == COUNTS_A
     assert_bitwise(res, plan_grouped(worlds), "a")
+    # only the mixed instantiations ran: every batch of this planner was a mixed one (each solver kernel is
+    # then the _mx one), and no launch of the uniform full-capacity evaluation kernel
+    assert_paths(P.path_counts(), ran=("batch_mixed", ("eval_small", "eval_mx"), "eval_cached"),
+                 not_ran=("batch_uniform", "eval_f64", "eval_f32", "eval_armtd_f64"))
 
 
 def test_idle_row_block_bitwise():
@@ -117,6 +122,10 @@ def test_mixed_without_plane_cache_bitwise(batch_a):
         P.plane_cache_stats()
     full, _ = P.plan_mixed(worlds)
     assert_bitwise(full, res, "d")
+    # without the cache every evaluation is eval_kernel_mx on the full scan
+    assert_paths(P.path_counts(), ran=("batch_mixed", "eval_mx", "eval_full_scan", "ipm_iter_sync"),
+                 not_ran=("batch_uniform", "eval_f64", "eval_small", "eval_cached", "pc_builds", "ls_speculative",
+                          "ls_one_round", "ipm_iter_tail"))
     P.close()
 
 
@@ -165,6 +174,8 @@ def test_saved_worlds_mixed_bitwise_on_one_reach_kernel():
     with engine("narrow"):
         P = A.Planner(T=100, max_obstacles=14, max_worlds=100)
         res, _ = P.plan_mixed(worlds)
+        assert_paths(P.path_counts(), ran=("batch_mixed",) + engine_paths("narrow")["ran"],
+                     not_ran=("batch_uniform",) + engine_paths("narrow")["not_ran"])
         P.close()
         assert_bitwise(res, plan_grouped(worlds, T=100), "one reach kernel")
 

@@ -14,6 +14,7 @@ import armour_amd as A
 from armour_amd import robot_tables as RT
 from conftest import engine, golden_names, load_golden, world_of
 from oracle import OraclePlanner
+from paths import assert_paths, engine_paths
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
@@ -58,6 +59,7 @@ def test_fixture(name, eng):
     np.testing.assert_allclose(r["cost"], fx["cost"], rtol=1e-8, atol=1e-12)
     np.testing.assert_allclose(P.constraints(0), fx["g_opt"], rtol=0, atol=1e-7)
     assert tm["reach_kernel_ms"] > 0 and tm["reach_bytes"] > 0
+    assert_paths(P.path_counts(), **engine_paths(eng))  # the engine the test is named after ran, the other never
 
 
 def _compare_batch(T, O, seeds, xs, robot=None, eng=None):
@@ -86,6 +88,8 @@ def _compare_batch(T, O, seeds, xs, robot=None, eng=None):
         ro = R.plan()
         assert r["feasible"] == ro["feasible"] and r["iterations"] == ro["iterations"]
         np.testing.assert_allclose(r["k_opt"], ro["k_opt"], rtol=0, atol=1e-8)
+    assert_paths(P.path_counts(), **engine_paths(eng))  # the engine asked for ran, the other never
+    return P
 
 
 @pytest.mark.parametrize("eng", ENGINES)
@@ -99,7 +103,8 @@ def test_config2_bench_batch_sweep():
     """BASELINE configs[1] at batch scale: 64 worlds (100 bundles of the reach engine, so bundle
     boundaries fall inside worlds), every plan against the oracle"""
     rng = np.random.default_rng(5)
-    _compare_batch(100, 20, list(range(500, 564)), [rng.uniform(-1, 1, 7)])
+    P = _compare_batch(100, 20, list(range(500, 564)), [rng.uniform(-1, 1, 7)])
+    assert_paths(P.path_counts(), ran=(("reach_lane_wide", "reach_lane_dense"),), not_ran=("reach_job_256", "reach_job_128"))
 
 
 def test_config5_fetch_batch():
@@ -108,7 +113,8 @@ def test_config5_fetch_batch():
     `bench.py --robot fetch`. Fetch's reach program does not fit the per-job engine's LDS pool, so
     every batch size runs on the bundle engine (planner.hip job_fits)"""
     fetch = RT.load_json(os.path.join(GOLD, "robot_fetch.json"))
-    _compare_batch(40, 8, [31, 32, 33], [np.zeros(7), np.linspace(-0.6, 0.6, 7)], robot=fetch)
+    P = _compare_batch(40, 8, [31, 32, 33], [np.zeros(7), np.linspace(-0.6, 0.6, 7)], robot=fetch)
+    assert_paths(P.path_counts(), ran=(("reach_lane_wide", "reach_lane_dense"),), not_ran=("reach_job_256", "reach_job_128"))
 
 
 def test_config5_fetch_full_size():

@@ -10,6 +10,7 @@ import pytest
 
 import armour_amd as A
 from conftest import engine
+from paths import assert_paths, engine_paths, taken
 from test_boundary import load, world
 
 pytestmark = pytest.mark.gpu
@@ -63,6 +64,16 @@ def check_plan(P, Q, worlds):
         np.testing.assert_array_equal(P.constraints(w), Q.constraints(w))
 
 
+def assert_cache_paths(P, Q, eng=None):
+    """the census of planners(): P built the cache and read it, Q (ARMOUR_PLANE_CACHE=0) never did, and so
+    ran without the kernels and searches that read only the cache"""
+    assert_paths(P.path_counts(), ran=("pc_builds", "eval_cached") + engine_paths(eng)["ran"],
+                 not_ran=("pc_fallbacks",) + engine_paths(eng)["not_ran"])
+    assert_paths(Q.path_counts(), ran=("eval_full_scan",) + engine_paths(eng)["ran"],
+                 not_ran=("pc_builds", "pc_regrows", "eval_cached", "eval_small", "ls_speculative", "ls_one_round",
+                          "ipm_iter_tail", "resto_inline", "resto_one_round") + engine_paths(eng)["not_ran"])
+
+
 @pytest.mark.parametrize("eng", ["lane", "job"])
 def test_plane_cache_survey_worlds(eng):
     T, O, W = 100, 20, 12
@@ -72,6 +83,7 @@ def test_plane_cache_survey_worlds(eng):
     rng = np.random.default_rng(7)
     check_eval(P, Q, worlds, rng)
     check_plan(P, Q, worlds)
+    assert_cache_paths(P, Q, eng)
 
 
 @pytest.mark.parametrize("name", ["boundary_config2_T100_O20", "boundary_config3_T200_O40"])
@@ -83,6 +95,7 @@ def test_plane_cache_boundary(name):
     rng = np.random.default_rng(11)
     check_eval(P, Q, worlds, rng, n=3)
     check_plan(P, Q, worlds)
+    assert_cache_paths(P, Q)
 
 
 def test_plane_cache_stats_survey():
@@ -112,6 +125,10 @@ def test_plane_cache_pool_regrows():
     assert st["blocks_cached"] == st["blocks"] and st["pool_records"] >= st["planes_kept"] > W * T * 7 * O
     check_plan(S, Q, worlds)
     check_plan(P, S, worlds)
+    assert_cache_paths(P, Q)
+    assert_paths(P.path_counts(), not_ran=("pc_regrows",))
+    # one build overflowed the one-record pool and was repeated; the pool then held the later builds
+    assert_paths(S.path_counts(), ran=("pc_builds", "eval_cached"), not_ran=("pc_fallbacks",), exactly={"pc_regrows": 1})
 
 
 def test_plane_cache_grow_failure_falls_back_to_full_scan():
@@ -125,7 +142,7 @@ def test_plane_cache_grow_failure_falls_back_to_full_scan():
     P, Q = planners(T, O, W)
     with env("ARMOUR_PC_K", "1"):
         S = A.Planner(T=T, max_obstacles=O, max_worlds=W)
-    with env("ARMOUR_PC_GROW_FAIL", "1"):
+    with env("ARMOUR_PC_GROW_FAIL", "1"), taken(S) as failed:
         check_plan(S, Q, worlds)
         S.reach(worlds)
         st = S.plane_cache_stats()
@@ -137,4 +154,9 @@ def test_plane_cache_grow_failure_falls_back_to_full_scan():
                 gq, Jq = Q.eval_constraints(w, x)
                 np.testing.assert_array_equal(g, gq)
                 np.testing.assert_array_equal(J, Jq)
-    check_plan(S, P, worlds)
+    assert_paths(failed, ran=("pc_builds", "pc_fallbacks", "eval_full_scan"),
+                 not_ran=("pc_regrows", "eval_cached", "eval_small", "ls_speculative", "ls_one_round", "ipm_iter_tail"))
+    with taken(S) as grown:
+        check_plan(S, P, worlds)
+    assert_paths(grown, ran=("pc_builds", "pc_regrows", "eval_cached"), not_ran=("pc_fallbacks", "eval_full_scan"))
+    assert_cache_paths(P, Q)

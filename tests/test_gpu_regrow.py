@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import armour_amd as A
+from paths import assert_paths
 
 pytestmark = pytest.mark.gpu
 T, O = 10, 2
@@ -109,9 +110,11 @@ def test_row_chunk_is_fixed_when_the_planner_is_created():
         os.environ["ARMOUR_ROW_CHUNK"] = "1024"
         P, Q = planner(14), planner(14)
         ref = plan_record(Q, Q.plan(WORLDS)[0])
+        ref_paths = Q.path_counts()
         Q.close()
         os.environ["ARMOUR_ROW_CHUNK"] = "256"
         got = plan_record(P, P.plan(WORLDS)[0])
+        got_paths = P.path_counts()
         P.close()
     finally:
         if prev is None:
@@ -119,3 +122,6 @@ def test_row_chunk_is_fixed_when_the_planner_is_created():
         else:
             os.environ["ARMOUR_ROW_CHUNK"] = prev
     assert same(got, ref)
+    # and the same launches, one by one: the row passes of both ran on one block per world
+    assert_paths(got_paths, ran=("ipm_iter_sync", "da_regs"), not_ran=("da_lds",))
+    assert got_paths == ref_paths, (got_paths, ref_paths)

@@ -31,11 +31,12 @@ import robot_variants as RV
 from armour_amd import robot_tables as RT
 from conftest import engine
 from oracle import OraclePlanner
+from paths import assert_paths, engine_paths
 from test_gpu_candidates import candidates, check_against_oracle, oracle_candidates
 from test_gpu_containment import _check
 from test_gpu_mixed_obstacles import assert_bitwise
 from test_gpu_parity import ENGINES, TOL, _compare_batch
-from test_gpu_plane_cache import check_eval, check_plan, env
+from test_gpu_plane_cache import assert_cache_paths, check_eval, check_plan, env
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "emu"))
 import emu  # noqa: E402
@@ -85,6 +86,7 @@ def test_reach_program_unchanged_for_kinova_and_fetch():
     for name, robot in (("kinova", None), ("fetch", RV.fetch())):
         P = planner(robot)
         assert np.array_equal(P.reach_program(), np.array(want[name])[:, 0]), name
+        assert_paths(P.path_counts(), not_ran=tuple(P.path_counts()))  # reading the program launches nothing
         P.close()
     P = planner(RV.variant("KINOVA_REV"))
     assert np.array_equal(P.reach_program(), np.array(want["kinova"])[:, 0])
@@ -99,6 +101,8 @@ def test_sets_contain_point_models(name, eng):
     P = planner(robot, eng)
     n, worst = _check(P, worlds_of(robot, (40, 41, 42), profile="survey"), robot, np.random.default_rng(4))
     print(f"{name} {eng}: {n} time samples, worst excess {worst}")
+    # (Fetch's programs and the nine-joint ones fit the bundle engine only: planner.hip job_fits)
+    assert_paths(P.path_counts(), **engine_paths(eng if fits_per_job_engine(robot) else "lane"))
     P.close()
 
 
@@ -156,6 +160,8 @@ def test_mirror_identity(case, eng):
         RV.assert_mirror_plan(ra[w], rb[w], joints, (case, seeds[w]))
         assert ra[w]["status"] == 0 or not ra[w]["feasible"]
     assert tuple(r["feasible"] for r in ra) == RV.MIRROR_FEASIBLE[case]
+    for P in (PA, PB):
+        assert_paths(P.path_counts(), **engine_paths(eng if fits_per_job_engine(Ar) else "lane"))
     PA.close()
     PB.close()
 
@@ -179,6 +185,7 @@ def test_nine_joints_constraint_count_and_plane_cache(name):
     assert st["blocks_cached"] == st["blocks"] and 1 <= st["max_per_pair"] <= 36
     check_plan(P, Q, worlds)
     assert P.constraints(0).shape == (7 * T + 9 * T * O + 28,)
+    assert_cache_paths(P, Q, "lane")  # (nine joints: the bundle engine at every batch size)
     P.close()
     Q.close()
 
@@ -204,6 +211,8 @@ def test_nine_joints_mixed_batch_bitwise(name):
     res, _ = P.plan_mixed(worlds)
     assert [P.world_obstacles(w) for w in range(W)] == counts
     assert [P.constraints(w).shape[0] for w in range(W)] == [7 * T + 9 * T * c + 28 for c in counts]
+    assert_paths(P.path_counts(), ran=("batch_mixed", ("eval_small", "eval_mx")) + engine_paths("lane")["ran"],
+                 not_ran=("batch_uniform", "eval_f64") + engine_paths("lane")["not_ran"])
     P.close()
     want = [None] * W
     for c in sorted(set(counts)):
@@ -214,6 +223,8 @@ def test_nine_joints_mixed_batch_bitwise(name):
             if k == c:
                 assert all(np.array_equal(a, b) for a, b in zip(uniform[i], worlds[i]))
                 want[i] = out[i]
+        assert_paths(U.path_counts(), ran=("batch_uniform",) + engine_paths("lane")["ran"],
+                     not_ran=("batch_mixed", "eval_mx") + engine_paths("lane")["not_ran"])
         U.close()
     assert_bitwise(res, want, name)
 
@@ -232,4 +243,6 @@ def test_nine_joints_candidates(name):
         R = OraclePlanner(*worlds[w], T=T, threads=8, robot=RT.to_struct(robot))
         R.reach()
         check_against_oracle(out, w, oracle_candidates(R, X[w]), name)
+    assert_paths(P.path_counts(), ran=(("cand_small", "cand_full"), "pc_builds") + engine_paths("lane")["ran"],
+                 not_ran=engine_paths("lane")["not_ran"], exactly={"cand_chunks": 1})
     P.close()

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import armour_amd as A
+from paths import assert_paths
 from test_saved_worlds import saved_worlds
 
 pytestmark = pytest.mark.gpu
@@ -47,6 +48,7 @@ def test_saved_worlds_monotone_barrier_option():
     finally:
         os.environ.pop("ARMOUR_MU_STRATEGY", None)
     res, _ = P.plan([worlds[i] for i in idx])
+    assert_paths(P.path_counts(), exactly={"solve_monotone": 1, "solve_adaptive": 0})
     its = []
     for i, r in zip(idx, res):
         R = OraclePlanner(*worlds[i], T=100, threads=8)

@@ -15,6 +15,7 @@ import pytest
 
 import armour_amd as A
 import sq_threshold_cases as Q
+from paths import assert_paths
 
 pytestmark = pytest.mark.gpu
 S_STAR = float.fromhex("0x1.0c6f7a0b5ed8ep-22")  # tests/test_sq_threshold.py
@@ -27,6 +28,11 @@ def run(case, variant, fallback=False):
     key = (case, variant, fallback)
     if key not in _runs:
         _runs[key] = Q.run_case(case, variant, fallback)
+    # the run took the engine and shape of its variant, and the sqrt kernels only as the forced fallback
+    mine = {"wide": "reach_lane_wide", "dense": "reach_lane_dense", "job": ("reach_job_256", "reach_job_128")}[variant]
+    others = tuple(n for n in ("reach_lane_wide", "reach_lane_dense", "reach_job_256", "reach_job_128") if n not in mine)
+    assert_paths(Q.PATHS[key], ran=(mine, "reach_sqrt" if fallback else "reach_sq"),
+                 not_ran=others + ("reach_sq" if fallback else "reach_sqrt",))
     return _runs[key]
 
 

@@ -7,6 +7,7 @@ import pytest
 
 import armour_amd as A
 from conftest import engine
+from paths import assert_paths, engine_paths
 from test_gpu_plane_cache import check_plan, env
 
 pytestmark = pytest.mark.gpu
@@ -28,6 +29,10 @@ def test_cu_masked_reach_stream_plans_bitwise(eng):
         for a, b in zip(ra, rb):
             np.testing.assert_array_equal(a["k_opt"], b["k_opt"])
             assert a["iterations"] == b["iterations"]
+    # every reach launch of the masked planner went to its CU-masked stream, none of the default one's
+    ran, not_ran = engine_paths(eng)["ran"], engine_paths(eng)["not_ran"]
+    assert_paths(P.path_counts(), ran=ran, not_ran=not_ran + ("reach_cu_masked",))
+    assert_paths(Q.path_counts(), ran=ran, not_ran=not_ran, exactly={"reach_cu_masked": 3, ran[0]: 3})
 
 
 def test_bundle_kernel_shapes_plan_bitwise():
@@ -44,3 +49,5 @@ def test_bundle_kernel_shapes_plan_bitwise():
     for w in range(W):
         np.testing.assert_array_equal(P.link_generators(w), Q.link_generators(w))
         np.testing.assert_array_equal(P.torque_radius(w), Q.torque_radius(w))
+    assert_paths(P.path_counts(), ran=("reach_lane_wide",), not_ran=("reach_lane_dense", "reach_job_256", "reach_job_128"))
+    assert_paths(Q.path_counts(), ran=("reach_lane_dense",), not_ran=("reach_lane_wide", "reach_job_256", "reach_job_128"))

@@ -28,6 +28,7 @@ import pytest
 import armour_amd as A
 import robot_variants as RV
 import track_cases as TC
+from paths import TRACK_ROW, TRACK_SERIAL, assert_paths
 
 pytestmark = pytest.mark.gpu
 NF = 7
@@ -49,12 +50,16 @@ def close_planners():
 
 
 class kernel:
-    """context manager: armour_track runs the serial kernel ("serial") or the default one (None)"""
+    """context manager: armour_track runs the serial kernel ("serial") or the default one (None). With
+    the planner the body drives, the body's launches are checked on leaving it (the path census): only
+    the kernel asked for, in its plain ("": armour_track), recording ("_rec": armour_track_motion) or
+    episode ("_episode": a tracked episode's step) form"""
 
-    def __init__(self, name):
-        self.name = name
+    def __init__(self, name, planner=None, form=""):
+        self.name, self.planner, self.form = name, planner, form
 
     def __enter__(self):
+        self.before = self.planner.path_counts() if self.planner is not None else None
         self.prev = os.environ.get("ARMOUR_TRACK_KERNEL")
         if self.name:
             os.environ["ARMOUR_TRACK_KERNEL"] = self.name
@@ -66,6 +71,11 @@ class kernel:
             os.environ.pop("ARMOUR_TRACK_KERNEL", None)
         else:
             os.environ["ARMOUR_TRACK_KERNEL"] = self.prev
+        if self.planner is not None and exc[0] is None:
+            after = self.planner.path_counts()
+            mine = ("track_serial" if self.name == "serial" else "track_row") + self.form
+            assert_paths({k: after[k] - self.before[k] for k in after}, ran=(mine,),
+                         not_ran=tuple(n for n in TRACK_ROW + TRACK_SERIAL if n != mine))
 
 
 def run(robot, shape, window, steps=TC.STEPS):
@@ -96,10 +106,10 @@ def test_parity_with_the_model(robot, window):
 @pytest.mark.parametrize("shape", TC.SHAPES)
 def test_row_kernel_is_bitwise_the_serial_kernel_and_reruns(shape, window):
     for robot in ("kinova", "KINOVA_9"):
-        with kernel(None):
+        with kernel(None, planner(robot)):
             a = run(robot, shape, window)
             b = run(robot, shape, window)
-        with kernel("serial"):
+        with kernel("serial", planner(robot)):
             c = run(robot, shape, window)
         for k in TC.FIELDS + ("status",):
             assert np.array_equal(a[k], b[k]), ("rerun", robot, k)
@@ -109,7 +119,7 @@ def test_row_kernel_is_bitwise_the_serial_kernel_and_reruns(shape, window):
 @pytest.mark.parametrize("name", (None, "serial"))
 def test_a_rollout_alone_is_bitwise_its_value_in_every_batch(name):
     P = planner("kinova")
-    with kernel(name):
+    with kernel(name, P):
         for shape in TC.SHAPES:
             tb, traj, scale, err0 = TC.case_inputs("kinova", shape)
             full = P.track(traj, scale, err0, 0.0, 0.5, TC.STEPS)
@@ -149,7 +159,7 @@ def test_a_rollout_that_stops_being_finite_keeps_its_last_state():
     want[1, 2] = 1
     keep = want == 0
     for name in (None, "serial"):
-        with kernel(name):
+        with kernel(name, P):
             clean = P.track(traj, scale, err0, 0.0, 0.5, 10)
             got = P.track(traj, scale, bad, 0.0, 0.5, 10)
         assert np.array_equal(got["status"], want)

@@ -126,10 +126,10 @@ def test_row_kernel_is_bitwise_the_serial_kernel_and_reruns(shape):
     for robot in ("kinova", "KINOVA_9"):
         P, traj, scale, err0, obs = batch(robot, shape)
         for C in (2, 11):
-            with kernel(None):
+            with kernel(None, P, "_rec"):
                 a = P.track_motion(traj, scale, err0, 0.5, 1.0, KC.STEPS, C)
                 b = P.track_motion(traj, scale, err0, 0.5, 1.0, KC.STEPS, C)
-            with kernel("serial"):
+            with kernel("serial", P, "_rec"):
                 c = P.track_motion(traj, scale, err0, 0.5, 1.0, KC.STEPS, C)
             same(a, b)
             same(a, c)
@@ -221,7 +221,7 @@ def test_a_rollout_that_stops_being_finite_is_flagged_and_the_others_are_untouch
     keep = np.ones((3, 5), dtype=bool)
     keep[1, 2] = False
     for name in (None, "serial"):
-        with kernel(name):
+        with kernel(name, P, "_rec"):
             clean = P.track_motion(traj, scale, err0, 0.0, 0.5, 10, 6)
             got = P.track_motion(traj, scale, bad, 0.0, 0.5, 10, 6)
         assert got["status"][1, 2] == 1 and not got["status"][keep].any()

@@ -268,7 +268,7 @@ def test_serial_kernel_is_bitwise_the_row_kernel(run):
     worlds, goals, scale, P = run["worlds"], run["goals"], run["scale"], run["P2"]
     got = {}
     for name in (None, "serial"):
-        with kernel(name):
+        with kernel(name, P, "_episode"):
             P.episode_begin(worlds, goals, check_samples=C)
             P.episode_track(scale=scale, steps=STEPS)
             for _ in range(3):

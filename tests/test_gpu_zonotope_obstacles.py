@@ -32,6 +32,7 @@ import boundary_worlds as B
 import test_zonotope_obstacles as Z
 from conftest import engine
 from oracle import OracleArmtd, OraclePlanner
+from paths import assert_paths, engine_paths
 from test_armtd import load as load_armtd, world as armtd_world
 from test_gpu_plane_cache import check_eval, check_plan, env
 
@@ -58,6 +59,17 @@ def planner(name, variant="default"):
     return _planners[name, variant]
 
 
+def assert_variant_paths(name, variant):
+    """the census of planner(name, variant) after it evaluated or planned: the bundle engine, and the
+    evaluation kernels of its variant (the small-capacity ones only for the Kinova's at most 280 pairs)"""
+    lane = engine_paths("lane")
+    small = ("eval_small",) if Z.case(name)["robot"] == "kinova" else ()
+    ran, not_ran = {"default": (("pc_builds", "eval_cached") + small, ("pc_fallbacks",) + (() if small else ("eval_small",))),
+                    "nocache": (("eval_full_scan",), ("pc_builds", "eval_cached", "eval_small", "trials_small")),
+                    "full": (("pc_builds", "eval_cached", "eval_f64"), ("eval_small", "trials_small"))}[variant]
+    assert_paths(planner(name, variant).path_counts(), ran=lane["ran"] + ran, not_ran=lane["not_ran"] + not_ran)
+
+
 def run(name):
     """the default planner on one fixture world: per point g, J, the link centres
     (armour_get_link_centers after armour_eval_constraints) and their central differences"""
@@ -76,6 +88,7 @@ def run(name):
             pts.append(dict(x=x, g=g, J=J, lc=P.link_centers(0), dc=dc))
         _runs[name] = dict(NJ=P.NJ, link_gens=P.link_generators(0), points=pts,
                            stats=P.plane_cache_stats(), occupancy=P.occupancy())
+    assert_variant_paths(name, "default")
     return _runs[name]
 
 
@@ -118,6 +131,7 @@ def test_variants_bitwise(name):
             g, J = Q.eval_constraints(0, p["x"])
             np.testing.assert_array_equal(g, p["g"], err_msg=f"{label} point {k}")
             np.testing.assert_array_equal(J, p["J"], err_msg=f"{label} point {k}")
+        assert_variant_paths(name, label)
     NJ, st = got["NJ"], got["stats"]
     print(f"{name}: plane cache {st}, occupancy {got['occupancy']}")
     assert st["box_misses"] == 0 and planner(name).plane_cache_stats()["box_misses"] == 0
@@ -165,6 +179,8 @@ def test_plans(name):
     if not local_infeasible:
         np.testing.assert_allclose(r["k_opt"], ro["k_opt"], rtol=0, atol=tol)
     check_plan(P, Q, [world])
+    assert_variant_paths(name, "default")
+    assert_variant_paths(name, "nocache")
     _runs.pop(name, None)  # the planner has moved on; a later run() evaluates again
 
 
@@ -198,6 +214,7 @@ def test_armtd():
     tol = 1e-8 if (r["status"] == 0 or r["feasible"]) else 1e-3
     np.testing.assert_allclose(r["k_opt"], ro["k_opt"], rtol=0, atol=tol)
     np.testing.assert_allclose(P.constraints(0), R.eval(r["k_opt"], jac=False), rtol=0, atol=1e-7)
+    assert_paths(P.path_counts(), ran=("eval_armtd_f64",), not_ran=("eval_f64", "eval_small", "eval_f32", "eval_armtd_f32"))
 
 
 def test_fp32_study_path():
@@ -218,3 +235,5 @@ def test_fp32_study_path():
         print(f"fp32 point {k}: worst {d[..., ~huge].max():.2e}, on the 1e3 m obstacle {d[..., huge].max():.2e}")
         assert d[..., ~huge].max() < 5e-6
         assert not np.array_equal(g32, p["g"])  # it really ran in float
+    assert_paths(F.path_counts(), ran=("eval_f32", "eval_full_scan") + engine_paths("lane")["ran"],
+                 not_ran=("eval_f64", "eval_small", "eval_cached", "pc_builds") + engine_paths("lane")["not_ran"])
