@@ -1464,17 +1464,36 @@ __global__ __launch_bounds__(64) void ipm_world_init(NlpDev d, Round r) {
     S.rphi = -1;
 }
 
+// A row block's place in its launch: list entry e (blockIdx.y; a speculative pass: the trial's entry)
+// is world w with the extents sh, the block's rows start at r0 of the world's R and at wb + r0 of
+// the row arrays. rows is false, and nothing else set, for a block the launch has no work for: a
+// block past this world's rows (mixed batch) or, where the kernel takes the list's length from the
+// device (counted: the launch's Round carries an lcount meant for it), an entry past that length.
+struct RowBlock {
+    int w;
+    Shape sh;
+    long r0, wb;
+    bool rows;
+};
+template <bool MX>
+__device__ __attribute__((always_inline)) RowBlock row_block(const NlpDev& d, const Round& r, unsigned e, bool counted) {
+    if (counted && r.lcount && e >= *r.lcount) return {};
+    const int w = world_of(r, (int)e);
+    const Shape sh = shape_of<MX>(d, w);
+    if (MX && (int)blockIdx.x >= sh.nblk) return {};
+    return {w, sh, (long)blockIdx.x * d.chunk, (long)w * d.R, true};
+}
+
 template <bool MX>
 __device__ __attribute__((always_inline)) void ipm_rows_init_body(const NlpDev& d, const Round& r) {
-    const int w = world_of(r, blockIdx.y);  // every world, or the list restarted by a restoration phase
-    const Shape sh = shape_of<MX>(d, w);
-    if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
+    // every world, or the list restarted by a restoration phase
+    const auto [w, sh, r0, wb, rows] = row_block<MX>(d, r, blockIdx.y, false);
+    if (!rows) return;
     const WorldState& S = d.ws[w];
-    const long r0 = (long)blockIdx.x * d.chunk;
     for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.R; r += blockDim.x) {
         double a[NF];
         const double v = row_va(d, sh, S.cur, w, (int)r, S.x, a);
-        const long i = (long)w * d.R + r;
+        const long i = wb + r;
         double L, U;
         bounds_of(d, sh, w, (int)r, L, U);
         d.L[i] = L;
@@ -1590,45 +1609,21 @@ __device__ inline double dual_step(double mu, double s, double z, double ds) {
     const double sg = z / s;
     return mu / s - z - sg * ds;
 }
-// pass D's row update (accept the trial: slacks, multipliers) and the BFGS ingredient sum w a
-__device__ inline __attribute__((always_inline)) void row_D(const NlpDev& d, long i, const double* a, double L, double U,
-                                                            double mu, double ad, double alpha, double* wn) {
-    const double ks = d.opt.kappa_sigma;
-    double wv = 0;
-    if (has_lo(d, L)) {
-        const double zn = d.zlo[i] + ad * dual_step(mu, d.slo[i], d.zlo[i], d.dslo[i]);
-        wv += zn;
-        const double s = d.slo[i] + alpha * d.dslo[i];
-        d.slo[i] = s;
-        d.zlo[i] = fmin(fmax(zn, mu / (ks * s)), ks * mu / s);
-    }
-    if (has_hi(d, U)) {
-        const double zn = d.zhi[i] + ad * dual_step(mu, d.shi[i], d.zhi[i], d.dshi[i]);
-        wv -= zn;
-        const double s = d.shi[i] + alpha * d.dshi[i];
-        d.shi[i] = s;
-        d.zhi[i] = fmin(fmax(zn, mu / (ks * s)), ks * mu / s);
-    }
-#pragma unroll
-    for (int j = 0; j < NF; j++) wn[j] += wv * a[j];
-}
 
 template <bool MX>
 __device__ __attribute__((always_inline)) void ipm_rows_A_body(const NlpDev& d, const Round& r) {
-    const int w = world_of(r, blockIdx.y);
-    const Shape sh = shape_of<MX>(d, w);
-    if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
+    const auto [w, sh, r0, wb, rows] = row_block<MX>(d, r, blockIdx.y, false);
+    if (!rows) return;
     const WorldState& S = d.ws[w];
     if (S.status != 0) return;
     __shared__ double lds[(ROW_THREADS / 64) * NA];
     AAcc c;
     c.zero();
     const double mu = S.mu;
-    const long r0 = (long)blockIdx.x * d.chunk;
     for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.R; r += blockDim.x) {
         double a[NF];
         const double v = row_va(d, sh, S.cur, w, (int)r, S.x, a);
-        const long i = (long)w * d.R + r;
+        const long i = wb + r;
         double L, U;
         row_bounds(d, sh, i, (int)r, L, U);
         row_A(d, i, v, a, L, U, mu, c);
@@ -1640,7 +1635,8 @@ __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_A_mx(NlpDev d, Round r) 
 
 // passes D (of the previous iteration) and A (of this one) in one sweep over the rows: the trial
 // point D accepts is the point A works at, so each row's value and gradient are read once; the
-// arithmetic of ipm_rows_D then ipm_rows_A. D's sums go to partial2, A's to partial.
+// arithmetic of pass D's row update (accept the trial: slacks, multipliers, and the BFGS ingredient
+// sum w a) then ipm_rows_A's. D's sums go to partial2, A's to partial.
 // ML > 0 (ipm_rows_DA_lds, the wide launches): the first ML of pass A's 28 Newton-matrix
 // accumulators live in LDS, one slot per thread, with the same additions in the same order, so the
 // kernel holds 166 VGPRs instead of 216 and runs three waves per SIMD instead of two: a 1308-world
@@ -1649,10 +1645,8 @@ __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_A_mx(NlpDev d, Round r) 
 constexpr int DA_ML = 20;
 template <int ML, bool MX = false>
 __device__ __attribute__((always_inline)) void rows_DA_body(const NlpDev& d, const Round& r) {
-    if (r.lcount && blockIdx.y >= *r.lcount) return;
-    const int w = world_of(r, blockIdx.y);
-    const Shape sh = shape_of<MX>(d, w);
-    if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
+    const auto [w, sh, r0, wb, rows] = row_block<MX>(d, r, blockIdx.y, true);
+    if (!rows) return;
     const WorldState& S = d.ws[w];
     if (S.status != 0) return;
     __shared__ double lds[(ROW_THREADS / 64) * NA];
@@ -1670,9 +1664,8 @@ __device__ __attribute__((always_inline)) void rows_DA_body(const NlpDev& d, con
     AAcc c;
     c.zero();
     const double ks = d.opt.kappa_sigma;
-    const long r0 = (long)blockIdx.x * d.chunk, wb = (long)w * d.R;
     for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.R; r += blockDim.x) {
-        // the row's loads in one batch, then row_D's and row_A's arithmetic on registers (A reads
+        // the row's loads in one batch, then pass D's and row_A's arithmetic on registers (A reads
         // the slacks and multipliers D has just formed)
         const long i = wb + r;
         const RowBounds B(d, sh, i, wb, (int)r);
@@ -1744,13 +1737,27 @@ __device__ bool chol_solve7(const double* M, double shift, const double* b, doub
 // (the arithmetic of a serial loop over the blocks), returned wave-uniform. op: 0 sum, 1 max, 2 min
 // onto init. The per-world kernels run one wave per world: the nblk dependent load rounds of a
 // single thread become one round per lane.
-template <int N>
-__device__ inline void world_partials_at(const double* base, int nblk, int stride, const double (&init)[N],
-                                         const int (&op)[N], double (&P)[N]);
-// (nblk: the world's own row blocks, Shape::nblk; its partials sit in a slab of d.nblk blocks)
-template <int N>
-__device__ inline void world_partials(const NlpDev& d, int w, int nblk, const double (&init)[N], const int (&op)[N], double (&P)[N]) {
-    world_partials_at(d.partial + (long)w * d.nblk * KA, nblk, KA, init, op, P);
+// The in-order fold every sum over a world's row blocks is: the partials in[b * stride] of blocks
+// b = 0 .. nblk - 1 combined onto s in block order (op: 0 sum, 1 max, 2 min), sixteen clamped loads
+// in flight per step. Any thread may call it; equal arguments give equal bits wherever it is called,
+// which is what holds the speculative and one-round kernels bitwise to the sequential ones.
+__device__ inline __attribute__((always_inline)) double fold_blocks(const double* in, int nblk, int stride, double s, int op) {
+    for (int b0 = 0; b0 < nblk; b0 += 16) {
+        double x[16];
+#pragma unroll
+        for (int u = 0; u < 16; u++) x[u] = in[(long)min(b0 + u, nblk - 1) * stride];
+#pragma unroll
+        for (int u = 0; u < 16; u++)
+            if (b0 + u < nblk) s = op == 0 ? s + x[u] : op == 1 ? fmax(s, x[u]) : fmin(s, x[u]);
+    }
+    return s;
+}
+// lane q's v on every lane of the wave (q wave-uniform)
+__device__ inline __attribute__((always_inline)) double lane_double(double v, int q) {
+    const uint64_t u = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, q);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), q);
+    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
 }
 template <int N>
 __device__ inline void world_partials_at(const double* base, int nblk, int stride, const double (&init)[N],
@@ -1761,25 +1768,14 @@ __device__ inline void world_partials_at(const double* base, int nblk, int strid
 #pragma unroll
     for (int q = 0; q < N; q++)
         if (q == lane) { s = init[q]; o = op[q]; }
-    if (lane < N) {
-        // sixteen block partials in flight per step (clamped loads), combined in block order
-        const double* in = base + lane;
-        for (int b0 = 0; b0 < nblk; b0 += 16) {
-            double x[16];
+    if (lane < N) s = fold_blocks(base + lane, nblk, stride, s, o);
 #pragma unroll
-            for (int u = 0; u < 16; u++) x[u] = in[(long)min(b0 + u, nblk - 1) * stride];
-#pragma unroll
-            for (int u = 0; u < 16; u++)
-                if (b0 + u < nblk) s = o == 0 ? s + x[u] : o == 1 ? fmax(s, x[u]) : fmin(s, x[u]);
-        }
-    }
-    const uint64_t u = __builtin_bit_cast(uint64_t, s);
-#pragma unroll
-    for (int q = 0; q < N; q++) {
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, q);
-        const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), q);
-        P[q] = __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-    }
+    for (int q = 0; q < N; q++) P[q] = lane_double(s, q);
+}
+// (nblk: the world's own row blocks, Shape::nblk; its partials sit in a slab of d.nblk blocks)
+template <int N>
+__device__ inline void world_partials(const NlpDev& d, int w, int nblk, const double (&init)[N], const int (&op)[N], double (&P)[N]) {
+    world_partials_at(d.partial + (long)w * d.nblk * KA, nblk, KA, init, op, P);
 }
 
 template <bool MX>
@@ -1805,28 +1801,51 @@ __device__ inline double mu_grid(double x) {
     for (int q = 1; q < 9; q++) gj = j == q ? G[q] : gj;
     return ldexp(gj, e - 1);
 }
-// A world kernel (one wave) works on its world's state staged in LDS: one coalesced round trip in
-// and one out, where lane 0's steps would otherwise wait on a dependent global load per field. The
-// way out is taken only for a world the kernel works on (interior point: status 0 at entry;
-// restoration: WS_RESTO): an iteration's list may still name a world whose line search failed after
-// the list was formed, and that world's restoration phase can run concurrently on the planner's
-// second stream (planner.hip ipm_loop), so a copy of its state taken here must not be written back.
 __device__ inline void ws_copy(WorldState& dst, const WorldState& src) {
     static_assert(sizeof(WorldState) % 8 == 0, "WorldState in 8-byte words");
     const uint64_t* s = reinterpret_cast<const uint64_t*>(&src);
     uint64_t* t = reinterpret_cast<uint64_t*>(&dst);
     for (int k = threadIdx.x; k < (int)(sizeof(WorldState) / 8); k += blockDim.x) t[k] = s[k];
 }
+// A world kernel (one wave) works on its world's state staged in LDS: one coalesced round trip in
+// and one out, where lane 0's steps would otherwise wait on a dependent global load per field. The
+// way out is taken only for a world the kernel works on, one whose status at entry is `want`
+// (interior point: 0; restoration: WS_RESTO): an iteration's list may still name a world whose line
+// search failed after the list was formed, and that world's restoration phase can run concurrently
+// on the planner's second stream (planner.hip ipm_loop), so a copy of its state taken here must not
+// be written back. step(S) runs on every lane between two barriers. A block with no list entry
+// (valid false, block-uniform; it is there for the ticket, last_block) touches neither d.ws nor the
+// stage and gets null; the others the staged state as step left it.
+template <typename F>
+__device__ __attribute__((always_inline)) const WorldState* world_step(const NlpDev& d, bool valid, int w, int want, F&& step) {
+    __shared__ WorldState S;  // one per kernel: F is a lambda of that kernel's body
+    if (!valid) return nullptr;
+    ws_copy(S, d.ws[w]);
+    __syncthreads();
+    const bool act = S.status == want;
+    step(S);
+    __syncthreads();
+    if (act) ws_copy(d.ws[w], S);
+    return &S;
+}
+// The last block of a launch publishes its counts: thread 0 of every block, after its appends and
+// counts, takes a ticket; the block that takes the last one sees them all (the fences), hands
+// publish the counts of CNT_RUN and CNT_SEARCH and zeroes the three counters for the next launch.
+template <typename F>
+__device__ __attribute__((always_inline)) void last_block(const NlpDev& d, F&& publish) {
+    __threadfence();
+    if (atomicAdd(&d.cnt[CNT_TICKET], 1u) == gridDim.x - 1) {
+        __threadfence();
+        publish(atomicAdd(&d.cnt[CNT_RUN], 0u), atomicAdd(&d.cnt[CNT_SEARCH], 0u));
+        d.cnt[CNT_RUN] = 0;
+        d.cnt[CNT_SEARCH] = 0;
+        d.cnt[CNT_TICKET] = 0;
+    }
+}
 template <bool MX>
 __device__ __attribute__((always_inline)) void ipm_world_A_body(const NlpDev& d, const Round& r, int nside) {
     const int w = world_of(r, blockIdx.x);
-    __shared__ WorldState S;
-    ws_copy(S, d.ws[w]);
-    __syncthreads();
-    const bool act = S.status == 0;
-    world_A_body<MX>(d, S, w, nside);
-    __syncthreads();
-    if (act) ws_copy(d.ws[w], S);
+    world_step(d, true, w, 0, [&](WorldState& S) { world_A_body<MX>(d, S, w, nside); });
 }
 __global__ __launch_bounds__(64) void ipm_world_A(NlpDev d, Round r, int nside) { ipm_world_A_body<false>(d, r, nside); }
 __global__ __launch_bounds__(64) void ipm_world_A_mx(NlpDev d, Round r, int nside) { ipm_world_A_body<true>(d, r, nside); }
@@ -1925,10 +1944,8 @@ __device__ inline void world_A_body(const NlpDev& d, WorldState& S, int w, int n
 // to three spills 32 registers and slows from 6.5 to 7.9 ms, so it stays at two.
 template <bool MX>
 __device__ __attribute__((always_inline)) void ipm_rows_B_body(const NlpDev& d, const Round& r) {
-    if (r.lcount && blockIdx.y >= *r.lcount) return;
-    const int w = world_of(r, blockIdx.y);
-    const Shape sh = shape_of<MX>(d, w);
-    if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
+    const auto [w, sh, r0, w0, rows] = row_block<MX>(d, r, blockIdx.y, true);
+    if (!rows) return;
     const WorldState& S = d.ws[w];
     if (S.status != 0) return;
     __shared__ double lds[(ROW_THREADS / 64) * NA];
@@ -1940,7 +1957,6 @@ __device__ __attribute__((always_inline)) void ipm_rows_B_body(const NlpDev& d, 
     double dx[NF];
 #pragma unroll
     for (int j = 0; j < NF; j++) dx[j] = S.dx[j];
-    const long r0 = (long)blockIdx.x * d.chunk, w0 = (long)w * d.R;
     for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.R; r += blockDim.x) {
         const long i = w0 + r;  // the row's loads in one batch (RowBounds)
         const RowBounds B(d, sh, i, w0, (int)r);
@@ -2028,62 +2044,46 @@ template <bool MX>
 __device__ __attribute__((always_inline)) void ipm_world_B_body(const NlpDev& d, const Round& r) {
     if (r.lcount && blockIdx.x >= *r.lcount) return;
     const int w = world_of(r, blockIdx.x);
-    __shared__ WorldState S;
-    ws_copy(S, d.ws[w]);
-    __syncthreads();
-    const bool act = S.status == 0;
-    world_B_body<MX>(d, S, w);
-    __syncthreads();
-    if (act) ws_copy(d.ws[w], S);
+    world_step(d, true, w, 0, [&](WorldState& S) { world_B_body<MX>(d, S, w); });
 }
 __global__ __launch_bounds__(64) void ipm_world_B(NlpDev d, Round r) { ipm_world_B_body<false>(d, r); }
 __global__ __launch_bounds__(64) void ipm_world_B_mx(NlpDev d, Round r) { ipm_world_B_body<true>(d, r); }
 // the first trial's step alpha = S.ap as world_B_body forms it: pass B's block partials of the
-// primal fraction to the boundary, min onto 1 in block order (world_partials' arithmetic), for the
-// tail's trial passes that run before the world step (NlpDev::b_in_cs)
+// primal fraction to the boundary, min onto 1 in block order, for the tail's trial passes that run
+// before the world step (NlpDev::b_in_cs)
 template <bool MX>
 __device__ inline double pass_b_alpha(const NlpDev& d, int w) {
-    const double* in = d.partial + (long)w * d.nblk * KA;
-    const int nblk = shape_of<MX>(d, w).nblk;
-    double a = 1.0;
-    for (int b0 = 0; b0 < nblk; b0 += 16) {
-        double x[16];
-#pragma unroll
-        for (int u = 0; u < 16; u++) x[u] = in[(long)min(b0 + u, nblk - 1) * KA];
-#pragma unroll
-        for (int u = 0; u < 16; u++)
-            if (b0 + u < nblk) a = fmin(a, x[u]);
-    }
-    return a;
+    return fold_blocks(d.partial + (long)w * d.nblk * KA, shape_of<MX>(d, w).nblk, KA, 1.0, 2);
 }
 
-// pass C: barrier objective and constraint violation at the trial point
-template <bool MX>
-__device__ __attribute__((always_inline)) void ipm_rows_C_body(const NlpDev& d, const Round& r) {
-    if (r.lcount && blockIdx.y >= *r.lcount) return;
-    const int w = world_of(r, blockIdx.y);
-    const Shape sh = shape_of<MX>(d, w);
-    if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
-    const WorldState& S = d.ws[w];
-    if (!(S.status == 0 && S.searching)) return;
+// pass C: barrier objective and constraint violation at a trial point with step alpha, one row
+// block's sums into out; value(r) is row r's value there
+template <typename F>
+__device__ __attribute__((always_inline)) void rows_C_sums(const NlpDev& d, const RowBlock& b, double alpha, F&& value, double* out) {
     __shared__ double lds[(ROW_THREADS / 64) * NA];
     double logt = 0, rpt = 0;
-    const double alpha = S.alpha;
-    const long r0 = (long)blockIdx.x * d.chunk, wb = (long)w * d.R;
-    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.R; r += blockDim.x) {
-        const long i = wb + r;  // the row's loads in one batch (RowBounds)
-        const RowBounds B(d, sh, i, wb, (int)r);
+    for (long r = b.r0 + threadIdx.x; r < b.r0 + d.chunk && r < b.sh.R; r += blockDim.x) {
+        const long i = b.wb + r;  // the row's loads in one batch (RowBounds)
+        const RowBounds B(d, b.sh, i, b.wb, (int)r);
         const double slo = d.slo[B.lo], dslo = d.dslo[B.lo], shi = d.shi[i], dshi = d.dshi[i];
-        double a[NF];
-        const double v = row_va(d, sh, 1 - S.cur, w, (int)r, S.xt, a);
+        const double v = value(r);
         const double L = B.L(), U = B.U();
         if (has_lo(d, L)) { const double st = slo + alpha * dslo; logt += log(st); rpt += fabs((v - L) - st); }
         if (has_hi(d, U)) { const double st = shi + alpha * dshi; logt += log(st); rpt += fabs((U - v) - st); }
     }
-    double* out = d.partial + ((long)w * d.nblk + blockIdx.x) * KA;
     double v[2] = {logt, rpt};
     const int kinds[2] = {0, 0};
     block_reduce_n(v, kinds, lds, out);
+}
+// the trial is the world's current one, evaluated in full in the trial slot
+template <bool MX>
+__device__ __attribute__((always_inline)) void ipm_rows_C_body(const NlpDev& d, const Round& r) {
+    const RowBlock b = row_block<MX>(d, r, blockIdx.y, true);
+    if (!b.rows) return;
+    const WorldState& S = d.ws[b.w];
+    if (!(S.status == 0 && S.searching)) return;
+    rows_C_sums(d, b, S.alpha, [&](long row) { double a[NF]; return row_va(d, b.sh, 1 - S.cur, b.w, (int)row, S.xt, a); },
+                d.partial + ((long)b.w * d.nblk + blockIdx.x) * KA);
 }
 __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_C(NlpDev d, Round r) { ipm_rows_C_body<false>(d, r); }
 __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_C_mx(NlpDev d, Round r) { ipm_rows_C_body<true>(d, r); }
@@ -2165,24 +2165,13 @@ template <bool MX>
 __device__ __attribute__((always_inline)) void ipm_world_C_body(const NlpDev& d, const Round& r) {
     const bool valid = !r.lcount || blockIdx.x < *r.lcount;
     const int w = valid ? world_of(r, blockIdx.x) : 0;
-    __shared__ WorldState S;
-    if (valid) {
-        ws_copy(S, d.ws[w]);
-        __syncthreads();
-        const bool act = S.status == 0;
-        world_C_body<MX>(d, r, S, w);
-        __syncthreads();
-        if (act) ws_copy(d.ws[w], S);
-    }
+    const WorldState* const out = world_step(d, valid, w, 0, [&](WorldState& S) { world_C_body<MX>(d, r, S, w); });
     if (threadIdx.x != 0) return;
-    if (valid && S.status == 0) {
+    if (out && out->status == 0) {
         if (r.ls0) r.wl_run[atomicAdd(&d.cnt[CNT_RUN], 1u)] = w;
-        if (S.searching) r.wl_search[atomicAdd(&d.cnt[CNT_SEARCH], 1u)] = w;
+        if (out->searching) r.wl_search[atomicAdd(&d.cnt[CNT_SEARCH], 1u)] = w;
     }
-    __threadfence();
-    if (atomicAdd(&d.cnt[CNT_TICKET], 1u) == gridDim.x - 1) {
-        __threadfence();
-        const unsigned nrun = atomicAdd(&d.cnt[CNT_RUN], 0u), nsearch = atomicAdd(&d.cnt[CNT_SEARCH], 0u);
+    last_block(d, [&](unsigned nrun, unsigned nsearch) {
         if (r.ls0) d.flags[FLAG_RUN] = (int)nrun;
         if (r.ls0 && r.lrun_out) *r.lrun_out = nrun;
         if (r.ls0 && r.nrun_flag) *r.nrun_flag = (int)nrun;
@@ -2190,10 +2179,7 @@ __device__ __attribute__((always_inline)) void ipm_world_C_body(const NlpDev& d,
         d.flags[FLAG_SEARCH] = (int)nsearch;
         if (r.lcount_out) *r.lcount_out = nsearch;
         if (r.pend_flag) *r.pend_flag = (int)atomicAdd(&d.cnt[CNT_RL], 0u);
-        d.cnt[CNT_RUN] = 0;
-        d.cnt[CNT_SEARCH] = 0;
-        d.cnt[CNT_TICKET] = 0;
-    }
+    });
 }
 __global__ __launch_bounds__(64) void ipm_world_C(NlpDev d, Round r) { ipm_world_C_body<false>(d, r); }
 __global__ __launch_bounds__(64) void ipm_world_C_mx(NlpDev d, Round r) { ipm_world_C_body<true>(d, r); }
@@ -2203,32 +2189,17 @@ __global__ __launch_bounds__(64) void ipm_world_C_mx(NlpDev d, Round r) { ipm_wo
 // from the trial's own slot; the arithmetic of ipm_rows_C at that trial.
 template <bool MX>
 __device__ __attribute__((always_inline)) void ipm_rows_Cs_body(const NlpDev& d, const Round& r) {
-    const int i = blockIdx.y / r.K, k = blockIdx.y % r.K;
-    if (r.lcount && (unsigned)i >= *r.lcount) return;
-    const int w = r.wl[i];
-    const Shape sh = shape_of<MX>(d, w);
-    if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
-    const WorldState& S = d.ws[w];
+    const int k = blockIdx.y % r.K;
+    const RowBlock b = row_block<MX>(d, r, blockIdx.y / r.K, true);
+    if (!b.rows) return;
+    const WorldState& S = d.ws[b.w];
     if (!(S.status == 0 && (r.b_in_cs || S.searching))) return;
-    __shared__ double lds[(ROW_THREADS / 64) * NA];
-    double alpha = r.b_in_cs ? pass_b_alpha<MX>(d, w) : S.alpha;
+    double alpha = r.b_in_cs ? pass_b_alpha<MX>(d, b.w) : S.alpha;
     for (int q = 0; q < k; q++) alpha *= 0.5;
     const double* G = r.gs + (long)blockIdx.y * d.m;
-    double logt = 0, rpt = 0;
-    const long r0 = (long)blockIdx.x * d.chunk, wb = (long)w * d.R;
-    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.R; r += blockDim.x) {
-        const long ii = wb + r;  // the row's loads in one batch (RowBounds)
-        const RowBounds B(d, sh, ii, wb, (int)r);
-        const double slo = d.slo[B.lo], dslo = d.dslo[B.lo], shi = d.shi[ii], dshi = d.dshi[ii];
-        const double v = r < sh.m ? G[r] : S.x[r - sh.m] + alpha * S.dx[r - sh.m];  // box row: the trial's x
-        const double L = B.L(), U = B.U();
-        if (has_lo(d, L)) { const double st = slo + alpha * dslo; logt += log(st); rpt += fabs((v - L) - st); }
-        if (has_hi(d, U)) { const double st = shi + alpha * dshi; logt += log(st); rpt += fabs((U - v) - st); }
-    }
-    double* out = r.partial_s + ((long)blockIdx.y * d.nblk + blockIdx.x) * KA;
-    double v[2] = {logt, rpt};
-    const int kinds[2] = {0, 0};
-    block_reduce_n(v, kinds, lds, out);
+    const int m = b.sh.m;  // a box row: the trial's x
+    rows_C_sums(d, b, alpha, [&](long row) { return row < m ? G[row] : S.x[row - m] + alpha * S.dx[row - m]; },
+                r.partial_s + ((long)blockIdx.y * d.nblk + blockIdx.x) * KA);
 }
 __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_Cs(NlpDev d, Round r) { ipm_rows_Cs_body<false>(d, r); }
 __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_Cs_mx(NlpDev d, Round r) { ipm_rows_Cs_body<true>(d, r); }
@@ -2242,14 +2213,7 @@ __device__ inline void world_Cs_body(const NlpDev& d, const Round& r, WorldState
 template <bool MX>
 __device__ __attribute__((always_inline)) void ipm_world_Cs_body(const NlpDev& d, const Round& r) {
     if (r.lcount && blockIdx.x >= *r.lcount) return;
-    const int w = r.wl[blockIdx.x];
-    __shared__ WorldState S;
-    ws_copy(S, d.ws[w]);
-    __syncthreads();
-    const bool act = S.status == 0;
-    world_Cs_body<MX>(d, r, S, blockIdx.x);
-    __syncthreads();
-    if (act) ws_copy(d.ws[w], S);
+    world_step(d, true, r.wl[blockIdx.x], 0, [&](WorldState& S) { world_Cs_body<MX>(d, r, S, blockIdx.x); });
 }
 __global__ __launch_bounds__(64) void ipm_world_Cs(NlpDev d, Round r) { ipm_world_Cs_body<false>(d, r); }
 __global__ __launch_bounds__(64) void ipm_world_Cs_mx(NlpDev d, Round r) { ipm_world_Cs_body<true>(d, r); }
@@ -2264,36 +2228,24 @@ template <bool MX>
 __device__ __attribute__((always_inline)) void ipm_world_Cs_all_body(const NlpDev& d, const Round& r) {
     const bool valid = !r.lcount || blockIdx.x < *r.lcount;
     const int w = valid ? r.wl[blockIdx.x] : 0;
-    __shared__ WorldState S;
-    if (valid) {
-        ws_copy(S, d.ws[w]);
-        __syncthreads();
-        const bool act = S.status == 0;
+    const WorldState* const out = world_step(d, valid, w, 0, [&](WorldState& S) {
         if (r.b_in_cs) world_B_body<MX>(d, S, w);
         __syncthreads();  // lane 0's WorldState stores before every lane's reads (filter_pass)
         world_Cs_body<MX>(d, r, S, blockIdx.x);
-        __syncthreads();
-        if (act) ws_copy(d.ws[w], S);
-    }
+    });
     if (threadIdx.x != 0) return;
-    if (valid && S.status == 0) {
+    if (out && out->status == 0) {
         r.wl_run[atomicAdd(&d.cnt[CNT_RUN], 1u)] = w;
-        if (S.spec_k > 0) atomicAdd(&d.cnt[CNT_SEARCH], 1u);  // searched past round 0
+        if (out->spec_k > 0) atomicAdd(&d.cnt[CNT_SEARCH], 1u);  // searched past round 0
     }
-    __threadfence();
-    if (atomicAdd(&d.cnt[CNT_TICKET], 1u) == gridDim.x - 1) {
-        __threadfence();
-        const unsigned nrun = atomicAdd(&d.cnt[CNT_RUN], 0u), nbt = atomicAdd(&d.cnt[CNT_SEARCH], 0u);
+    last_block(d, [&](unsigned nrun, unsigned nbt) {
         d.flags[FLAG_RUN] = (int)nrun;
         d.flags[FLAG_SEARCH] = 0;
         if (r.lrun_out) *r.lrun_out = nrun;
         if (r.nrun_flag) *r.nrun_flag = (int)nrun;
         if (r.bt_flag) *r.bt_flag = (int)nbt;
         if (r.pend_flag) *r.pend_flag = (int)atomicAdd(&d.cnt[CNT_RL], 0u);
-        d.cnt[CNT_RUN] = 0;
-        d.cnt[CNT_SEARCH] = 0;
-        d.cnt[CNT_TICKET] = 0;
-    }
+    });
 }
 __global__ __launch_bounds__(64) void ipm_world_Cs_all(NlpDev d, Round r) { ipm_world_Cs_all_body<false>(d, r); }
 __global__ __launch_bounds__(64) void ipm_world_Cs_all_mx(NlpDev d, Round r) { ipm_world_Cs_all_body<true>(d, r); }
@@ -2301,34 +2253,15 @@ template <bool MX>
 __device__ inline void world_Cs_body(const NlpDev& d, const Round& r, WorldState& S, int i) {
     const int lane = threadIdx.x & 63;
     double s = 0.0;
-    if (lane < 2 * r.K) {
-        const double* in = r.partial_s + ((long)i * r.K + (lane >> 1)) * d.nblk * KA + (lane & 1);
-        const int nb = shape_of<MX>(d, r.wl[i]).nblk;
-        for (int b0 = 0; b0 < nb; b0 += 16) {
-            double x[16];
-#pragma unroll
-            for (int u = 0; u < 16; u++) x[u] = in[(long)min(b0 + u, nb - 1) * KA];
-#pragma unroll
-            for (int u = 0; u < 16; u++)
-                if (b0 + u < nb) s = s + x[u];
-        }
-    }
-    const uint64_t u = __builtin_bit_cast(uint64_t, s);
+    if (lane < 2 * r.K)
+        s = fold_blocks(r.partial_s + ((long)i * r.K + (lane >> 1)) * d.nblk * KA + (lane & 1), shape_of<MX>(d, r.wl[i]).nblk, KA, 0.0, 0);
     // the trials' objective values, one per lane in a single load round (a load per trial inside
     // the loop below waited a memory latency per trial)
-    const uint64_t uf = __builtin_bit_cast(uint64_t, lane < r.K ? r.fs[(long)i * r.K + lane] : 0.0);
+    const double fl = lane < r.K ? r.fs[(long)i * r.K + lane] : 0.0;
     int chosen = -1;
     const double mu = S.mu;
     for (int k = 0; k < r.K; k++) {
-        const uint32_t lo0 = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, 2 * k);
-        const uint32_t hi0 = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), 2 * k);
-        const uint32_t lo1 = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, 2 * k + 1);
-        const uint32_t hi1 = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), 2 * k + 1);
-        const uint32_t lof = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)uf, k);
-        const uint32_t hif = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uf >> 32), k);
-        const double logt = __builtin_bit_cast(double, ((uint64_t)hi0 << 32) | lo0);
-        const double rpt = __builtin_bit_cast(double, ((uint64_t)hi1 << 32) | lo1);
-        const double ft = __builtin_bit_cast(double, ((uint64_t)hif << 32) | lof);
+        const double logt = lane_double(s, 2 * k), rpt = lane_double(s, 2 * k + 1), ft = lane_double(fl, k);
         // (the filter does not change while a search goes on: an acceptance ends it)
         const bool filt = filter_pass(S, rpt, ft - mu * logt);
         if (threadIdx.x == 0 && chosen == k - 1 && S.status == 0 && S.searching) {
@@ -2339,37 +2272,8 @@ __device__ inline void world_Cs_body(const NlpDev& d, const Round& r, WorldState
     if (threadIdx.x == 0) S.spec_k = chosen;
 }
 
-// pass D: accept the trial point — slacks, multipliers, BFGS ingredients
-template <bool MX>
-__device__ __attribute__((always_inline)) void ipm_rows_D_body(const NlpDev& d, const Round& r) {
-    const int w = world_of(r, blockIdx.y);
-    const Shape sh = shape_of<MX>(d, w);
-    if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
-    const WorldState& S = d.ws[w];
-    if (S.status != 0) return;
-    __shared__ double lds[(ROW_THREADS / 64) * NA];
-    const double mu = S.mu, ad = S.ad, alpha = S.alpha;
-    double wn[NF];
-#pragma unroll
-    for (int j = 0; j < NF; j++) wn[j] = 0;
-    const long r0 = (long)blockIdx.x * d.chunk;
-    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.R; r += blockDim.x) {
-        double a[NF];
-        row_va(d, sh, 1 - S.cur, w, (int)r, S.xt, a);
-        const long i = (long)w * d.R + r;
-        double L, U;
-        row_bounds(d, sh, i, (int)r, L, U);
-        row_D(d, i, a, L, U, mu, ad, alpha, wn);
-    }
-    double* out = d.partial2 + ((long)w * d.nblk + blockIdx.x) * KA2;
-    const int kinds[NF] = {};
-    block_reduce_n(wn, kinds, lds, out);
-}
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_D(NlpDev d, Round r) { ipm_rows_D_body<false>(d, r); }
-__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_D_mx(NlpDev d, Round r) { ipm_rows_D_body<true>(d, r); }
-
-// pass D's world step: BFGS update, accept the trial point; every lane of the wave calls it. The
-// vectors and scalars are formed by every lane alike (the same arithmetic in the same order, so the
+// pass D's world step (its rows: rows_DA_body): BFGS update, accept the trial point; every lane of
+// the wave calls it. The vectors and scalars are formed by every lane alike (the same arithmetic in the same order, so the
 // same values on every lane, at the cost of one lane), and lane l < 49 updates H's element l: the
 // update's 98 divisions run side by side instead of one after another on lane 0. Within the one
 // wave, every lane's reads of H precede the first write in program order.
@@ -2443,33 +2347,16 @@ __device__ inline void world_D_body(const NlpDev& d, WorldState& S, int w) {
     S.iter++;
     if (S.nfail >= 3) S.status = 3;
 }
-template <bool MX>
-__device__ __attribute__((always_inline)) void ipm_world_D_body(const NlpDev& d, const Round& r) {
-    const int w = world_of(r, blockIdx.x);
-    __shared__ WorldState S;
-    ws_copy(S, d.ws[w]);
-    __syncthreads();
-    const bool act = S.status == 0;
-    world_D_body<MX>(d, S, w);
-    __syncthreads();
-    if (act) ws_copy(d.ws[w], S);
-}
-__global__ __launch_bounds__(64) void ipm_world_D(NlpDev d, Round r) { ipm_world_D_body<false>(d, r); }
-__global__ __launch_bounds__(64) void ipm_world_D_mx(NlpDev d, Round r) { ipm_world_D_body<true>(d, r); }
 // the fused passes' world step: D's (of the previous iteration), then A's, one wave
 template <bool MX>
 __device__ __attribute__((always_inline)) void ipm_world_DA_body(const NlpDev& d, const Round& r, int nside) {
     if (r.lcount && blockIdx.x >= *r.lcount) return;
     const int w = world_of(r, blockIdx.x);
-    __shared__ WorldState S;
-    ws_copy(S, d.ws[w]);
-    __syncthreads();
-    const bool act = S.status == 0;
-    world_D_body<MX>(d, S, w);
-    __syncthreads();  // lane 0's WorldState stores before every lane's reads in world_A_body
-    world_A_body<MX>(d, S, w, nside);
-    __syncthreads();
-    if (act) ws_copy(d.ws[w], S);
+    world_step(d, true, w, 0, [&](WorldState& S) {
+        world_D_body<MX>(d, S, w);
+        __syncthreads();  // lane 0's WorldState stores before every lane's reads in world_A_body
+        world_A_body<MX>(d, S, w, nside);
+    });
 }
 __global__ __launch_bounds__(64) void ipm_world_DA(NlpDev d, Round r, int nside) { ipm_world_DA_body<false>(d, r, nside); }
 __global__ __launch_bounds__(64) void ipm_world_DA_mx(NlpDev d, Round r, int nside) { ipm_world_DA_body<true>(d, r, nside); }
@@ -2510,10 +2397,8 @@ __device__ inline double resto_barrier(const NlpDev& d, const double* x) {
 
 template <bool MX>
 __device__ __attribute__((always_inline)) void resto_rows_G_body(const NlpDev& d, const Round& r) {
-    if (r.lcount && blockIdx.y >= *r.lcount) return;
-    const int w = world_of(r, blockIdx.y);
-    const Shape sh = shape_of<MX>(d, w);
-    if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
+    const auto [w, sh, r0, wb, rows] = row_block<MX>(d, r, blockIdx.y, true);
+    if (!rows) return;
     const WorldState& S = d.ws[w];
     if (S.status != WS_RESTO) return;
     __shared__ double lds[(ROW_THREADS / 64) * NRG];
@@ -2523,7 +2408,6 @@ __device__ __attribute__((always_inline)) void resto_rows_G_body(const NlpDev& d
     for (int k = 0; k < 28; k++) M[k] = 0;
 #pragma unroll
     for (int j = 0; j < NF; j++) b[j] = 0;
-    const long r0 = (long)blockIdx.x * d.chunk, wb = (long)w * d.R;
     for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.m; r += blockDim.x) {
         const long i = wb + r;
         const RowBounds B(d, sh, i, wb, (int)r);
@@ -2632,105 +2516,93 @@ __device__ inline void resto_step(const NlpDev& d, WorldState& S, const double (
 // searching) into the mapped host flags and resets the ticket counters
 __device__ inline void resto_count(const NlpDev& d, bool mine, int flag) {
     if (mine) atomicAdd(&d.cnt[CNT_RUN], 1u);
-    __threadfence();
-    if (atomicAdd(&d.cnt[CNT_TICKET], 1u) == gridDim.x - 1) {
-        __threadfence();
-        d.flags[flag] = (int)atomicAdd(&d.cnt[CNT_RUN], 0u);
-        d.cnt[CNT_RUN] = 0;
-        d.cnt[CNT_TICKET] = 0;
-    }
+    last_block(d, [&](unsigned n, unsigned) { d.flags[flag] = (int)n; });
 }
 
 template <bool MX>
 __device__ __attribute__((always_inline)) void resto_world_G_body(const NlpDev& d, const Round& r) {
     if (r.lcount && blockIdx.x >= *r.lcount) return;  // (one-round search: no count published)
     const int w = world_of(r, blockIdx.x);
-    __shared__ WorldState S;
-    ws_copy(S, d.ws[w]);
-    __syncthreads();
-    const bool act = S.status == WS_RESTO;
-    if (act) {
+    const WorldState* const out = world_step(d, true, w, WS_RESTO, [&](WorldState& S) {
+        if (S.status != WS_RESTO) return;
         double P[NRG], init[NRG];
         int op[NRG];
 #pragma unroll
         for (int k = 0; k < NRG; k++) { init[k] = 0; op[k] = k == 36 ? 1 : 0; }
         world_partials(d, w, shape_of<MX>(d, w).nblk, init, op, P);
-        if (threadIdx.x == 0) {
-            if (S.rpend) {  // the step chosen last iteration, evaluated in the trial slot
-                for (int j = 0; j < NF; j++) S.x[j] = S.xt[j];
-                S.cur = 1 - S.cur;
-                S.iter++;
-                S.rpend = 0;
-            }
-            resto_step(d, S, P);
+        if (threadIdx.x != 0) return;
+        if (S.rpend) {  // the step chosen last iteration, evaluated in the trial slot
+            for (int j = 0; j < NF; j++) S.x[j] = S.xt[j];
+            S.cur = 1 - S.cur;
+            S.iter++;
+            S.rpend = 0;
         }
-    }
-    __syncthreads();
-    if (act) ws_copy(d.ws[w], S);
-    if (threadIdx.x == 0 && r.rflag >= 0) resto_count(d, S.status == WS_RESTO, r.rflag);
+        resto_step(d, S, P);
+    });
+    if (threadIdx.x == 0 && r.rflag >= 0) resto_count(d, out->status == WS_RESTO, r.rflag);
 }
 __global__ __launch_bounds__(64) void resto_world_G(NlpDev d, Round r) { resto_world_G_body<false>(d, r); }
 __global__ __launch_bounds__(64) void resto_world_G_mx(NlpDev d, Round r) { resto_world_G_body<true>(d, r); }
 
-// sum e^2 at the trial point (the trial slot's full evaluation, EVAL_TRIAL)
-template <bool MX>
-__device__ __attribute__((always_inline)) void resto_rows_V_body(const NlpDev& d, const Round& r) {
-    const int w = world_of(r, blockIdx.y);
-    const Shape sh = shape_of<MX>(d, w);
-    if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
-    const WorldState& S = d.ws[w];
-    if (!(S.status == WS_RESTO && S.searching)) return;
+// sum e^2 of one row block at a trial point into out; value(r) is constraint row r's value there
+template <typename F>
+__device__ __attribute__((always_inline)) void rows_V_sum(const NlpDev& d, const RowBlock& b, F&& value, double* out) {
     __shared__ double lds[(ROW_THREADS / 64) * NRG];
-    const int slot = 1 - S.cur;
     double V = 0;
-    const long r0 = (long)blockIdx.x * d.chunk, wb = (long)w * d.R;
-    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.m; r += blockDim.x) {
-        const long i = wb + r;
-        const RowBounds B(d, sh, i, wb, (int)r);
-        const double v = d.g[gidx(d, slot, w, r)];
+    for (long r = b.r0 + threadIdx.x; r < b.r0 + d.chunk && r < b.sh.m; r += blockDim.x) {
+        const long i = b.wb + r;
+        const RowBounds B(d, b.sh, i, b.wb, (int)r);
         double e, sg, e0;
-        resto_row(d, v, B.L(), B.U(), e, sg, e0);
+        resto_row(d, value(r), B.L(), B.U(), e, sg, e0);
         V += e * e;
     }
     double vv[1] = {V};
     const int kinds[1] = {0};
-    block_reduce_n(vv, kinds, lds, d.partial + ((long)w * d.nblk + blockIdx.x) * KA);
+    block_reduce_n(vv, kinds, lds, out);
+}
+// the trial is the world's current one (the trial slot's full evaluation, EVAL_TRIAL)
+template <bool MX>
+__device__ __attribute__((always_inline)) void resto_rows_V_body(const NlpDev& d, const Round& r) {
+    const RowBlock b = row_block<MX>(d, r, blockIdx.y, false);
+    if (!b.rows) return;
+    const WorldState& S = d.ws[b.w];
+    if (!(S.status == WS_RESTO && S.searching)) return;
+    const double* G = d.g + gidx(d, 1 - S.cur, b.w, 0);
+    rows_V_sum(d, b, [&](long row) { return G[row]; }, d.partial + ((long)b.w * d.nblk + blockIdx.x) * KA);
 }
 __global__ __launch_bounds__(ROW_THREADS) void resto_rows_V(NlpDev d, Round r) { resto_rows_V_body<false>(d, r); }
 __global__ __launch_bounds__(ROW_THREADS) void resto_rows_V_mx(NlpDev d, Round r) { resto_rows_V_body<true>(d, r); }
 
-// the Armijo test of the round's trial; a rejected trial halves alpha (max_ls trials, then the
-// phase fails: local infeasibility at the current point)
+// the Armijo test of one trial (S.xt, S.alpha; V its sum e^2), on lane 0: accepted, the step waits
+// for its full evaluation; a rejected trial halves alpha (max_ls trials, then the phase fails: local
+// infeasibility at the current point)
+__device__ inline void resto_armijo(const NlpDev& d, WorldState& S, double V) {
+    S.nevals++;
+    const double phit = 0.5 * V + resto_barrier(d, S.xt);
+    if (phit <= S.phi0 + d.opt.eta * S.alpha * S.Dphi) {
+        S.searching = 0;
+        S.rpend = 1;
+    } else if (++S.ls >= d.opt.max_ls) {
+        S.searching = 0;
+        S.status = 5;
+    } else {
+        S.alpha *= 0.5;
+        for (int j = 0; j < NF; j++) S.xt[j] = S.x[j] + S.alpha * S.dx[j];
+    }
+}
+// one Armijo trial per round
 template <bool MX>
 __device__ __attribute__((always_inline)) void resto_world_V_body(const NlpDev& d, const Round& r) {
     const int w = world_of(r, blockIdx.x);
-    __shared__ WorldState S;
-    ws_copy(S, d.ws[w]);
-    __syncthreads();
-    const bool act = S.status == WS_RESTO;
-    if (act && S.searching) {
+    const WorldState* const out = world_step(d, true, w, WS_RESTO, [&](WorldState& S) {
+        if (!(S.status == WS_RESTO && S.searching)) return;
         double P[1];
         const double init[1] = {0.0};
         const int op[1] = {0};
         world_partials(d, w, shape_of<MX>(d, w).nblk, init, op, P);
-        if (threadIdx.x == 0) {
-            S.nevals++;
-            const double phit = 0.5 * P[0] + resto_barrier(d, S.xt);
-            if (phit <= S.phi0 + d.opt.eta * S.alpha * S.Dphi) {
-                S.searching = 0;
-                S.rpend = 1;
-            } else if (++S.ls >= d.opt.max_ls) {
-                S.searching = 0;
-                S.status = 5;
-            } else {
-                S.alpha *= 0.5;
-                for (int j = 0; j < NF; j++) S.xt[j] = S.x[j] + S.alpha * S.dx[j];
-            }
-        }
-    }
-    __syncthreads();
-    if (act) ws_copy(d.ws[w], S);
-    if (threadIdx.x == 0) resto_count(d, S.status == WS_RESTO && S.searching, FLAG_SEARCH);
+        if (threadIdx.x == 0) resto_armijo(d, S, P[0]);
+    });
+    if (threadIdx.x == 0) resto_count(d, out->status == WS_RESTO && out->searching, FLAG_SEARCH);
 }
 __global__ __launch_bounds__(64) void resto_world_V(NlpDev d, Round r) { resto_world_V_body<false>(d, r); }
 __global__ __launch_bounds__(64) void resto_world_V_mx(NlpDev d, Round r) { resto_world_V_body<true>(d, r); }
@@ -2742,27 +2614,12 @@ __global__ __launch_bounds__(64) void resto_world_V_mx(NlpDev d, Round r) { rest
 // EVAL_CHOSEN, r.resto). The decisions and the chosen point are those of the sequential rounds.
 template <bool MX>
 __device__ __attribute__((always_inline)) void resto_rows_Vs_body(const NlpDev& d, const Round& r) {
-    const int i = blockIdx.y / r.K;
-    if (r.lcount && (unsigned)i >= *r.lcount) return;
-    const int w = r.wl[i];
-    const Shape sh = shape_of<MX>(d, w);
-    if (MX && (int)blockIdx.x >= sh.nblk) return;  // a block past this world's rows
-    const WorldState& S = d.ws[w];
+    const RowBlock b = row_block<MX>(d, r, blockIdx.y / r.K, true);
+    if (!b.rows) return;
+    const WorldState& S = d.ws[b.w];
     if (!(S.status == WS_RESTO && S.searching)) return;
-    __shared__ double lds[(ROW_THREADS / 64) * NRG];
     const double* G = r.gs + (long)blockIdx.y * d.m;
-    double V = 0;
-    const long r0 = (long)blockIdx.x * d.chunk, wb = (long)w * d.R;
-    for (long r = r0 + threadIdx.x; r < r0 + d.chunk && r < sh.m; r += blockDim.x) {
-        const long ii = wb + r;
-        const RowBounds B(d, sh, ii, wb, (int)r);
-        double e, sg, e0;
-        resto_row(d, G[r], B.L(), B.U(), e, sg, e0);
-        V += e * e;
-    }
-    double vv[1] = {V};
-    const int kinds[1] = {0};
-    block_reduce_n(vv, kinds, lds, r.partial_s + ((long)blockIdx.y * d.nblk + blockIdx.x) * KA);
+    rows_V_sum(d, b, [&](long row) { return G[row]; }, r.partial_s + ((long)blockIdx.y * d.nblk + blockIdx.x) * KA);
 }
 __global__ __launch_bounds__(ROW_THREADS) void resto_rows_Vs(NlpDev d, Round r) { resto_rows_Vs_body<false>(d, r); }
 __global__ __launch_bounds__(ROW_THREADS) void resto_rows_Vs_mx(NlpDev d, Round r) { resto_rows_Vs_body<true>(d, r); }
@@ -2773,70 +2630,28 @@ template <bool MX>
 __device__ __attribute__((always_inline)) void resto_world_Vs_body(const NlpDev& d, const Round& r) {
     const bool valid = !r.lcount || blockIdx.x < *r.lcount;
     const int i = blockIdx.x, w = valid ? r.wl[i] : 0;
-    __shared__ WorldState S;
-    bool act = false;
-    if (valid) {
-        ws_copy(S, d.ws[w]);
-        __syncthreads();
-        act = S.status == WS_RESTO;
-    }
-    if (act && S.searching) {
-        // trial k's sum on lane k, its blocks combined in order (world_partials_at's arithmetic)
+    const WorldState* const out = world_step(d, valid, w, WS_RESTO, [&](WorldState& S) {
+        if (!(S.status == WS_RESTO && S.searching)) return;
+        // trial k's sum on lane k, then the tests in trial order (S.xt, S.alpha are trial k's)
         const int lane = threadIdx.x & 63;
         double v = 0.0;
-        if (lane < r.K) {
-            const double* in = r.partial_s + ((long)i * r.K + lane) * d.nblk * KA;
-            const int nblk = shape_of<MX>(d, w).nblk;
-            for (int b0 = 0; b0 < nblk; b0 += 16) {
-                double xb[16];
-#pragma unroll
-                for (int u = 0; u < 16; u++) xb[u] = in[(long)min(b0 + u, nblk - 1) * KA];
-#pragma unroll
-                for (int u = 0; u < 16; u++)
-                    if (b0 + u < nblk) v = v + xb[u];
-            }
-        }
-        const uint64_t u = __builtin_bit_cast(uint64_t, v);
+        if (lane < r.K) v = fold_blocks(r.partial_s + ((long)i * r.K + lane) * d.nblk * KA, shape_of<MX>(d, w).nblk, KA, 0.0, 0);
         for (int k = 0; k < r.K; k++) {
-            const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, k);
-            const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), k);
-            const double Vk = __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-            if (threadIdx.x == 0 && S.searching) {
-                // resto_world_V's test of trial k (S.xt, S.alpha are trial k's)
-                S.nevals++;
-                const double phit = 0.5 * Vk + resto_barrier(d, S.xt);
-                if (phit <= S.phi0 + d.opt.eta * S.alpha * S.Dphi) {
-                    S.searching = 0;
-                    S.rpend = 1;
-                } else if (++S.ls >= d.opt.max_ls) {
-                    S.searching = 0;
-                    S.status = 5;
-                } else {
-                    S.alpha *= 0.5;
-                    for (int j = 0; j < NF; j++) S.xt[j] = S.x[j] + S.alpha * S.dx[j];
-                }
-            }
+            const double Vk = lane_double(v, k);
+            if (threadIdx.x == 0 && S.searching) resto_armijo(d, S, Vk);
         }
-    }
-    if (valid) {
-        __syncthreads();
-        if (act) ws_copy(d.ws[w], S);
-    }
+    });
+    const bool kept = out && out->status == WS_RESTO;
     if (threadIdx.x != 0) return;
     if (r.rl_app) {  // inside the interior-point loop: the phase list, published by resto_publish
-        if (valid && S.status == WS_RESTO) r.rl_app[atomicAdd(&d.cnt[CNT_RL], 1u)] = w;
+        if (kept) r.rl_app[atomicAdd(&d.cnt[CNT_RL], 1u)] = w;
         return;
     }
-    if (valid && S.status == WS_RESTO) r.wl_run[atomicAdd(&d.cnt[CNT_RUN], 1u)] = w;
-    __threadfence();
-    if (atomicAdd(&d.cnt[CNT_TICKET], 1u) == gridDim.x - 1) {
-        __threadfence();
-        const unsigned n = atomicAdd(&d.cnt[CNT_RUN], 0u);
+    if (kept) r.wl_run[atomicAdd(&d.cnt[CNT_RUN], 1u)] = w;
+    last_block(d, [&](unsigned n, unsigned) {
         *r.lrun_out = n;
         *r.nrun_flag = (int)n;
-        d.cnt[CNT_RUN] = 0;
-        d.cnt[CNT_TICKET] = 0;
-    }
+    });
 }
 __global__ __launch_bounds__(64) void resto_world_Vs(NlpDev d, Round r) { resto_world_Vs_body<false>(d, r); }
 __global__ __launch_bounds__(64) void resto_world_Vs_mx(NlpDev d, Round r) { resto_world_Vs_body<true>(d, r); }

@@ -8,6 +8,7 @@ project's other A/B tests: concurrent against sequential, speculative against se
 against full evaluation). Shapes: T = 10 (NJ = 7, rows R = 7 T + 7 T O + 35 per world, 1024 rows per
 block), counts chosen so that the first world is not the largest, some worlds have no obstacles and
 counts repeat; [13, 14] puts a one-block world (R = 1015) into a two-block grid (R = 1085)."""
+import contextlib
 import os
 
 import numpy as np
@@ -178,6 +179,69 @@ def test_saved_worlds_mixed_bitwise_on_one_reach_kernel():
                      not_ran=("batch_uniform",) + engine_paths("narrow")["not_ran"])
         P.close()
         assert_bitwise(res, plan_grouped(worlds, T=100), "one reach kernel")
+
+
+EDGE_COUNTS = (14, 0, 13, 1)
+ARMS = ("default", "rounds", "after_loop", "sequential", "tail")
+
+
+def arm_of(name):
+    """(the setting of a loop form or None, the paths a planner created under it must show)"""
+    return {
+        "default": (None, dict(ran=("batch_mixed", "resto_inline"))),
+        "rounds": (("ARMOUR_RESTO_ROUNDS", "1"), dict(ran=("resto_rounds", "resto_after_loop"), not_ran=("resto_inline",))),
+        "after_loop": (("ARMOUR_RESTO_INLINE", "0"), dict(ran=("resto_one_round", "resto_after_loop"), not_ran=("resto_inline",))),
+        "sequential": (("ARMOUR_NO_SPEC", "1"), dict(ran=("ls_sequential",), not_ran=("ls_speculative", "ls_one_round"))),
+        "tail": (("ARMOUR_TAIL_WORLDS", "1000"), dict(ran=("ipm_iter_tail", ("ls_one_round", "ls_speculative")))),
+    }[name]
+
+
+@pytest.fixture(scope="module")
+def edge_worlds():
+    """the 33 worlds of domain_edges.plan_cases() (limits, speeds, far goals: 20 end in local
+    infeasibility, four of the others backtrack), world i with the first (14, 0, 13, 1)[i % 4] boxes of
+    make_world(3, 14) (the first three are the base world's own): two row blocks (R = 1085) for 14
+    obstacles, one and an idle second block for the others. With the oracle's verdicts, computed once."""
+    import domain_edges as DE
+
+    assert DE.T == T
+    boxes = np.asarray(A.make_world(3, 14)[4], dtype=np.float64).reshape(14, 12)
+    assert np.array_equal(boxes[:3], np.asarray(DE.base_world()[4]).reshape(3, 12))
+    worlds = [tuple(w[:4]) + (boxes[:EDGE_COUNTS[i % 4]].copy(),) for i, (_, w) in enumerate(DE.plan_cases())]
+    assert len(worlds) == 33
+    want = []
+    for world in worlds:
+        R = OraclePlanner(*world, T=T, threads=4)
+        R.reach()
+        ro = R.plan()
+        want.append((ro["feasible"], ro["status"]))
+    return worlds, want
+
+
+@pytest.mark.parametrize("arm", ARMS)
+def test_phases_and_backtracking_in_a_mixed_batch_bitwise(edge_worlds, arm):
+    """The restoration and speculative kernels' mixed instantiations on worlds that enter a phase or
+    backtrack, with idle second row blocks inside the phase launches: under each loop form, the mixed
+    plan is bitwise the uniform batches' plan under the same setting, every world's verdict is the
+    oracle's, and exactly 20 worlds end in local infeasibility."""
+    from test_gpu_plane_cache import env
+
+    worlds, want = edge_worlds
+    setting, paths = arm_of(arm)
+    with env(*setting) if setting else contextlib.nullcontext():
+        P = A.Planner(T=T, max_obstacles=14, max_worlds=len(worlds))
+        res, _ = P.plan_mixed(worlds)
+        counts = P.path_counts()
+        P.close()
+        grouped = plan_grouped(worlds)
+    assert_bitwise(res, grouped, arm)
+    for w, (r, (feasible, status)) in enumerate(zip(res, want)):
+        assert r["feasible"] == feasible and r["status"] == status, (arm, w, r["feasible"], r["status"])
+    stalled = [w for w, r in enumerate(res) if r["status"] == 4]
+    print(f"{arm}: locally infeasible {stalled}; evaluations - iterations "
+          f"{[r['evaluations'] - r['iterations'] for r in res]}")
+    assert len(stalled) == 20, stalled
+    assert_paths(counts, **paths)
 
 
 def test_mixed_errors_and_uniform_list():

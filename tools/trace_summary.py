@@ -10,7 +10,7 @@ idx = [i for i, r in enumerate(rows) if "reach_kernel" in r["Kernel_Name"]]
 R = rows[idx[-1]:]
 t0 = int(R[0]["Start_Timestamp"])
 names = ["eval_kernel", "eval_trials_kernel", "ipm_world_Cs", "ipm_rows_A", "ipm_rows_DA", "ipm_rows_B",
-         "ipm_rows_D", "ipm_world_A", "ipm_world_B", "ipm_world_C", "ipm_world_D", "lane_reach", "reach_kernel",
+         "ipm_world_A", "ipm_world_B", "ipm_world_C", "ipm_world_DA", "lane_reach", "reach_kernel",
          "bounds", "feasible", "jrs", "ipm_world_init", "ipm_rows_init"]
 
 
