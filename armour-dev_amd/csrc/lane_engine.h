@@ -15,6 +15,13 @@
 // key order, group heads, compaction scans — happens once per bundle here; the coefficient
 // arithmetic is lane-parallel with coalesced 512-byte row accesses, and the thread-0 ops of the
 // per-job engine (1-D PZs, rotations, emits, torque radius) become plain lane code.
+//
+// Shared with the per-job engine, written once there: the handle (PZH, set_meta), an operator's
+// term count and term-list builder (reach.h op_terms, op_terms_of), the term index arithmetic
+// (pz_engine.h TermIndex, the base of LTerms), the OP_CONST operand choice (const_operand), the group
+// policies' decisions (PolBlock, PolCrossPPT) and the constant-cross table. Own on purpose: the
+// operand view LSrc and the generators, rank() (no RK batching), block_scan (wave loop unrolled at
+// compile time), bcast0 (readfirstlane) and the round loops.
 #pragma once
 #include "reach.h"
 
@@ -66,18 +73,11 @@ DI GAS T* gas(T* p) { return (GAS T*)p; }
 template <class T>
 DI GAS const T* gas(const T* p) { return (GAS const T*)p; }
 
-// bundle handle (LDS): union structure + where the lane data lives
-struct LH {
-    int R, C;
-    int cnt;       // union monomials
-    int stride;    // coefficient rows per monomial (parent's R*C for views)
-    long hoff;     // hash / mask index
-    long coff;     // first coefficient row; row r of lane l is c[r * LG + l]
-    int comp;      // element view (>= 0) of the parent's block
-    int scaled;
-    double scale;
-    int off;       // header payload rows in the pool: centre[n], ind0[n], ind1[n], absum[n]
-};
+// bundle handle (LDS): the per-job engine's handle (pz_engine.h PZH, set_meta), read for a bundle:
+// cnt counts the union's monomials, hoff indexes the union hashes and presence masks, coff is the
+// first coefficient row (row r of lane l is c[r * LG + l]; stride rows per monomial), and off is the
+// header's first payload row in the pool (centre[n], ind0[n], ind1[n], absum[n] rows)
+using LH = PZH;
 
 struct LArena {
     uint64_t* h;   // union hashes
@@ -174,18 +174,12 @@ DI GAS const T* opaque(GAS const T* p) { return (GAS const T*)(uintptr_t)opaque(
 
 // per-lane header rows
 DI double& P(const LCtx& x, int row) { return x.pool[(long)row * LG + x.lane]; }
-DI int nel(const LH& h) { return h.R * h.C; }
 DI double& cen(const LCtx& x, const LH& h, int e) { return P(x, h.off + e); }
 DI double& ind(const LCtx& x, const LH& h, int v, int e) { return P(x, h.off + (1 + v) * nel(h) + e); }
 DI double& abs_(const LCtx& x, const LH& h, int e) { return P(x, h.off + 3 * nel(h) + e); }
 
 DI void err_or(const LCtx& x, int bits) { atomicOr(x.err, bits); }
 
-// meta of an empty R x C handle (one lane writes; the slot keeps its payload offset)
-DI void set_meta(LH& h, int R, int C) {
-    h.R = R; h.C = C; h.cnt = 0; h.stride = R * C; h.hoff = 0; h.coff = 0;
-    h.comp = -1; h.scaled = 0; h.scale = 1.0;
-}
 // zero this lane's header of an R x C handle (payload rows of class R*C)
 DI void hdr_zero(const LCtx& x, int off, int n) {
     for (int q = 0; q < 4 * n; q++) x.pool[(long)(off + q) * LG + x.lane] = 0.0;
@@ -247,51 +241,10 @@ DI LSrc src_of(const LCtx& x, const LH& p) {
     return s;
 }
 
-// term list of an operator over the union lists (same layout as pz_engine.h Terms): kind 0 =
-// product (T1 a_i x B.c, T2 A.c x b_j, T3 a_i x b_j), kind 1 = concatenation of up to 3 sources
-struct LTerms {
-    int kind, ns;
-    LSrc S[3];
-    int places, negs;
-    int AR, AC, BC;
-    int nout;
-    uint32_t nbm;
+// term list of an operator over the union lists: the per-job engine's shape table and index
+// arithmetic (pz_engine.h TermIndex), over the bundle's sources
+struct LTerms : TermIndex<LSrc> {
     double Ac[9], Bc[9];  // this lane's operand centres (products)
-    DI void split(int q, int& i, int& j) const {
-        const int nb = S[1].cnt;
-        i = nb == 1 ? q : (int)__umulhi((uint32_t)q, nbm);
-        j = q - i * nb;
-    }
-    DI void which(int p, int& s, int& k) const {
-        s = 0;
-        if (p >= S[0].cnt) { p -= S[0].cnt; s = 1; if (p >= S[1].cnt) { p -= S[1].cnt; s = 2; } }
-        k = p;
-    }
-    DI uint64_t hash(int p) const {
-        if (kind == 0) {
-            const int na = S[0].cnt, nb = S[1].cnt;
-            if (p < na) return S[0].hash(p);
-            if (p < na + nb) return S[1].hash(p - na);
-            int i, j;
-            split(p - na - nb, i, j);
-            return S[0].hash(i) + S[1].hash(j);
-        }
-        int s, k;
-        which(p, s, k);
-        return s == 0 ? S[0].hash(k) : s == 1 ? S[1].hash(k) : S[2].hash(k);
-    }
-    DI void prod(const double* a, const double* b, double* out) const {
-        const bool as = AR == 1 && AC == 1, bs = S[1].n == 1;
-        if (as) {
-#pragma unroll
-            for (int e = 0; e < 9; e++) out[e] = a[0] * b[e];
-        } else if (bs) {
-#pragma unroll
-            for (int e = 0; e < 9; e++) out[e] = a[e] * b[0];
-        } else {
-            matmul(a, AR, AC, b, BC, out);
-        }
-    }
     // operand rows of term p for this lane: u = left factor, w = right factor (products)
     DI void factors(int p, double* u, double* w, int lane) const {
         const int na = S[0].cnt, nb = S[1].cnt;
@@ -1481,45 +1434,6 @@ DI void torque_radius(const LCtx& x, const RobotParams& rp, const ReachOut& out)
 }
 
 // ---- the program ----------------------------------------------------------------------------
-DI void op_terms_of(const LCtx& x, const Op& op, LTerms& T) {
-    const LH& A = x.H[op.a];
-    const LH& B = x.H[op.b];
-    T.ns = 2;
-    T.places = 0;
-    T.negs = 0;
-    T.S[0] = src_of(x, A);
-    T.S[1] = src_of(x, B);
-    switch (op.code) {
-        case OP_MUL:
-        case OP_CROSS_PP: {
-            T.kind = 0;
-            T.AR = op.code == OP_CROSS_PP ? 3 : A.R;
-            T.AC = op.code == OP_CROSS_PP ? 1 : A.C;
-            T.BC = op.code == OP_CROSS_PP ? 1 : B.C;
-            T.nbm = B.cnt > 1 ? 0xFFFFFFFFu / (uint32_t)B.cnt + 1u : 0u;
-            const bool as = A.R == 1 && A.C == 1, bs = B.R == 1 && B.C == 1;
-            T.nout = op.code == OP_CROSS_PP ? 3 : (as ? nel(B) : (bs ? nel(A) : A.R * B.C));
-            break;
-        }
-        case OP_ADD:
-            T.kind = 1;
-            T.negs = op.i < 0 ? 2 : 0;
-            T.nout = nel(A);
-            break;
-        case OP_STACK3:
-            T.kind = 1;
-            T.ns = 3;
-            T.S[2] = src_of(x, x.H[op.c]);
-            T.places = 1 | (2 << 4) | (3 << 8);
-            T.nout = 3;
-            break;
-        default:  // OP_ADD1D: self = a, 1-D = b at component i
-            T.kind = 1;
-            T.places = (op.i + 1) << 4;
-            T.nout = nel(A);
-            break;
-    }
-}
 // this lane's operand centres, for the runtime-shaped (GAny) product readers only
 DI void terms_centres(const LCtx& x, const Op& op, LTerms& T) {
     const LH& A = x.H[op.a];
@@ -1530,13 +1444,6 @@ DI void terms_centres(const LCtx& x, const Op& op, LTerms& T) {
         T.Ac[e] = e < na ? cen(x, A, e) : 0.0;
         T.Bc[e] = e < nb ? cen(x, B, e) : 0.0;
     }
-}
-DI int op_terms(const LCtx& x, const Op& op) {
-    const LH& A = x.H[op.a];
-    const LH& B = x.H[op.b];
-    if (op.code == OP_MUL || op.code == OP_CROSS_PP) return A.cnt + B.cnt + A.cnt * B.cnt;
-    if (op.code == OP_STACK3) return A.cnt + B.cnt + x.H[op.c].cnt;
-    return A.cnt + B.cnt;
 }
 // output header of a simplifying op for this lane's job (wave 0), meta by lane 0
 DI void op_header(const LCtx& x, const Op& op) {
@@ -1620,10 +1527,9 @@ DI void run_program(LCtx& x, const RobotParams& rp, const Op* prog, int nops, co
                         case OP_MAKEROT: make_rot(x, m.o, rp, m.i); break;
                         case OP_MAKEBOX: make_box(x, m.o, rp, m.i); break;
                         case OP_CONST:
-                            if (m.a == CONST_RPY) make_const(x, m.o, 3, 3, rp.rpy[m.i], 0.0);
-                            else if (m.a == CONST_TRANS) make_const(x, m.o, 3, 1, &rp.trans[3 * m.i], 0.0);
-                            else if (m.a == CONST_MASS) make_const(x, m.o, 1, 1, &rp.mass[m.i], rp.mass_uncertainty);
-                            else make_const(x, m.o, 3, 3, &rp.inertia[9 * m.i], rp.inertia_uncertainty);
+                            const_operand(rp, m.a, m.i, [&](int R, int C, const double* v, double unc) __attribute__((always_inline)) {
+                                make_const(x, m.o, R, C, v, unc);
+                            });
                             break;
                         case OP_ZERO: {
                             LH& h = x.H[m.o];
@@ -1662,8 +1568,8 @@ DI void run_program(LCtx& x, const RobotParams& rp, const Op* prog, int nops, co
             }
             default: {
                 LTerms T;
-                op_terms_of(x, op, T);
-                const int N = op_terms(x, op);
+                op_terms_of(x.H, op, T, [&](const LH& p) __attribute__((always_inline)) { return src_of(x, p); });
+                const int N = op_terms(x.H, op);
                 nterms = N;
                 long long ph_t = x.prof ? clock64() : 0;
                 if (x.wave == 0) op_header(x, op);

@@ -26,8 +26,10 @@
 //     pass over its operands' monomials.
 // All device functions are force-inlined: the reach kernel is an interpreter whose op bodies
 // are inlined once each into one switch (reach.h), so the program runs with no device calls.
-// The group abstraction (Grp) lets the same code run as a sequential host emulation in tests.
+// The same code also runs as a sequential host emulation in tests; what the two builds do
+// differently is collected in the platform seam below.
 #pragma once
+#include <cassert>
 #include "common.h"
 #include "wave.h"
 
@@ -40,14 +42,135 @@ constexpr int MAX_SLOTS = 96;  // handle slots of a reach program (ProgramBuilde
 
 namespace armour {
 
+// =============================================================================================
+// PLATFORM SEAM. This header and reach.h compile twice: in the device pass, and for the sequential
+// host emulation (tests/emu) that the CPU suites run against the oracle. Everything that differs
+// between the two is in this section, each item in a device form and a host form; below it neither
+// file asks which pass it is in (one marked exception here: the wave-0 simplify, device only).
+//
+// The emulation is single-threaded by construction: it runs a job as the one-thread group
+// Grp{0, 1}. So its barrier is nothing, a group reduction or scan is the thread's own value, a
+// shared counter is a plain variable, and the reduction / scan scratch (Ctx::red, Ctx::iscan) is
+// never touched. The host forms assert g.n == 1.
 struct Grp {
     int tid, n;
-    AI void sync() const {
+    AI void sync() const;  // the group barrier
+};
+// emulation hooks' sinks (tests/emu sets them): per op [code, class, term kind, |S0|, |S1|, N, runs,
+// output count], and per op the output handle's monomial hashes (structure studies)
+inline int* g_op_stats = nullptr;
+inline void (*g_hash_sink)(int pc, const uint64_t* h, int n) = nullptr;
+
 #if defined(__HIP_DEVICE_COMPILE__)
-        __syncthreads();
+// which pass: guards what only the emulation does (its own squared-threshold search and JRS scalars,
+// reach.h run_program) and the wave-0 paths, which only the device has
+AI bool emulated() { return false; }
+AI void Grp::sync() const { __syncthreads(); }
+// deterministic sum over the group of the slots e < n (n <= 18) of v whose mask bit is set; the
+// totals land in v on every thread. red: LDS [waves][18]
+AI void group_sum(const Grp& g, double* red, double* v, int n, unsigned mask) {
+    UNR for (int e = 0; e < 18; e++) if (e < n && ((mask >> e) & 1)) v[e] = wave_sum(v[e]);
+    const int wave = g.tid >> 6, nw = (g.n + 63) >> 6;
+    if ((g.tid & 63) == 0)
+        UNR for (int e = 0; e < 18; e++) if (e < n && ((mask >> e) & 1)) red[wave * 18 + e] = v[e];
+    g.sync();
+    UNR for (int e = 0; e < 18; e++) {
+        if (e < n && ((mask >> e) & 1)) {
+            double s = red[e];
+            for (int w = 1; w < nw; w++) s = s + red[w * 18 + e];
+            v[e] = s;
+        }
+    }
+    g.sync();
+}
+// exclusive prefix of s over the group's threads, in thread order, and the total. iscan: LDS [waves]
+AI int group_scan(const Grp& g, int* iscan, int s, int& total) {
+    const int lane = g.tid & 63, wave = g.tid >> 6, nw = (g.n + 63) >> 6;
+    const int inc = wave_incl_scan(s);
+    if (lane == 63) iscan[wave] = inc;
+    g.sync();
+    int base = 0;
+    total = 0;
+    for (int w = 0; w < nw; w++) {
+        const int t = iscan[w];
+        if (w < wave) base += t;
+        total += t;
+    }
+    return base + inc - s;
+}
+// LDS updates that several lanes may make at once (a lane-parallel group of thread-0 ops, reach.h)
+AI void err_or(int* err, int bits) { atomicOr(err, bits); }
+AI void bytes_add(double* bytes, double b) { atomicAdd(bytes, b); }
+AI long bump(long* used, long n) { return (long)atomicAdd((unsigned long long*)used, (unsigned long long)n); }  // returns the old value
+// high half of a 32 x 32 bit product (TermIndex::split)
+AI uint32_t mulhi_u32(uint32_t a, uint32_t b) { return __umulhi(a, b); }
+// f(e) for e < n <= 64: element e on lane e of wave 0
+template <class F>
+AI void per_lane(const Grp& g, int n, const F& f) {
+    if (g.tid < n) f(g.tid);
+}
+// instrumentation: the cycle stamp, and the per-op profile's accumulation
+AI long long cycles() { return clock64(); }
+AI void prof_add(unsigned long long* p, unsigned long long v) { atomicAdd(p, v); }
+// emulation hooks (run_program): nothing here
+AI void emu_op_stats(int pc, int code, int cls, int kind, int n0, int n1, int N, int runs) {}
+AI void emu_op_count(int pc, int cnt) {}
+AI void emu_hashes(int pc, const uint64_t* h, int n) {}
+#else  // ---- the host forms, one thread
+AI bool emulated() { return true; }
+AI void Grp::sync() const { assert(n == 1); }
+AI void group_sum(const Grp& g, double* red, double* v, int n, unsigned mask) { assert(g.n == 1); }
+AI int group_scan(const Grp& g, int* iscan, int s, int& total) {
+    assert(g.n == 1);
+    total = s;
+    return 0;
+}
+AI void err_or(int* err, int bits) { *err |= bits; }
+AI void bytes_add(double* bytes, double b) { *bytes += b; }
+AI long bump(long* used, long n) {
+    const long old = *used;
+    *used += n;
+    return old;
+}
+AI uint32_t mulhi_u32(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * b) >> 32); }
+template <class F>
+AI void per_lane(const Grp& g, int n, const F& f) {
+    assert(g.n == 1);
+    for (int e = 0; e < n; e++) f(e);
+}
+AI long long cycles() { return 0; }
+AI void prof_add(unsigned long long* p, unsigned long long v) {}
+AI void emu_op_stats(int pc, int code, int cls, int kind, int n0, int n1, int N, int runs) {
+    if (!g_op_stats) return;
+    int* st = g_op_stats + 8 * pc;
+    st[0] = code; st[1] = cls; st[2] = kind; st[3] = n0; st[4] = n1; st[5] = N; st[6] = runs;
+}
+AI void emu_op_count(int pc, int cnt) {
+    if (g_op_stats) g_op_stats[8 * pc + 7] = cnt;
+}
+AI void emu_hashes(int pc, const uint64_t* h, int n) {
+    if (g_hash_sink) g_hash_sink(pc, h, n);
+}
 #endif
+
+// Cycle probe (profiling): adds the cycles since its last stamp to a slot of `slots` (Ctx::phase;
+// null: off). rec says whether this thread records. With cycles() = 0 and no slots the emulation's
+// probes do nothing.
+struct Probe {
+    unsigned long long* slots;
+    bool rec;
+    long long t;
+    AI void stamp_all() { t = slots ? cycles() : 0; }           // every thread stamps
+    AI void stamp() { t = (slots && rec) ? cycles() : 0; }      // the recording thread stamps
+    AI void lap(int k) {
+        if (slots && rec) {
+            const long long c = cycles();
+            slots[k] += (unsigned long long)(c - t);
+            t = c;
+        }
     }
 };
+// =============================================================================================
 
 // PZ handle. Views: comp >= 0 selects one element of the parent's coefficient block (the
 // reference's operator()(r,c), PZsparse.cu:678-697); scaled applies s * c on read (PZ * double,
@@ -90,8 +213,8 @@ struct Ctx {
     double* gout;      // group sums of the simplify in flight, by key position (HBM): cap_glb * 9
     double* stage;     // operand staging (LDS), stage_cap doubles
     int stage_cap;
-    double* red;       // reduction scratch (LDS): [waves * 18] on device, [n * 18] in the emulation
-    int* iscan;        // scan scratch (LDS): [waves] on device, [2 * n] in the emulation
+    double* red;       // reduction scratch (LDS): [waves * 18] (group_sum; unused by the emulation)
+    int* iscan;        // scan scratch (LDS): [waves] (group_scan; unused by the emulation)
     int* err;          // error word (LDS)
     double thr;
     double thr_sq;     // SqThr::s and ::valid of thr (set by the kernel from RobotParams; the
@@ -207,46 +330,6 @@ AI void read_mono(const Ctx& x, const PZH& h, int k, double* out) {
 AI uint64_t mono_hash(const Ctx& x, const PZH& h, int k) { return x.ah[h.hoff + k]; }
 
 // ---------------------------------------------------------------------------------------------
-// wave / block primitives
-#if defined(__HIP_DEVICE_COMPILE__)
-__device__ inline __attribute__((always_inline)) double wsum(double v) { return wave_sum(v); }
-__device__ inline __attribute__((always_inline)) long bcast0(long v) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 0);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), 0);
-    return (long)(((uint64_t)hi << 32) | lo);
-}
-#endif
-
-// deterministic reduction of an n-block (n <= 18) over the group; result in v on every thread
-AI void block_sum(const Ctx& x, double* v, int n) {
-    const Grp& g = x.g;
-#if defined(__HIP_DEVICE_COMPILE__)
-    UNR for (int e = 0; e < 18; e++) if (e < n) v[e] = wsum(v[e]);
-    const int wave = g.tid >> 6, nw = (g.n + 63) >> 6;
-    if ((g.tid & 63) == 0)
-        UNR for (int e = 0; e < 18; e++) if (e < n) x.red[wave * 18 + e] = v[e];
-    g.sync();
-    UNR for (int e = 0; e < 18; e++) {
-        if (e < n) {
-            double s = x.red[e];
-            for (int w = 1; w < nw; w++) s = s + x.red[w * 18 + e];
-            v[e] = s;
-        }
-    }
-    g.sync();
-#else
-    for (int e = 0; e < n; e++) x.red[g.tid * 18 + e] = v[e];
-    g.sync();
-    for (int s = g.n / 2; s > 0; s >>= 1) {
-        if (g.tid < s)
-            for (int e = 0; e < n; e++) x.red[g.tid * 18 + e] = x.red[g.tid * 18 + e] + x.red[(g.tid + s) * 18 + e];
-        g.sync();
-    }
-    for (int e = 0; e < n; e++) v[e] = x.red[e];
-    g.sync();
-#endif
-}
-
 // exclusive scan of kp[0..N) in place (contiguous chunk per thread); returns total
 AI int block_scan(const Ctx& x, int* kp, int N) {
     const Grp& g = x.g;
@@ -254,38 +337,11 @@ AI int block_scan(const Ctx& x, int* kp, int N) {
     const int lo = g.tid * chunk, hi = (lo + chunk < N) ? lo + chunk : N;
     int s = 0;
     for (int i = lo; i < hi; i++) s += kp[i];
-#if defined(__HIP_DEVICE_COMPILE__)
-    const int lane = g.tid & 63, wave = g.tid >> 6, nw = (g.n + 63) >> 6;
-    const int inc = wave_incl_scan(s);
-    if (lane == 63) x.iscan[wave] = inc;
-    g.sync();
-    int base = 0, total = 0;
-    for (int w = 0; w < nw; w++) {
-        const int t = x.iscan[w];
-        if (w < wave) base += t;
-        total += t;
-    }
-    int run = base + inc - s;
+    int total;
+    int run = group_scan(g, x.iscan, s, total);
     for (int i = lo; i < hi; i++) { const int v = kp[i]; kp[i] = run; run += v; }
     g.sync();
     return total;
-#else
-    int* a = x.iscan;
-    int* b = x.iscan + g.n;
-    a[g.tid] = s;
-    g.sync();
-    for (int off = 1; off < g.n; off <<= 1) {
-        b[g.tid] = a[g.tid] + (g.tid >= off ? a[g.tid - off] : 0);
-        g.sync();
-        int* t = a; a = b; b = t;
-    }
-    const int incl = a[g.tid];
-    const int total = a[g.n - 1];
-    int run = incl - s;
-    for (int i = lo; i < hi; i++) { const int v = kp[i]; kp[i] = run; run += v; }
-    g.sync();
-    return total;
-#endif
 }
 
 AI bool key_less(uint64_t h1, uint32_t i1, uint64_t h2, uint32_t i2) { return h1 < h2 || (h1 == h2 && i1 < i2); }
@@ -373,25 +429,24 @@ AI void lower_bounds(const uint64_t* h, int cnt, const uint64_t* off, const uint
 
 // term lists of an operator: kind 0 = product (PZsparse.cu:864-994: T1 a_i x B.c, T2 A.c x b_j,
 // T3 a_i x b_j with hash a_i + b_j), kind 1 = concatenation of up to 3 sources, each a full block
-// (place = -1) or a 1x1 source placed at component `place` (operator+/-, stack, addOneDimPZ)
-struct Terms {
+// (place = -1) or a 1x1 source placed at component `place` (operator+/-, stack, addOneDimPZ).
+// TermIndex is the half both engines share: the operator's shape table (filled by reach.h op_shape)
+// and the term index arithmetic over the sources' hash runs. SRC is the engine's operand view (Src
+// here, lane_engine.h LSrc): cnt, n and hash(k) are what this half reads. What a term's value is,
+// and how a term is ranked, each engine adds itself.
+template <class SRC>
+struct TermIndex {
     int kind, ns;
-    Src S[3];
+    SRC S[3];
     int places;        // 4 bits per source: component + 1 (0: full block)
     int negs;          // bit per source: negate on read
-    const double* Ac;  // product: operand centres (LDS handles)
-    const double* Bc;
-    int AR, AC, BC;
+    int AR, AC, BC;    // product: operand shapes
     int nout;          // elements of the output block
     uint32_t nbm;      // product: ceil(2^32 / |S1|), so T3 index q splits as q / nb = mulhi(q, nbm)
     // T3 index q -> (row i, column j) without an integer division: exact for q, nb < 2^16
     AI void split(int q, int& i, int& j) const {
         const int nb = S[1].cnt;
-#if defined(__HIP_DEVICE_COMPILE__)
-        i = nb == 1 ? q : (int)__umulhi((uint32_t)q, nbm);
-#else
-        i = nb == 1 ? q : (int)(((uint64_t)(uint32_t)q * nbm) >> 32);
-#endif
+        i = nb == 1 ? q : (int)mulhi_u32((uint32_t)q, nbm);
         j = q - i * nb;
     }
     AI void which(int p, int& s, int& k) const {
@@ -418,6 +473,11 @@ struct Terms {
         else if (bs) { UNR for (int e = 0; e < 9; e++) out[e] = a[e] * b[0]; }
         else matmul(a, AR, AC, b, BC, out);
     }
+};
+
+struct Terms : TermIndex<Src> {
+    const double* Ac;  // product: operand centres (LDS handles)
+    const double* Bc;
     AI void coef(int p, double* out) const {
         if (kind == 0) {
             const int na = S[0].cnt, nb = S[1].cnt;
@@ -574,48 +634,14 @@ AI void stage_sources(Ctx& x, Terms& T) {
     }
 }
 
-// shared counters of the workgroup, updated by one lane per op — or by several lanes at once in
-// a lane-parallel group of thread-0 ops (reach.h), hence LDS atomics on the device
-AI void err_or(const Ctx& x, int bits) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    atomicOr(x.err, bits);
-#else
-    *x.err |= bits;
-#endif
-}
-AI void bytes_add(const Ctx& x, double b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    atomicAdd(&x.A->bytes, b);
-#else
-    x.A->bytes += b;
-#endif
-}
-AI void int_add(int* p, int v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    atomicAdd(p, v);
-#else
-    *p += v;
-#endif
-}
-AI void int_min(int* p, int v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    atomicMin(p, v);
-#else
-    *p = v < *p ? v : *p;
-#endif
-}
+// monomial storage for K monomials of `stride` doubles (thread 0 — or several lanes at once in a
+// lane-parallel group of thread-0 ops, reach.h: hence bump() and err_or(), LDS atomics on the device)
 AI void arena_alloc_t0(Ctx& x, PZH& h, int K, int stride) {
     h.stride = stride;
-#if defined(__HIP_DEVICE_COMPILE__)
-    const long h0 = (long)atomicAdd((unsigned long long*)&x.A->hused, (unsigned long long)K);
-    const long c0 = (long)atomicAdd((unsigned long long*)&x.A->cused, (unsigned long long)K * stride);
-#else
-    const long h0 = x.A->hused, c0 = x.A->cused;
-    x.A->hused += K;
-    x.A->cused += (long)K * stride;
-#endif
+    const long h0 = bump(&x.A->hused, K);
+    const long c0 = bump(&x.A->cused, (long)K * stride);
     if (h0 + K > x.A->hcap || c0 + (long)K * stride > x.A->ccap) {
-        err_or(x, ERR_ARENA);
+        err_or(x.err, ERR_ARENA);
         h.cnt = 0; h.hoff = 0; h.coff = 0;
     } else {
         h.hoff = h0;
@@ -762,121 +788,6 @@ struct PolCrossPPT {
 };
 using PolCrossPP = PolCrossPPT<>;
 
-// deterministic reduction of the masked slots of an NR-block over the group
-AI void block_sum_mask(const Ctx& x, double* v, int nr, unsigned mask) {
-    const Grp& g = x.g;
-#if defined(__HIP_DEVICE_COMPILE__)
-    UNR for (int e = 0; e < 18; e++) if (e < nr && ((mask >> e) & 1)) v[e] = wsum(v[e]);
-    const int wave = g.tid >> 6, nw = (g.n + 63) >> 6;
-    if ((g.tid & 63) == 0)
-        UNR for (int e = 0; e < 18; e++) if (e < nr && ((mask >> e) & 1)) x.red[wave * 18 + e] = v[e];
-    g.sync();
-    UNR for (int e = 0; e < 18; e++) {
-        if (e < nr && ((mask >> e) & 1)) {
-            double s = x.red[e];
-            for (int w = 1; w < nw; w++) s = s + x.red[w * 18 + e];
-            v[e] = s;
-        }
-    }
-    g.sync();
-#else
-    block_sum(x, v, nr);
-#endif
-}
-
-#if defined(__HIP_DEVICE_COMPILE__)
-// ---- N <= 64: wave 0 alone, keys and term values in registers ---------------------------------
-#define SPHASE(k)                                                                                  \
-    if (x.phase && lane == 0) {                                                                    \
-        const long long c_ = clock64();                                                            \
-        x.phase[k] += (unsigned long long)(c_ - ph_t);                                             \
-        ph_t = c_;                                                                                 \
-    }
-template <class Pol>
-__device__ inline __attribute__((always_inline)) void simplify_small(Ctx& x, int o, const Terms& T, const Pol& pol, int N) {
-    constexpr int NV = Pol::NV, n = Pol::NO;
-    const int lane = x.g.tid & 63;
-    long long ph_t = x.phase ? clock64() : 0;
-    uint64_t h = ~(uint64_t)0;
-    double c[NV];
-    if (lane < N) {
-        h = T.hash(lane);
-        pol.term(T, lane, c);
-    } else {
-        UNR for (int e = 0; e < NV; e++) c[e] = 0.0;
-    }
-    if (x.phase) { UNR for (int e = 0; e < NV; e++) h ^= (c[e] != c[e]) ? 1 : 0; }  // force the loads before the stamp
-    SPHASE(8)
-    uint32_t id = (uint32_t)lane;
-    int P = 1;
-    while (P < N) P <<= 1;
-    UNR for (int lk = 1; lk <= 6; lk++) {
-        const int k = 1 << lk;
-        if (k > P) break;
-        UNR for (int lj = lk - 1; lj >= 0; lj--) {
-            const int j = 1 << lj;
-            const uint64_t oh = xor_u64(h, j);
-            const uint32_t oi = xor_u32(id, j);
-            const bool asc = (lane & k) == 0, lower = (lane & j) == 0;
-            const bool other_less = key_less(oh, oi, h, id);
-            if ((lower == asc) ? other_less : !other_less) { h = oh; id = oi; }
-        }
-    }
-    SPHASE(9)
-    // term values follow their keys
-    UNR for (int e = 0; e < NV; e++) c[e] = __shfl(c[e], (int)id, 64);
-    const uint64_t prev = prev_u64(h);
-    const bool head = lane < N && (lane == 0 || h != prev);
-    const unsigned long long hm = __ballot(head);
-    const unsigned long long above = lane < 63 ? (hm & ~((2ull << lane) - 1)) : 0ull;
-    const int next = above ? __builtin_ctzll(above) : N;
-    const int size = head ? next - lane : 0;
-    const int maxg = wave_max(size);
-    double acc[NV], t[NV];
-    UNR for (int e = 0; e < NV; e++) { acc[e] = c[e]; t[e] = c[e]; }
-    for (int st = 1; st < maxg; st++) {
-        // t <- value of lane + 1: after st shifts lane q holds the term at q + st
-        UNR for (int e = 0; e < NV; e++) t[e] = next_f64(t[e]);
-        if (head && st < size) UNR for (int e = 0; e < NV; e++) acc[e] = acc[e] + t[e];
-    }
-    SPHASE(10)
-    double red[Pol::NR], out[n];
-    UNR for (int e = 0; e < Pol::NR; e++) red[e] = 0.0;
-    UNR for (int e = 0; e < n; e++) out[e] = 0.0;
-    const bool keep = head && pol.group(acc, out, red);
-    if (!head) UNR for (int e = 0; e < Pol::NR; e++) red[e] = 0.0;
-    const unsigned long long km = __ballot(keep);
-    const int K = __popcll(km);
-    const int pos = __popcll(km & ((1ull << lane) - 1));
-    long hoff = 0, coff = 0;
-    int ok = 0;
-    if (lane == 0) {
-        PZH& oh = x.H[o];
-        arena_alloc_t0(x, oh, K, n);
-        hoff = oh.hoff;
-        coff = oh.coff;
-        ok = oh.cnt == K;
-        x.A->bytes += T.in_bytes() + (double)K * (8.0 + 8.0 * n);
-    }
-    hoff = bcast0(hoff);
-    coff = bcast0(coff);
-    ok = __builtin_amdgcn_readlane(ok, 0);
-    if (ok && keep) {
-        x.ah[hoff + pos] = h;
-        double* dst = x.ac + coff + (long)pos * n;
-        UNR for (int e = 0; e < n; e++) dst[e] = out[e];
-    }
-    SPHASE(11)
-    const unsigned mask = pol.mask();
-    UNR for (int e = 0; e < Pol::NR; e++) if ((mask >> e) & 1) red[e] = wsum(red[e]);
-    if (lane == 0) pol.finish(x, o, red);
-    SPHASE(12)
-}
-
-#endif
-
-
-
 // ---- N > 64: whole group. Key order first (independent of the policy), then the group passes.
 // Keys live in LDS up to its capacity, else in the workgroup's global buffers. Returns false (and
 // flags the error) when even those are too small. Sources staged, caller's barrier done.
@@ -909,24 +820,12 @@ AI bool order_keys(Ctx& x, const Terms& T, int N, KeyBufs& K) {
     return true;
 }
 
-#if defined(__HIP_DEVICE_COMPILE__)
-#define PHASE(k)                                                                                   \
-    if (x.phase && g.tid == 0) {                                                                   \
-        const long long c_ = clock64();                                                            \
-        x.phase[k] += (unsigned long long)(c_ - ph_t);                                             \
-        ph_t = c_;                                                                                 \
-    }
-#else
-#define PHASE(k)
-#endif
-
 // group sums in term order, keep flags and pruned amounts, compaction, output (keys ordered)
 template <class Pol>
 AI void simplify_groups(Ctx& x, int o, const Terms& T, const Pol& pol, int N, const KeyBufs& K) {
     const Grp& g = x.g;
-#if defined(__HIP_DEVICE_COMPILE__)
-    long long ph_t = x.phase ? clock64() : 0;
-#endif
+    Probe pr{x.phase, g.tid == 0};
+    pr.stamp_all();
     constexpr int NV = Pol::NV, n = Pol::NO;
     const uint64_t* kh = K.kh;
     const uint32_t* ki = K.ki;
@@ -952,14 +851,14 @@ AI void simplify_groups(Ctx& x, int o, const Terms& T, const Pol& pol, int N, co
         kp[q] = keep;
     }
     g.sync();
-    PHASE(2)
+    pr.lap(2);
     const int K_ = block_scan(x, kp, N);
     if (g.tid == 0) {
         arena_alloc_t0(x, x.H[o], K_, n);
         x.A->bytes += T.in_bytes() + (double)K_ * (8.0 + 8.0 * n);
     }
     g.sync();
-    PHASE(3)
+    pr.lap(3);
     // pass 2, same thread and q order as pass 1: the group decision again from the parked sums,
     // its pruned / kept amounts into the reduction slots (the order pass 1 would have used), and
     // the kept rows written at their compacted position
@@ -980,9 +879,9 @@ AI void simplify_groups(Ctx& x, int o, const Terms& T, const Pol& pol, int N, co
             UNR for (int e = 0; e < n; e++) dst[e] = out[e];
         }
     }
-    PHASE(4)
-    block_sum_mask(x, red, Pol::NR, pol.mask());
-    PHASE(5)
+    pr.lap(4);
+    group_sum(g, x.red, red, Pol::NR, pol.mask());
+    pr.lap(5);
     if (g.tid == 0) pol.finish(x, o, red);
 }
 
@@ -1047,6 +946,141 @@ AI void cross_const_finish(const Ctx& x, PZH& h, const PZH& A, const CrossC& C, 
     }
 }
 
+// ---- N <= 64: wave 0 alone, keys and term values in registers ---------------------------------
+// The one region outside the seam that depends on the pass: these two bodies are made of wave
+// intrinsics (DPP moves, ballots, lane reads) that have no one-thread host form. Their callers take
+// them only when !emulated(), so the host pass gets empty stand-ins that are never run.
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ inline __attribute__((always_inline)) long bcast0(long v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 0);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), 0);
+    return (long)(((uint64_t)hi << 32) | lo);
+}
+// simplify of N <= 64 terms; called by the threads of wave 0
+template <class Pol>
+__device__ inline __attribute__((always_inline)) void simplify_small(Ctx& x, int o, const Terms& T, const Pol& pol, int N) {
+    constexpr int NV = Pol::NV, n = Pol::NO;
+    const int lane = x.g.tid & 63;
+    Probe pr{x.phase, lane == 0};
+    pr.stamp_all();
+    uint64_t h = ~(uint64_t)0;
+    double c[NV];
+    if (lane < N) {
+        h = T.hash(lane);
+        pol.term(T, lane, c);
+    } else {
+        UNR for (int e = 0; e < NV; e++) c[e] = 0.0;
+    }
+    if (x.phase) { UNR for (int e = 0; e < NV; e++) h ^= (c[e] != c[e]) ? 1 : 0; }  // force the loads before the stamp
+    pr.lap(8);
+    uint32_t id = (uint32_t)lane;
+    int P = 1;
+    while (P < N) P <<= 1;
+    UNR for (int lk = 1; lk <= 6; lk++) {
+        const int k = 1 << lk;
+        if (k > P) break;
+        UNR for (int lj = lk - 1; lj >= 0; lj--) {
+            const int j = 1 << lj;
+            const uint64_t oh = xor_u64(h, j);
+            const uint32_t oi = xor_u32(id, j);
+            const bool asc = (lane & k) == 0, lower = (lane & j) == 0;
+            const bool other_less = key_less(oh, oi, h, id);
+            if ((lower == asc) ? other_less : !other_less) { h = oh; id = oi; }
+        }
+    }
+    pr.lap(9);
+    // term values follow their keys
+    UNR for (int e = 0; e < NV; e++) c[e] = __shfl(c[e], (int)id, 64);
+    const uint64_t prev = prev_u64(h);
+    const bool head = lane < N && (lane == 0 || h != prev);
+    const unsigned long long hm = __ballot(head);
+    const unsigned long long above = lane < 63 ? (hm & ~((2ull << lane) - 1)) : 0ull;
+    const int next = above ? __builtin_ctzll(above) : N;
+    const int size = head ? next - lane : 0;
+    const int maxg = wave_max(size);
+    double acc[NV], t[NV];
+    UNR for (int e = 0; e < NV; e++) { acc[e] = c[e]; t[e] = c[e]; }
+    for (int st = 1; st < maxg; st++) {
+        // t <- value of lane + 1: after st shifts lane q holds the term at q + st
+        UNR for (int e = 0; e < NV; e++) t[e] = next_f64(t[e]);
+        if (head && st < size) UNR for (int e = 0; e < NV; e++) acc[e] = acc[e] + t[e];
+    }
+    pr.lap(10);
+    double red[Pol::NR], out[n];
+    UNR for (int e = 0; e < Pol::NR; e++) red[e] = 0.0;
+    UNR for (int e = 0; e < n; e++) out[e] = 0.0;
+    const bool keep = head && pol.group(acc, out, red);
+    if (!head) UNR for (int e = 0; e < Pol::NR; e++) red[e] = 0.0;
+    const unsigned long long km = __ballot(keep);
+    const int K = __popcll(km);
+    const int pos = __popcll(km & ((1ull << lane) - 1));
+    long hoff = 0, coff = 0;
+    int ok = 0;
+    if (lane == 0) {
+        PZH& oh = x.H[o];
+        arena_alloc_t0(x, oh, K, n);
+        hoff = oh.hoff;
+        coff = oh.coff;
+        ok = oh.cnt == K;
+        x.A->bytes += T.in_bytes() + (double)K * (8.0 + 8.0 * n);
+    }
+    hoff = bcast0(hoff);
+    coff = bcast0(coff);
+    ok = __builtin_amdgcn_readlane(ok, 0);
+    if (ok && keep) {
+        x.ah[hoff + pos] = h;
+        double* dst = x.ac + coff + (long)pos * n;
+        UNR for (int e = 0; e < n; e++) dst[e] = out[e];
+    }
+    pr.lap(11);
+    const unsigned mask = pol.mask();
+    UNR for (int e = 0; e < Pol::NR; e++) if ((mask >> e) & 1) red[e] = wave_sum(red[e]);
+    if (lane == 0) pol.finish(x, o, red);
+    pr.lap(12);
+}
+// the PZ x constant cross of N <= 64 monomials (cross_const below); called by every thread, wave 0 works
+template <class D>
+__device__ inline __attribute__((always_inline)) void cross_const_small(Ctx& x, int o, const PZH& A, const Src& S, const CrossC& C, const D& thr, int N) {
+    if (x.g.tid >= 64) return;
+    const int lane = x.g.tid;
+    double red[9], out[9], m[9];
+    UNR for (int e = 0; e < 9; e++) { red[e] = 0.0; out[e] = 0.0; }
+    bool keep = false;
+    if (lane < N) {
+        S.read(lane, false, m);
+        keep = cross_const_mono(C, m, thr, out, red);
+    }
+    const unsigned long long km = __ballot(keep);
+    const int K = __popcll(km);
+    const int pos = __popcll(km & ((1ull << lane) - 1));
+    long hoff = 0, coff = 0;
+    int ok = 0;
+    if (lane == 0) {
+        PZH& oh = x.H[o];
+        arena_alloc_t0(x, oh, K, 3);
+        hoff = oh.hoff;
+        coff = oh.coff;
+        ok = oh.cnt == K;
+        x.A->bytes += (double)N * 32.0 + (double)K * 32.0;
+    }
+    hoff = bcast0(hoff);
+    coff = bcast0(coff);
+    ok = __builtin_amdgcn_readlane(ok, 0);
+    if (ok && keep) {
+        x.ah[hoff + pos] = S.h[lane];
+        double* dst = x.ac + coff + (long)pos * 3;
+        UNR for (int e = 0; e < 3; e++) dst[e] = out[e];
+    }
+    UNR for (int e = 0; e < 9; e++) red[e] = wave_sum(red[e]);
+    if (lane == 0) cross_const_finish(x, x.H[o], A, C, red);
+}
+#else
+template <class Pol>
+inline void simplify_small(Ctx& x, int o, const Terms& T, const Pol& pol, int N) { assert(false); }
+template <class D>
+inline void cross_const_small(Ctx& x, int o, const PZH& A, const Src& S, const CrossC& C, const D& thr, int N) { assert(false); }
+#endif
+
 // the whole op; the header of o (3x1) is initialised by the caller's thread 0; ends without barrier
 template <bool SQ>
 AI void cross_const(Ctx& x, int o, int a, const CrossC& C) {
@@ -1055,43 +1089,12 @@ AI void cross_const(Ctx& x, int o, int a, const CrossC& C) {
     const PZH& A = x.H[a];
     const int N = A.cnt;
     const Src S = src_of(x, A);
-    double red[9], out[9], m[9];
-    UNR for (int e = 0; e < 9; e++) { red[e] = 0.0; out[e] = 0.0; }
-#if defined(__HIP_DEVICE_COMPILE__)
-    if (N <= 64) {
-        if (g.tid >= 64) return;
-        const int lane = g.tid;
-        bool keep = false;
-        if (lane < N) {
-            S.read(lane, false, m);
-            keep = cross_const_mono(C, m, thr, out, red);
-        }
-        const unsigned long long km = __ballot(keep);
-        const int K = __popcll(km);
-        const int pos = __popcll(km & ((1ull << lane) - 1));
-        long hoff = 0, coff = 0;
-        int ok = 0;
-        if (lane == 0) {
-            PZH& oh = x.H[o];
-            arena_alloc_t0(x, oh, K, 3);
-            hoff = oh.hoff;
-            coff = oh.coff;
-            ok = oh.cnt == K;
-            x.A->bytes += (double)N * 32.0 + (double)K * 32.0;
-        }
-        hoff = bcast0(hoff);
-        coff = bcast0(coff);
-        ok = __builtin_amdgcn_readlane(ok, 0);
-        if (ok && keep) {
-            x.ah[hoff + pos] = S.h[lane];
-            double* dst = x.ac + coff + (long)pos * 3;
-            UNR for (int e = 0; e < 3; e++) dst[e] = out[e];
-        }
-        UNR for (int e = 0; e < 9; e++) red[e] = wsum(red[e]);
-        if (lane == 0) cross_const_finish(x, x.H[o], A, C, red);
+    if (!emulated() && N <= 64) {
+        cross_const_small(x, o, A, S, C, thr, N);
         return;
     }
-#endif
+    double red[9], out[9], m[9];
+    UNR for (int e = 0; e < 9; e++) { red[e] = 0.0; out[e] = 0.0; }
     int* kp = N <= x.cap_lds ? x.kp : x.gkp;
     if (N > x.cap_lds && N > x.cap_glb) {
         if (g.tid == 0) { *x.err |= ERR_SORTCAP; x.H[o].cnt = 0; }
@@ -1123,7 +1126,7 @@ AI void cross_const(Ctx& x, int o, int a, const CrossC& C) {
             UNR for (int e = 0; e < 3; e++) dst[e] = out[e];
         }
     }
-    block_sum_mask(x, red, 9, 0x1ff);
+    group_sum(g, x.red, red, 9, 0x1ff);
     if (g.tid == 0) cross_const_finish(x, x.H[o], A, C, red);
 }
 
@@ -1138,86 +1141,14 @@ AI void hdr_init(const Ctx& x, PZH& h, int R, int C) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// operators: term list (all threads, uniform) and output header (thread 0: the operator's own
-// centre / independent formula). Operands are never aliased by the output (the program builder
-// allocates SSA-style slots).
+// operators' output headers (the operator's own centre / independent formula; the term lists are
+// built in reach.h). Operands are never aliased by the output (the program builder allocates
+// SSA-style slots).
 
-// a + b (sign = +1) or a - b (sign = -1)  (PZsparse.cu:743-764, 813-834)
-AI void terms_add(const Ctx& x, int a, int b, int sign, Terms& T) {
-    const PZH& A = x.H[a];
-    const PZH& B = x.H[b];
-    T.kind = 1; T.ns = 2;
-    T.S[0] = src_of(x, A); T.S[1] = src_of(x, B);
-    T.places = 0;
-    T.negs = sign < 0 ? 2 : 0;
-    T.nout = nel(A);
-}
-AI void header_add(Ctx& x, int o, int a, int b, int sign) {
-    const PZH& A = x.H[a];
-    const PZH& B = x.H[b];
-    PZH& h = x.H[o];
-    hdr_init(x, h, A.R, A.C);
-    const int n = nel(A);
-    UNR for (int e = 0; e < 9; e++) {
-        if (e < n) {
-            cen(x, h)[e] = sign > 0 ? cen(x, A)[e] + cen(x, B)[e] : cen(x, A)[e] - cen(x, B)[e];
-            ind(x, h, 0)[e] = ind(x, A, 0)[e] + ind(x, B, 0)[e];
-            ind(x, h, 1)[e] = ind(x, A, 1)[e] + ind(x, B, 1)[e];
-        }
-    }
-}
 
-// a * b  (PZsparse.cu:864-994)
-AI void terms_mul(const Ctx& x, int a, int b, Terms& T) {
-    const PZH& A = x.H[a];
-    const PZH& B = x.H[b];
-    T.kind = 0; T.ns = 2;
-    T.places = 0; T.negs = 0;
-    T.S[0] = src_of(x, A); T.S[1] = src_of(x, B);
-    T.Ac = cen(x, A); T.Bc = cen(x, B);
-    T.AR = A.R; T.AC = A.C; T.BC = B.C;
-    T.nbm = B.cnt > 1 ? 0xFFFFFFFFu / (uint32_t)B.cnt + 1u : 0u;
-    const bool as = A.R == 1 && A.C == 1, bs = B.R == 1 && B.C == 1;
-    T.nout = as ? nel(B) : (bs ? nel(A) : A.R * B.C);
-}
-// centre, then the dual independent part
-//   ind = A.ind B.ind + (|A.c| + sum|a_i|) B.ind + A.ind (|B.c| + sum|b_j|)
-AI void header_mul(Ctx& x, int o, int a, int b, const Terms& T) {
-    const PZH& A = x.H[a];
-    const PZH& B = x.H[b];
-    const bool as = A.R == 1 && A.C == 1, bs = B.R == 1 && B.C == 1;
-    PZH& h = x.H[o];
-    hdr_init(x, h, as ? B.R : A.R, as ? B.C : (bs ? A.C : B.C));
-    const int na = nel(A), nb = nel(B), nr = nel(h);
-    double cv[9], ac[9], bc[9], r2[9], r3[9];
-    UNR for (int e = 0; e < 9; e++) {
-        ac[e] = cen(x, A)[e];
-        bc[e] = cen(x, B)[e];
-        r2[e] = e < na ? fabs(cen(x, A)[e]) + abs_(x, A)[e] : 0.0;
-        r3[e] = e < nb ? fabs(cen(x, B)[e]) + abs_(x, B)[e] : 0.0;
-    }
-    T.prod(ac, bc, cv);
-    UNR for (int e = 0; e < 9; e++) if (e < nr) cen(x, h)[e] = cv[e];
-    UNR for (int v = 0; v < 2; v++) {
-        double ai[9], bi[9], t2[9], t3[9], ii[9];
-        UNR for (int e = 0; e < 9; e++) { ai[e] = ind(x, A, v)[e]; bi[e] = ind(x, B, v)[e]; }
-        if (as) {
-            UNR for (int e = 0; e < 9; e++) { t2[e] = r2[0] * bi[e]; t3[e] = ai[0] * r3[e]; ii[e] = ai[0] * bi[e]; }
-        } else if (bs) {
-            UNR for (int e = 0; e < 9; e++) { t2[e] = r2[e] * bi[0]; t3[e] = ai[e] * r3[0]; ii[e] = ai[e] * bi[0]; }
-        } else {
-            matmul(r2, A.R, A.C, bi, B.C, t2);
-            matmul(ai, A.R, A.C, r3, B.C, t3);
-            matmul(ai, A.R, A.C, bi, B.C, ii);
-        }
-        UNR for (int e = 0; e < 9; e++) if (e < nr) ind(x, h, v)[e] = ii[e] + (t2[e] + t3[e]);
-    }
-    if (as && !bs && B.R != 1 && A.cnt > 0 && B.cnt > 0) *x.err |= ERR_HANDLES;  // Eigen assert in the reference
-    if (!as && !bs && !(A.R == 3 && A.C == 3 && B.R == 3)) *x.err |= ERR_HANDLES;  // block shape outside matmul()
-}
-
-// ---- element-parallel headers: lane e < R*C of wave 0 computes output element e (the same
-// arithmetic, element for element, as the serial formulas above); lane 0 also writes the meta.
+// ---- element-parallel headers: lane e < R*C of wave 0 computes output element e of the operator's
+// own centre / independent formula (the emulation calls them for e = 0..8 in turn); lane 0 also
+// writes the meta.
 AI void set_meta(PZH& h, int R, int C) {
     h.R = R; h.C = C; h.cnt = 0; h.stride = R * C; h.hoff = 0; h.coff = 0;
     h.comp = -1; h.scaled = 0; h.scale = 1.0;
@@ -1321,63 +1252,6 @@ AI void header_add_one_dim_par(Ctx& x, int o, int self, int a, int pos, int e) {
     ph[n + e] = at ? pa[n + e] + pb[1] : pa[n + e];
     ph[2 * n + e] = at ? pa[2 * n + e] + pb[2] : pa[2 * n + e];
     ph[3 * n + e] = 0.0;
-}
-
-// fused PZ x PZ cross: the term list of the six 1x1 products is the product term list of the two
-// full 3x1 operands (hashes only; PolCrossPP evaluates the coefficients)
-AI void terms_cross_pp(const Ctx& x, int a, int b, Terms& T) {
-    const PZH& A = x.H[a];
-    const PZH& B = x.H[b];
-    T.kind = 0; T.ns = 2;
-    T.places = 0; T.negs = 0;
-    T.S[0] = src_of(x, A); T.S[1] = src_of(x, B);
-    T.Ac = cen(x, A); T.Bc = cen(x, B);
-    T.AR = 3; T.AC = 1; T.BC = 1;
-    T.nbm = B.cnt > 1 ? 0xFFFFFFFFu / (uint32_t)B.cnt + 1u : 0u;
-    T.nout = 3;
-}
-
-// stack three 1x1 PZs into a 3x1 (PZsparse.cu:1087-1116)
-AI void terms_stack3(const Ctx& x, int a0, int a1, int a2, Terms& T) {
-    T.kind = 1; T.ns = 3;
-    T.S[0] = src_of(x, x.H[a0]); T.S[1] = src_of(x, x.H[a1]); T.S[2] = src_of(x, x.H[a2]);
-    T.places = 1 | (2 << 4) | (3 << 8);
-    T.negs = 0;
-    T.nout = 3;
-}
-AI void header_stack3(Ctx& x, int o, int a0, int a1, int a2) {
-    const PZH& S0 = x.H[a0];
-    const PZH& S1 = x.H[a1];
-    const PZH& S2 = x.H[a2];
-    PZH& h = x.H[o];
-    hdr_init(x, h, 3, 1);
-    cen(x, h)[0] = cen(x, S0)[0]; ind(x, h, 0)[0] = ind(x, S0, 0)[0]; ind(x, h, 1)[0] = ind(x, S0, 1)[0];
-    cen(x, h)[1] = cen(x, S1)[0]; ind(x, h, 0)[1] = ind(x, S1, 0)[0]; ind(x, h, 1)[1] = ind(x, S1, 1)[0];
-    cen(x, h)[2] = cen(x, S2)[0]; ind(x, h, 0)[2] = ind(x, S2, 0)[0]; ind(x, h, 1)[2] = ind(x, S2, 1)[0];
-}
-
-// self(e) += a (1x1)  (PZsparse.cu:1068-1085)
-AI void terms_add_one_dim(const Ctx& x, int self, int a, int e, Terms& T) {
-    const PZH& A = x.H[self];
-    T.kind = 1; T.ns = 2;
-    T.S[0] = src_of(x, A); T.S[1] = src_of(x, x.H[a]);
-    T.places = (e + 1) << 4;
-    T.negs = 0;
-    T.nout = nel(A);
-}
-AI void header_add_one_dim(Ctx& x, int o, int self, int a, int e) {
-    const PZH& A = x.H[self];
-    const PZH& B = x.H[a];
-    PZH& h = x.H[o];
-    hdr_init(x, h, A.R, A.C);
-    const int n = nel(A);
-    UNR for (int q = 0; q < 9; q++) {
-        if (q >= n) break;
-        const bool at = q == e;
-        cen(x, h)[q] = at ? cen(x, A)[q] + cen(x, B)[0] : cen(x, A)[q];
-        ind(x, h, 0)[q] = at ? ind(x, A, 0)[q] + ind(x, B, 0)[0] : ind(x, A, 0)[q];
-        ind(x, h, 1)[q] = at ? ind(x, A, 1)[q] + ind(x, B, 1)[0] : ind(x, A, 1)[q];
-    }
 }
 
 }  // namespace armour

@@ -1,8 +1,12 @@
 // armour-mi355x — one reach-set job = one (world, time interval): JRS -> PZ forward kinematics ->
 // reduce_link_PZ -> PZ RNEA (nominal and interval fused) -> disturbance -> reduce -> torque radius.
 // Follows, op for op, KPR/Trajectory.cu:63-254, KPR/Dynamics.cu:69-181 and
-// KPR/armour_main.cu:118-211; runs as one 256-thread workgroup on gfx950 (reach_kernel in
-// reach_kernel.hip) or sequentially in the CPU emulation used by tests.
+// KPR/armour_main.cu:118-211; runs as one 128- or 256-thread workgroup on gfx950 (reach_kernel in
+// reach_kernel.hip) or sequentially in the CPU emulation used by tests. The two builds share this
+// text: what they do differently (barrier, group primitives, LDS updates, cycle stamps, the
+// emulation's hooks) is the platform seam of pz_engine.h, and nothing here asks which pass it is in.
+// The op's term count, term-list builder and OP_CONST operand choice (op_terms, op_terms_of,
+// const_operand) also serve the bundle engine (lane_engine.h).
 #pragma once
 #include <initializer_list>
 #include <vector>
@@ -287,7 +291,7 @@ T0FN void t0_view(Ctx& x, int o, int a, int e, int scaled, double s) {
     h.comp = e >= 0 ? e : P.comp;
     h.scaled = scaled;
     h.scale = scaled ? s : 1.0;
-    if (P.comp >= 0 || P.scaled) err_or(x, ERR_HANDLES);  // views of views never occur in this program
+    if (P.comp >= 0 || P.scaled) err_or(x.err, ERR_HANDLES);  // views of views never occur in this program
     for (int q = 0; q < n; q++) {
         const int src = e >= 0 ? e : q;
         double c = cen(x, P)[src], i0 = ind(x, P, 0)[src], i1 = ind(x, P, 1)[src], ab = abs_(x, P)[src];
@@ -319,7 +323,7 @@ T0FN void t0_transpose(Ctx& x, int o, int a) {
             for (int i = 0; i < A.R; i++)
                 for (int jj = 0; jj < A.C; jj++) x.ac[h.coff + (long)k * n + jj + i * A.C] = m[i + jj * A.R];
         }
-    bytes_add(x, 2.0 * A.cnt * (8.0 + 8.0 * n));
+    bytes_add(&x.A->bytes, 2.0 * A.cnt * (8.0 + 8.0 * n));
 }
 
 T0FN void t0_make_1d(Ctx& x, int o, const JrsJoint& J, int i, int v) {
@@ -385,12 +389,12 @@ T0FN void t0_emit_link(Ctx& x, const ReachOut& out, long j, int a, int l) {
                 out.link_hash[base * CAP_LM + kk] = (uint16_t)hh;
                 for (int e = 0; e < 3; e++) out.link_coef[(base * CAP_LM + kk) * 3 + e] = c[e];
             } else {
-                err_or(x, ERR_OUTCAP);
+                err_or(x.err, ERR_OUTCAP);
             }
             kk++;
         } else if (hh < HASH_K_LINKS_ONLY && (hh & K_MASK) == 0) {
             if (jg < 3) { for (int e = 0; e < 3; e++) gl[e + 3 * jg] = c[e]; }
-            else err_or(x, ERR_LINKGEN);
+            else err_or(x.err, ERR_LINKGEN);
             jg++;
         } else {
             for (int e = 0; e < 3; e++) rad[e] += fabs(c[e]);
@@ -422,7 +426,7 @@ T0FN void t0_emit_torque(Ctx& x, const ReachOut& out, long j, int a, int i, doub
                 out.tq_hash[base * CAP_UM + kk] = (uint16_t)hh;
                 out.tq_coef[base * CAP_UM + kk] = c;
             } else {
-                err_or(x, ERR_OUTCAP);
+                err_or(x.err, ERR_OUTCAP);
             }
             kk++;
         } else {
@@ -452,24 +456,72 @@ T0FN void t0_torque_radius(const RobotParams& rp, const ReachOut& out, long j, c
     for (int i = 0; i < NF; i++) out.torque_radius[j * NF + i] = tr[i];
 }
 
+// the operand of OP_CONST (kind, i): f(R, C, values, uncertainty of the interval part)
+template <class F>
+AI void const_operand(const RobotParams& rp, int kind, int i, const F& f) {
+    if (kind == CONST_RPY) f(3, 3, rp.rpy[i], 0.0);
+    else if (kind == CONST_TRANS) f(3, 1, &rp.trans[3 * i], 0.0);
+    else if (kind == CONST_MASS) f(1, 1, &rp.mass[i], rp.mass_uncertainty);
+    else f(3, 3, &rp.inertia[9 * i], rp.inertia_uncertainty);
+}
+
 // ---- operator dispatch ----------------------------------------------------------------------
-// number of candidate terms of a simplifying op (uniform: every thread reads the same headers)
-AI int op_terms(const Ctx& x, const Op& op) {
-    const PZH& A = x.H[op.a];
-    const PZH& B = x.H[op.b];
-    if (op.code == OP_CROSS_C) return A.cnt;
+// number of candidate terms of a simplifying op with a term list (MUL / CROSS_PP / ADD / STACK3 /
+// ADD1D), from the handle table H of either engine (uniform: every thread reads the same headers)
+AI int op_terms(const PZH* H, const Op& op) {
+    const PZH& A = H[op.a];
+    const PZH& B = H[op.b];
     if (op.code == OP_MUL || op.code == OP_CROSS_PP) return A.cnt + B.cnt + A.cnt * B.cnt;
-    if (op.code == OP_STACK3) return A.cnt + B.cnt + x.H[op.c].cnt;
+    if (op.code == OP_STACK3) return A.cnt + B.cnt + H[op.c].cnt;
     return A.cnt + B.cnt;
 }
 
-// term list of a simplifying op (all threads, uniform)
-AI void op_terms_of(const Ctx& x, const Op& op, Terms& T) {
+// Term list of a simplifying op: its shape table, from the handle table H of either engine, and its
+// sources S[0 .. ns), each through src, the engine's own src_of (all threads, uniform).
+//   MUL       a * b (PZsparse.cu:864-994)
+//   CROSS_PP  fused PZ x PZ cross: the term list of its six 1x1 products is the product term list of
+//             the two full 3x1 operands (hashes only; PolCrossPP evaluates the coefficients)
+//   ADD       a + b (i = +1) or a - b (i = -1) (PZsparse.cu:743-764, 813-834)
+//   STACK3    three 1x1 PZs a, b, c into a 3x1 (PZsparse.cu:1087-1116)
+//   ADD1D     a(i) += b, b 1x1 (PZsparse.cu:1068-1085)
+template <class SRC, class F>
+AI void op_terms_of(const PZH* H, const Op& op, TermIndex<SRC>& T, const F& src) {
+    const PZH& A = H[op.a];
+    const PZH& B = H[op.b];
+    T.ns = 2;
+    T.places = 0;
+    T.negs = 0;
+    T.S[0] = src(A);
+    T.S[1] = src(B);
     switch (op.code) {
-        case OP_MUL: terms_mul(x, op.a, op.b, T); break;
-        case OP_ADD: terms_add(x, op.a, op.b, op.i, T); break;
-        case OP_STACK3: terms_stack3(x, op.a, op.b, op.c, T); break;
-        default: terms_add_one_dim(x, op.a, op.b, op.i, T); break;
+        case OP_MUL:
+        case OP_CROSS_PP: {
+            T.kind = 0;
+            T.AR = op.code == OP_CROSS_PP ? 3 : A.R;
+            T.AC = op.code == OP_CROSS_PP ? 1 : A.C;
+            T.BC = op.code == OP_CROSS_PP ? 1 : B.C;
+            T.nbm = B.cnt > 1 ? 0xFFFFFFFFu / (uint32_t)B.cnt + 1u : 0u;
+            const bool as = A.R == 1 && A.C == 1, bs = B.R == 1 && B.C == 1;
+            T.nout = op.code == OP_CROSS_PP ? 3 : (as ? nel(B) : (bs ? nel(A) : A.R * B.C));
+            break;
+        }
+        case OP_ADD:
+            T.kind = 1;
+            T.negs = op.i < 0 ? 2 : 0;
+            T.nout = nel(A);
+            break;
+        case OP_STACK3:
+            T.kind = 1;
+            T.ns = 3;
+            T.S[2] = src(H[op.c]);
+            T.places = 1 | (2 << 4) | (3 << 8);
+            T.nout = 3;
+            break;
+        default:  // OP_ADD1D
+            T.kind = 1;
+            T.places = (op.i + 1) << 4;
+            T.nout = nel(A);
+            break;
     }
 }
 // output header, element-parallel: called by lanes e = 0..8 of wave 0
@@ -481,35 +533,50 @@ AI void op_header_par(Ctx& x, const Op& op, int e) {
         default: header_add_one_dim_par(x, op.o, op.a, op.b, op.i, e); break;
     }
 }
-// output header (thread 0)
-AI void op_header(Ctx& x, const Op& op, const Terms& T) {
-    switch (op.code) {
-        case OP_MUL: header_mul(x, op.o, op.a, op.b, T); break;
-        case OP_ADD: header_add(x, op.o, op.a, op.b, op.i); break;
-        case OP_STACK3: header_stack3(x, op.o, op.a, op.b, op.c); break;
-        default: header_add_one_dim(x, op.o, op.a, op.b, op.i); break;
+
+// Thread 0's per-op stamps: the cycles of op pc and its term count into prof[2 * pc], [2 * pc + 1]
+// (ARMOUR_PROFILE_OPS=1), or the cycles between ops into phase slot 13 (=2; the two are exclusive).
+struct OpProbe {
+    unsigned long long* prof;
+    unsigned long long* phase;
+    bool on;
+    long long c0, c_end;
+    AI OpProbe(const Ctx& x, unsigned long long* prof_) : prof(prof_), phase(x.phase), on((prof_ || x.phase) && x.g.tid == 0), c0(0) {
+        c_end = on ? cycles() : 0;
     }
-}
+    AI void op_begin() {
+        c0 = 0;
+        if (on) {
+            c0 = cycles();
+            if (phase) phase[13] += (unsigned long long)(c0 - c_end);  // between ops
+        }
+    }
+    AI void op_end(const Ctx& x, const Op& op, int pc) {
+        if (on) {
+            c_end = cycles();
+            if (prof) {
+                prof_add(&prof[2 * pc], (unsigned long long)(c_end - c0));
+                if ((op.code >= OP_MUL && op.code <= OP_ADD1D) || op.code >= OP_CROSS_C)
+                    prof_add(&prof[2 * pc + 1], (unsigned long long)(op.code == OP_CROSS_C ? x.H[op.a].cnt : op_terms(x.H, op)));
+                c_end = cycles();
+            }
+        }
+    }
+};
 
 // One job (world w, interval t): the interpreter. jrs / scratch live in LDS.
 // dump (diagnostics, may be null): per op, the output handle's [cnt, R*C, centre[0..2], ind0[0],
 // ind1[0], absum[0]] after the op
 constexpr int DUMP_W = 8;
-#if !defined(__HIP_DEVICE_COMPILE__)
-// host emulation statistics (tests/emu): per op [code, class, term kind, |S0|, |S1|, N, runs, output count]
-inline int* g_op_stats = nullptr;
-// host emulation: per op, the output handle's monomial hashes (structure studies)
-inline void (*g_hash_sink)(int pc, const uint64_t* h, int n) = nullptr;
-#endif
 // SQ: keep / prune decisions on squared norms (pz_engine.h SqThr; needs x.thr_valid), else with sqrt
 template <bool SQ = true>
 AI void run_program(Ctx& x, const RobotParams& rp, const Op* prog, int nops, int T, int t, const double* q0,
                     const double* qd0, const double* qdd0, const ReachOut& out, long j, JrsJoint* jrs,
                     double* scratch, unsigned long long* prof, double* dump = nullptr, const JrsJoint* jrs_in = nullptr) {
     const int tid = x.g.tid;
-#if !defined(__HIP_DEVICE_COMPILE__)
-    if (SQ) {
-        // the emulation: the same search with the host's sqrt
+    if (SQ && emulated()) {
+        // the emulation finds the squared threshold itself: the same search with the host's sqrt
+        // (on the device the kernel takes it from RobotParams)
         const SqThr q = sq_threshold(x.thr);
         x.thr_sq = q.s;
         x.thr_valid = q.valid;
@@ -518,13 +585,9 @@ AI void run_program(Ctx& x, const RobotParams& rp, const Op* prog, int nops, int
             return;
         }
     }
-#endif
     double* rdist = scratch;
     double* ured = scratch + NF;
-#if defined(__HIP_DEVICE_COMPILE__)
-    const bool stamp = (prof || x.phase) && tid == 0;
-    long long c_end = stamp ? clock64() : 0;
-#endif
+    OpProbe opr(x, prof);
     // every handle empty at the job's start: a slot named before its first definition (an operand
     // field an op does not use) must not carry what the previous job or kernel left in LDS
     for (int k = x.g.tid; k < MAX_SLOTS; k += x.g.n) {
@@ -536,22 +599,14 @@ AI void run_program(Ctx& x, const RobotParams& rp, const Op* prog, int nops, int
     for (int pc = 0; pc < nops; pc++) {
         const Op op = prog[pc];
         const int par = op.par > 1 ? op.par : 1;  // ops pc .. pc + par - 1 run as one group
-#if defined(__HIP_DEVICE_COMPILE__)
-        long long c0 = 0;
-        if (stamp) {
-            c0 = clock64();
-            if (x.phase) x.phase[13] += (unsigned long long)(c0 - c_end);  // between ops
-        }
-#endif
+        opr.op_begin();
         switch (op.code) {
             case OP_JRS:
                 // on the device the JRS scalars come from jrs_kernel (their interval arithmetic
                 // would otherwise set this kernel's register budget); the emulation computes them
-#if defined(__HIP_DEVICE_COMPILE__)
-                for (int i = tid; i < NF; i += x.g.n) jrs[i] = jrs_in[i];
-#else
-                for (int i = tid; i < NF; i += x.g.n) jrs[i] = jrs_in ? jrs_in[i] : jrs_joint(rp, T, t, i, q0[i], qd0[i], qdd0[i]);
-#endif
+                // when it is given none
+                for (int i = tid; i < NF; i += x.g.n)
+                    jrs[i] = (emulated() && !jrs_in) ? jrs_joint(rp, T, t, i, q0[i], qd0[i], qdd0[i]) : jrs_in[i];
                 break;
             case OP_MAKE1D:
             case OP_MAKEROT:
@@ -570,10 +625,9 @@ AI void run_program(Ctx& x, const RobotParams& rp, const Op* prog, int nops, int
                         case OP_MAKEROT: t0_make_rot(x, m.o, rp, jrs[m.i], m.i); break;
                         case OP_MAKEBOX: t0_make_box(x, m.o, rp, m.i); break;
                         case OP_CONST:
-                            if (m.a == CONST_RPY) t0_const(x, m.o, 3, 3, rp.rpy[m.i], 0.0);
-                            else if (m.a == CONST_TRANS) t0_const(x, m.o, 3, 1, &rp.trans[3 * m.i], 0.0);
-                            else if (m.a == CONST_MASS) t0_const(x, m.o, 1, 1, &rp.mass[m.i], rp.mass_uncertainty);
-                            else t0_const(x, m.o, 3, 3, &rp.inertia[9 * m.i], rp.inertia_uncertainty);
+                            const_operand(rp, m.a, m.i, [&](int R, int C, const double* v, double unc) __attribute__((always_inline)) {
+                                t0_const(x, m.o, R, C, v, unc);
+                            });
                             break;
                         case OP_ZERO:
                             hdr_init(x, x.H[m.o], m.b, m.c);
@@ -598,37 +652,21 @@ AI void run_program(Ctx& x, const RobotParams& rp, const Op* prog, int nops, int
                 // MUL / ADD / STACK3 / ADD1D / CROSS_PP: term list, header, simplify. The ordering of
                 // large term lists is shared; the group passes are instantiated per output class.
                 Terms Tm;
-                int cls;  // 0: 1x1, 1: 3x1, 2: 3x3 plain simplify, 3: fused PZ x PZ cross
-                if (op.code == OP_CROSS_PP) {
-                    terms_cross_pp(x, op.a, op.b, Tm);
-                    cls = 3;
-                } else {
-                    op_terms_of(x, op, Tm);
-                    cls = Tm.nout == 1 ? 0 : (Tm.nout == 3 ? 1 : 2);
-                }
-                const int N = op_terms(x, op);
-#if !defined(__HIP_DEVICE_COMPILE__)
-                if (g_op_stats) {
-                    int* st = g_op_stats + 8 * pc;
-                    st[0] = op.code; st[1] = cls; st[2] = Tm.kind; st[3] = Tm.S[0].cnt;
-                    st[4] = Tm.ns > 1 ? Tm.S[1].cnt : 0; st[5] = N; st[6] = Tm.runs();
-                }
-#endif
-#if defined(__HIP_DEVICE_COMPILE__)
-                long long ph0 = (x.phase && tid == 0) ? clock64() : 0;
-#endif
-#if defined(__HIP_DEVICE_COMPILE__)
-                if (tid < 9) {
-                    if (cls == 3) { if (tid == 0) hdr_init(x, x.H[op.o], 3, 1); }
-                    else op_header_par(x, op, tid);
-                }
-#else
-                if (cls == 3) hdr_init(x, x.H[op.o], 3, 1);
-                else for (int e = 0; e < 9; e++) op_header_par(x, op, e);
-#endif
-#if defined(__HIP_DEVICE_COMPILE__)
-                if (x.phase && tid == 0) x.phase[14] += (unsigned long long)(clock64() - ph0);
-#endif
+                op_terms_of(x.H, op, Tm, [&](const PZH& p) __attribute__((always_inline)) { return src_of(x, p); });
+                Tm.Ac = cen(x, x.H[op.a]);  // a product's operand centres
+                Tm.Bc = cen(x, x.H[op.b]);
+                // 0: 1x1, 1: 3x1, 2: 3x3 plain simplify, 3: fused PZ x PZ cross
+                const int cls = op.code == OP_CROSS_PP ? 3 : (Tm.nout == 1 ? 0 : (Tm.nout == 3 ? 1 : 2));
+                const int N = op_terms(x.H, op);
+                emu_op_stats(pc, op.code, cls, Tm.kind, Tm.S[0].cnt, Tm.ns > 1 ? Tm.S[1].cnt : 0, N, Tm.runs());
+                Probe pr{x.phase, tid == 0};
+                pr.stamp();
+                // output header: element e by lane e of wave 0 (the fused cross only clears it)
+                per_lane(x.g, 9, [&](int e) __attribute__((always_inline)) {
+                    if (cls == 3) { if (e == 0) hdr_init(x, x.H[op.o], 3, 1); }
+                    else op_header_par(x, op, e);
+                });
+                pr.lap(14);
                 const Decide<SQ> dec{x.thr, x.thr_sq};
                 PolBlock<1, Decide<SQ>> p1{dec};
                 PolBlock<3, Decide<SQ>> p3{dec};
@@ -639,8 +677,7 @@ AI void run_program(Ctx& x, const RobotParams& rp, const Op* prog, int nops, int
                 pp.bc = cen(x, x.H[op.b]);
                 pp.a = op.a;
                 pp.b = op.b;
-#if defined(__HIP_DEVICE_COMPILE__)
-                if (N <= 64 && !(x.mode & 1)) {
+                if (!emulated() && N <= 64 && !(x.mode & 1)) {
                     if (tid < 64) {
                         if (cls == 0) simplify_small(x, op.o, Tm, p1, N);
                         else if (cls == 1) simplify_small(x, op.o, Tm, p3, N);
@@ -649,21 +686,16 @@ AI void run_program(Ctx& x, const RobotParams& rp, const Op* prog, int nops, int
                     }
                     break;
                 }
-                long long pt = (x.phase && tid == 0) ? clock64() : 0;
-#endif
+                pr.stamp();
                 stage_sources(x, Tm);
                 x.g.sync();
-#if defined(__HIP_DEVICE_COMPILE__)
-                if (x.phase && tid == 0) { const long long c_ = clock64(); x.phase[6] += (unsigned long long)(c_ - pt); pt = c_; }
-#endif
+                pr.lap(6);
                 KeyBufs K;
                 if (!order_keys(x, Tm, N, K)) {
                     if (tid == 0) { *x.err |= ERR_SORTCAP; x.H[op.o].cnt = 0; }
                     break;
                 }
-#if defined(__HIP_DEVICE_COMPILE__)
-                if (x.phase && tid == 0) x.phase[1] += (unsigned long long)(clock64() - pt);
-#endif
+                pr.lap(1);
                 if (cls == 0) simplify_groups<decltype(p1)>(x, op.o, Tm, p1, N, K);
                 else if (cls == 1) simplify_groups<decltype(p3)>(x, op.o, Tm, p3, N, K);
                 else if (cls == 2) simplify_groups<decltype(p9)>(x, op.o, Tm, p9, N, K);
@@ -672,14 +704,13 @@ AI void run_program(Ctx& x, const RobotParams& rp, const Op* prog, int nops, int
             }
         }
         if (op.sync) x.g.sync();
-#if !defined(__HIP_DEVICE_COMPILE__)
-        if (g_op_stats && op.o >= 0) g_op_stats[8 * pc + 7] = x.H[op.o].cnt;
-        if (g_hash_sink)
+        if (emulated()) {
+            if (op.o >= 0) emu_op_count(pc, x.H[op.o].cnt);
             for (int mi = 0; mi < par; mi++) {
                 const int mo = prog[pc + mi].o;
-                if (mo >= 0) g_hash_sink(pc + mi, x.ah + x.H[mo].hoff, x.H[mo].cnt);
+                if (mo >= 0) emu_hashes(pc + mi, x.ah + x.H[mo].hoff, x.H[mo].cnt);
             }
-#endif
+        }
         if (dump) {
             x.g.sync();
             if (tid == 0)
@@ -693,17 +724,7 @@ AI void run_program(Ctx& x, const RobotParams& rp, const Op* prog, int nops, int
                 }
             x.g.sync();
         }
-#if defined(__HIP_DEVICE_COMPILE__)
-        if (stamp) {
-            c_end = clock64();
-            if (prof) {
-                atomicAdd(&prof[2 * pc], (unsigned long long)(c_end - c0));
-                if ((op.code >= OP_MUL && op.code <= OP_ADD1D) || op.code >= OP_CROSS_C)
-                    atomicAdd(&prof[2 * pc + 1], (unsigned long long)op_terms(x, op));
-                c_end = clock64();
-            }
-        }
-#endif
+        opr.op_end(x, op, pc);
         pc += par - 1;
     }
 }
