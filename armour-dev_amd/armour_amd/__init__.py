@@ -291,6 +291,24 @@ def _ptr(a):
     return a.ctypes.data_as(_dp) if a is not None else None
 
 
+def _iptr(a):
+    """as _ptr, for an int32 array"""
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if a is not None else None
+
+
+def _records(cls, recs):
+    """a list of ctypes records of class `cls` as a dict of arrays over the records: float64 for the
+    floating-point fields, int64 for the integer ones; an array field of length n gives [len(recs), n]"""
+    out = {}
+    for k, ctype in cls._fields_:
+        n = getattr(ctype, "_length_", None)
+        base = ctype._type_ if n is not None else ctype
+        vals = [getattr(r, k)[:] if n is not None else getattr(r, k) for r in recs]
+        a = np.array(vals, dtype=np.float64 if base is ctypes.c_double else np.int64)
+        out[k] = a.reshape(len(recs), n) if n is not None else a
+    return out
+
+
 def candidates_array(x, W):
     """the [W, N, 7] array Planner.eval_candidates hands to the library, from x of that shape or
     [N, 7] (the same candidates for each of the W worlds); ValueError for a wrong shape, a non-finite
@@ -483,9 +501,7 @@ class Planner:
         viol = np.zeros((Wx, N, 3))
         feas = np.zeros((Wx, N), dtype=np.int32)
         best = np.zeros(Wx, dtype=np.int32)
-        ip = ctypes.POINTER(ctypes.c_int)
-        _check(lib().armour_eval_candidates(self.h, N, _ptr(x), _ptr(cost), _ptr(viol), feas.ctypes.data_as(ip),
-                                            best.ctypes.data_as(ip)))
+        _check(lib().armour_eval_candidates(self.h, N, _ptr(x), _ptr(cost), _ptr(viol), _iptr(feas), _iptr(best)))
         return dict(cost=cost, violation=viol, feasible=feas.astype(bool), best=best)
 
     def check_motion(self, traj, t0=0.0, t1=1.0, samples=11):
@@ -498,8 +514,7 @@ class Planner:
             raise ValueError(f"check_motion: traj must have shape [W, 4, {NF}] (W = {self._W}), got {traj.shape}")
         clear = np.zeros(self._W)
         where = np.zeros((self._W, 3), dtype=np.int32)
-        _check(lib().armour_check_motion(self.h, _ptr(traj), float(t0), float(t1), int(samples), _ptr(clear),
-                                         where.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        _check(lib().armour_check_motion(self.h, _ptr(traj), float(t0), float(t1), int(samples), _ptr(clear), _iptr(where)))
         return clear, where
 
     def track(self, traj, scale=None, err0=None, t0=0.0, t1=0.5, steps=250):
@@ -518,19 +533,21 @@ class Planner:
         out["qe"], out["qde"] = self._ultimate_bound()
         return out
 
-    def _track_inputs(self, name, traj, scale, err0, N=None):
-        """the shape checks of the tracking entries: (traj, scale, err0, N, S), contiguous float64"""
-        traj = np.ascontiguousarray(np.asarray(traj, dtype=np.float64))
-        if traj.ndim != 3 or traj.shape[1:] != (4, NF) or traj.shape[0] < 1 or (N is not None and traj.shape[0] != N):
-            raise ValueError(f"{name}: traj must have shape [{'N' if N is None else N}, 4, {NF}], got {traj.shape}")
-        N = traj.shape[0]
+    def _track_inputs(self, name, traj, scale, err0, N=None, n="N"):
+        """the shape checks of the tracking entries: (traj, scale, err0, N, S), contiguous float64. traj None
+        (a tracked episode, which brings no trajectories): N worlds, called `n` in the messages"""
+        if traj is not None:
+            traj = np.ascontiguousarray(np.asarray(traj, dtype=np.float64))
+            if traj.ndim != 3 or traj.shape[1:] != (4, NF) or traj.shape[0] < 1 or (N is not None and traj.shape[0] != N):
+                raise ValueError(f"{name}: traj must have shape [{'N' if N is None else N}, 4, {NF}], got {traj.shape}")
+            N = traj.shape[0]
         S = None
         if scale is not None:
             scale = np.asarray(scale, dtype=np.float64)
             if scale.ndim == 3:
                 scale = np.broadcast_to(scale, (N,) + scale.shape)
             if scale.ndim != 4 or scale.shape[0] != N or scale.shape[1] < 1 or scale.shape[2:] != (2, self.NJ):
-                raise ValueError(f"{name}: scale must have shape [N, S, 2, {self.NJ}] or [S, 2, {self.NJ}] (N = {N}), "
+                raise ValueError(f"{name}: scale must have shape [{n}, S, 2, {self.NJ}] or [S, 2, {self.NJ}] ({n} = {N}), "
                                  f"got {scale.shape}")
             scale = np.ascontiguousarray(scale)
             S = scale.shape[1]
@@ -538,7 +555,7 @@ class Planner:
             err0 = np.ascontiguousarray(np.asarray(err0, dtype=np.float64))
             if err0.ndim != 4 or err0.shape[0] != N or err0.shape[1] < 1 or err0.shape[2:] != (2, NF) or \
                     (S is not None and err0.shape[1] != S):
-                raise ValueError(f"{name}: err0 must have shape [N, S, 2, {NF}] (N = {N}, S = {S}), got {err0.shape}")
+                raise ValueError(f"{name}: err0 must have shape [{n}, S, 2, {NF}] ({n} = {N}, S = {S}), got {err0.shape}")
             S = err0.shape[1]
         return traj, scale, err0, N, 1 if S is None else S
 
@@ -549,7 +566,7 @@ class Planner:
                    max_V=np.zeros((N, S)), max_robust=np.zeros((N, S)), end_state=np.zeros((N, S, 2, NF)))
         out["status"] = np.zeros((N, S), dtype=np.int32)
         o = TrackOutput(*[_ptr(out[k]) for k in ("max_pos_err", "max_vel_err", "max_torque", "max_V", "max_robust",
-                                                  "end_state")], out["status"].ctypes.data_as(ctypes.POINTER(ctypes.c_int)), 0.0)
+                                                  "end_state")], _iptr(out["status"]), 0.0)
         return out, o
 
     def _ultimate_bound(self):
@@ -572,11 +589,10 @@ class Planner:
         and check_ms; +inf and -1 without obstacles."""
         traj, scale, err0, W, S = self._track_inputs("track_motion", traj, scale, err0, N=self._W)
         out, o = self._track_outputs(W, S)
-        ip = ctypes.POINTER(ctypes.c_int)
         out.update(clearance=np.zeros((W, S)), where=np.zeros((W, S, 3), dtype=np.int32), flags=np.zeros((W, S), dtype=np.int32),
                    world_clearance=np.zeros(W), world_where=np.zeros((W, 4), dtype=np.int32))
-        m = TrackMotionOutput(o, _ptr(out["clearance"]), out["where"].ctypes.data_as(ip), out["flags"].ctypes.data_as(ip),
-                              _ptr(out["world_clearance"]), out["world_where"].ctypes.data_as(ip), 0.0)
+        m = TrackMotionOutput(o, _ptr(out["clearance"]), _iptr(out["where"]), _iptr(out["flags"]), _ptr(out["world_clearance"]),
+                              _iptr(out["world_where"]), 0.0)
         _check(lib().armour_track_motion(self.h, _ptr(traj), S, _ptr(scale), _ptr(err0), float(t0), float(t1), int(steps),
                                          int(check_samples), ctypes.byref(m)))
         out["track_ms"], out["check_ms"] = float(m.track.track_ms), float(m.check_ms)
@@ -606,8 +622,7 @@ class Planner:
         res = (Result * max(self._W, 1))()
         tm = Timing()
         ems = np.zeros(2)
-        n = lib().armour_episode_step(self.h, rj.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if rj is not None else None,
-                                      res, ctypes.byref(tm), _ptr(ems))
+        n = lib().armour_episode_step(self.h, _iptr(rj), res, ctypes.byref(tm), _ptr(ems))
         if n < 0:
             _check(n)
         t = self._span(tm.as_dict())
@@ -622,24 +637,8 @@ class Planner:
         episode's start state); S comes from them, or from num_samples when both are None. steps must be a
         multiple of the episode's check_samples - 1. The stops default to the reference's (input and
         ultimate bound, not the joint limits)."""
-        W = self._W
-        S = None
-        if scale is not None:
-            scale = np.asarray(scale, dtype=np.float64)
-            if scale.ndim == 3:
-                scale = np.broadcast_to(scale, (W,) + scale.shape)
-            if scale.ndim != 4 or scale.shape[0] != W or scale.shape[1] < 1 or scale.shape[2:] != (2, self.NJ):
-                raise ValueError(f"episode_track: scale must have shape [W, S, 2, {self.NJ}] or [S, 2, {self.NJ}] (W = {W}), "
-                                 f"got {scale.shape}")
-            scale = np.ascontiguousarray(scale)
-            S = scale.shape[1]
-        if err0 is not None:
-            err0 = np.ascontiguousarray(np.asarray(err0, dtype=np.float64))
-            if err0.ndim != 4 or err0.shape[0] != W or err0.shape[1] < 1 or err0.shape[2:] != (2, NF) or \
-                    (S is not None and err0.shape[1] != S):
-                raise ValueError(f"episode_track: err0 must have shape [W, S, 2, {NF}] (W = {W}, S = {S}), got {err0.shape}")
-            S = err0.shape[1]
-        if S is None:
+        _, scale, err0, _, S = self._track_inputs("episode_track", None, scale, err0, N=self._W, n="W")
+        if scale is None and err0 is None:
             S = 1 if num_samples is None else int(num_samples)
         elif num_samples is not None and int(num_samples) != S:
             raise ValueError(f"episode_track: num_samples = {num_samples} but the arrays carry {S} samples")
@@ -657,16 +656,8 @@ class Planner:
         true = np.zeros((W, S, 2, NF))
         flags = np.zeros((W, S), dtype=np.int32)
         ms = np.zeros(2)
-        _check(lib().armour_episode_get_tracked(self.h, rec, _ptr(true), flags.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
-                                                _ptr(ms)))
-        rec = rec[:W]
-        out = {k: np.array([getattr(r, k)[:] for r in rec], dtype=np.float64).reshape(W, NF)
-               for k in ("max_pos_err", "max_vel_err", "max_torque")}
-        for k in ("clearance", "max_V", "max_robust"):
-            out[k] = np.array([getattr(r, k) for r in rec], dtype=np.float64)
-        out["clearance_at"] = np.array([r.clearance_at[:] for r in rec], dtype=np.int64).reshape(W, 4)
-        out["flags"] = np.array([r.flags for r in rec], dtype=np.int64)
-        out["flag_step"] = np.array([r.flag_step[:] for r in rec], dtype=np.int64).reshape(W, 5)
+        _check(lib().armour_episode_get_tracked(self.h, rec, _ptr(true), _iptr(flags), _ptr(ms)))
+        out = _records(EpisodeTracked, rec[:W])
         out.update(true_state=true, last_flags=flags, rollout_ms=float(ms[0]), check_ms=float(ms[1]))
         return out
 
@@ -675,15 +666,7 @@ class Planner:
         failed_plans, failed_streak [W], clearance [W], clearance_at [W, 3], goal_distance [W])"""
         st = (EpisodeState * max(self._W, 1))()
         _check(lib().armour_episode_get(self.h, st))
-        st = st[:self._W]
-        out = {k: np.array([getattr(s, k)[:] for s in st], dtype=np.float64).reshape(len(st), NF)
-               for k in ("q", "qd", "qdd", "q_des")}
-        for k in ("status", "mode", "steps", "failed_plans", "failed_streak"):
-            out[k] = np.array([getattr(s, k) for s in st], dtype=np.int64)
-        out["clearance"] = np.array([s.clearance for s in st], dtype=np.float64)
-        out["clearance_at"] = np.array([s.clearance_at[:] for s in st], dtype=np.int64).reshape(len(st), 3)
-        out["goal_distance"] = np.array([s.goal_distance for s in st], dtype=np.float64)
-        return out
+        return _records(EpisodeState, st[:self._W])
 
     def constraints(self, w):
         g = np.zeros(self._m(w))
@@ -739,8 +722,7 @@ class Planner:
         """(link [T, NJ], torque [T, 7]) k-only monomial counts of world w"""
         lk = np.zeros((self.T, self.NJ), dtype=np.int32)
         tq = np.zeros((self.T, NF), dtype=np.int32)
-        _check(lib().armour_get_monomial_counts(self.h, w, lk.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
-                                                tq.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        _check(lib().armour_get_monomial_counts(self.h, w, _iptr(lk), _iptr(tq)))
         return lk, tq
 
     OCCUPANCY = ("arena_hashes", "arena_rows", "operator_terms", "link_monomials", "torque_monomials",

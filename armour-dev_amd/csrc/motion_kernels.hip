@@ -30,6 +30,7 @@
 
 #include "../../include/armour_hip.h"
 #include "common.h"
+#include "track.h"
 #include "traj.h"
 #include "wave.h"
 
@@ -97,6 +98,31 @@ __device__ __forceinline__ double motion_separation(const double* ob, const doub
 
 // (value, index) ordered by value, then by index: the first minimiser
 __device__ inline bool motion_before(double v, int i, double bv, int bi) { return v < bv || (v == bv && i < bi); }
+// the wave's first minimum: every lane leaves with the winning (value, index)
+WAVE_FN void motion_first_min(double& v, int& i) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        const double ov = xor_f64(v, m);
+        const int oi = xor_i32(i, m);
+        if (motion_before(ov, oi, v, i)) {
+            v = ov;
+            i = oi;
+        }
+    }
+}
+
+// world w's obstacle count, within what a block stages
+__device__ inline int motion_obstacles(const MotionArgs& a, int w) {
+    const int O = a.Ow ? a.Ow[w] : a.O;
+    return O < 0 ? 0 : (O > MAX_OBS ? MAX_OBS : O);
+}
+// the pair behind idx = link * O + obstacle; idx < 0 (none): -1, -1
+struct MotionPair { int link, obs; };
+__device__ inline MotionPair motion_pair(int idx, int O) {
+    if (idx < 0) return {-1, -1};
+    const int l = idx / O;
+    return {l, idx - l * O};
+}
 
 // Where the configuration of a block comes from. MotionFromCurve: sample s of the world's Bezier curve
 // over its window (armour_check_motion, the episodes). MotionFromStates: check point c of rollout
@@ -108,7 +134,7 @@ struct MotionFromCurve {
     __device__ bool empty() const { return !(t0 <= t1); }
     __device__ double angle(const RobotParams& rp, int j) const {
         double q, qd, qdd;
-        bezier_joint(tr[j], tr[NF + j], tr[2 * NF + j], tr[3 * NF + j] * rp.k_range[j], motion_time(t0, t1, s, S), q, qd, qdd);
+        traj_joint(rp, tr, j, motion_time(t0, t1, s, S), q, qd, qdd);
         return q;
     }
 };
@@ -131,8 +157,7 @@ __device__ __forceinline__ void motion_check_body(const MotionArgs& a, int w, lo
     __shared__ int s_wi[MOTION_WAVES];
     const RobotParams& rp = *a.rp;
     const int NJ = rp.num_joints;
-    int O = a.Ow ? a.Ow[w] : a.O;
-    O = O < 0 ? 0 : (O > MAX_OBS ? MAX_OBS : O);
+    const int O = motion_obstacles(a, w);
     // (block-uniform) a world without obstacles, or one that executes nothing
     if (O == 0 || src.empty()) {
         if (tid == 0) {
@@ -156,21 +181,7 @@ __device__ __forceinline__ void motion_check_body(const MotionArgs& a, int w, lo
             const double* tr = rp.trans + 3 * i;
             for (int r = 0; r < 3; r++) p[r] += R[3 * r] * tr[0] + R[3 * r + 1] * tr[1] + R[3 * r + 2] * tr[2];
             double Ri[9], Rn[9];
-            for (int r = 0; r < 3; r++)
-                for (int c = 0; c < 3; c++) Ri[3 * r + c] = rp.rpy[i][r + 3 * c];  // (stored column-major)
-            const int ax = rp.axes[i];
-            if (ax != 0 && i < NF) {
-                // rotation by q about e_a; a reversed joint (code -a) turns about -e_a: Rot(e_a, -q)
-                const double c = s_cs[i][0], sn = ax > 0 ? s_cs[i][1] : -s_cs[i][1];
-                const int aa = (ax > 0 ? ax : -ax) - 1, u = (aa + 1) % 3, v = (aa + 2) % 3;
-                double Q[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, RQ[9];
-                Q[3 * u + u] = c;
-                Q[3 * v + v] = c;
-                Q[3 * u + v] = -sn;
-                Q[3 * v + u] = sn;
-                mat3_mul(Ri, Q, RQ);
-                for (int e = 0; e < 9; e++) Ri[e] = RQ[e];
-            }
+            track_joint_rot(rp, i, &s_cs[0][0], Ri);
             mat3_mul(R, Ri, Rn);
             for (int e = 0; e < 9; e++) R[e] = Rn[e];
             double* L = s_link[i];
@@ -184,22 +195,14 @@ __device__ __forceinline__ void motion_check_body(const MotionArgs& a, int w, lo
     double best = INFINITY;
     int bidx = INT_MAX;
     for (int idx = tid; idx < NJ * O; idx += MOTION_THREADS) {
-        const int l = idx / O, o = idx - l * O;
-        const double v = motion_separation(s_obs + 12 * o, s_link[l]);
+        const MotionPair pr = motion_pair(idx, O);
+        const double v = motion_separation(s_obs + 12 * pr.obs, s_link[pr.link]);
         if (motion_before(v, idx, best, bidx)) {
             best = v;
             bidx = idx;
         }
     }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-        const double ov = xor_f64(best, m);
-        const int oi = xor_i32(bidx, m);
-        if (motion_before(ov, oi, best, bidx)) {
-            best = ov;
-            bidx = oi;
-        }
-    }
+    motion_first_min(best, bidx);
     if ((tid & 63) == 0) {
         s_wv[tid >> 6] = best;
         s_wi[tid >> 6] = bidx;
@@ -257,8 +260,7 @@ __global__ __launch_bounds__(64) void motion_state_finish_kernel(MotionArgs a, T
     if (motion_world_skipped(a, w)) return;  // (block-uniform) its outputs stay as they were
     const RobotParams& rp = *a.rp;
     const long NR = (long)a.W * a.S;
-    int O = a.Ow ? a.Ow[w] : a.O;
-    O = O < 0 ? 0 : (O > MAX_OBS ? MAX_OBS : O);
+    const int O = motion_obstacles(a, w);
     double wbest = INFINITY;
     int ws = -1, wc = -1, widx = -1;
     for (int s = 0; s < a.S; s++) {
@@ -275,31 +277,25 @@ __global__ __launch_bounds__(64) void motion_state_finish_kernel(MotionArgs a, T
             for (int j = 0; j < NF; j++)
                 if (st[j] < rp.state_lb[j] || st[j] > rp.state_ub[j] || fabs(st[NF + j]) > rp.speed_limits[j]) out_of_limits = 1;
         }
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            const double ov = xor_f64(best, m);
-            const int oc = xor_i32(bc, m);
-            if (motion_before(ov, oc, best, bc)) {
-                best = ov;
-                bc = oc;
-            }
-            out_of_limits |= xor_i32(out_of_limits, m);
-        }
+        motion_first_min(best, bc);
+        out_of_limits = wave_or(out_of_limits);
         const bool none = bc == INT_MAX || O <= 0;
         const int idx = none ? -1 : a.pidx[r * f.C + bc];
         int fl = 0;
         if (!none && best <= 0) fl |= ARMOUR_TRACK_COLLISION;
         for (int j = 0; j < NF; j++) {
-            if (f.out[(2 * NR + r) * NF + j] > rp.torque_limits[j]) fl |= ARMOUR_TRACK_INPUT;
-            if (f.out[r * NF + j] > rp.qe || f.out[(NR + r) * NF + j] > rp.qde) fl |= ARMOUR_TRACK_BOUND;
+            if (f.out[track_out_max(TRACK_MAX_TORQUE, NR, r, j)] > rp.torque_limits[j]) fl |= ARMOUR_TRACK_INPUT;
+            if (f.out[track_out_max(TRACK_MAX_POS, NR, r, j)] > rp.qe || f.out[track_out_max(TRACK_MAX_VEL, NR, r, j)] > rp.qde)
+                fl |= ARMOUR_TRACK_BOUND;
         }
         if (out_of_limits) fl |= ARMOUR_TRACK_LIMIT;
         if (f.status[r] != 0) fl |= ARMOUR_TRACK_NOT_FINITE;
         if (lane == 0) {
+            const MotionPair pr = motion_pair(idx, O);
             f.clearance[r] = none ? INFINITY : best;
             f.where[3 * r] = none ? -1 : bc;
-            f.where[3 * r + 1] = none ? -1 : idx / O;
-            f.where[3 * r + 2] = none ? -1 : idx - (idx / O) * O;
+            f.where[3 * r + 1] = pr.link;
+            f.where[3 * r + 2] = pr.obs;
             f.flags[r] = fl;
         }
         if (!none && best < wbest) {
@@ -310,11 +306,12 @@ __global__ __launch_bounds__(64) void motion_state_finish_kernel(MotionArgs a, T
         }
     }
     if (lane == 0) {
+        const MotionPair pr = motion_pair(widx, O);  // (widx stays -1 with ws)
         f.wclear[w] = wbest;
         f.wwhere[4 * w] = ws;
         f.wwhere[4 * w + 1] = wc;
-        f.wwhere[4 * w + 2] = ws < 0 ? -1 : widx / O;
-        f.wwhere[4 * w + 3] = ws < 0 ? -1 : widx - (widx / O) * O;
+        f.wwhere[4 * w + 2] = pr.link;
+        f.wwhere[4 * w + 3] = pr.obs;
     }
 }
 
@@ -330,27 +327,15 @@ __global__ __launch_bounds__(64) void motion_finish_kernel(MotionArgs a, double*
             bs = s;
         }
     }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-        const double ov = xor_f64(best, m);
-        const int os = xor_i32(bs, m);
-        if (motion_before(ov, os, best, bs)) {
-            best = ov;
-            bs = os;
-        }
-    }
+    motion_first_min(best, bs);
     if (lane == 0) {
-        int O = a.Ow ? a.Ow[w] : a.O;
-        if (bs == INT_MAX || O <= 0) {
-            clearance[w] = INFINITY;
-            where[3 * w] = where[3 * w + 1] = where[3 * w + 2] = -1;
-        } else {
-            const int idx = a.pidx[(long)w * a.S + bs];
-            clearance[w] = best;
-            where[3 * w] = bs;
-            where[3 * w + 1] = idx / O;
-            where[3 * w + 2] = idx - (idx / O) * O;
-        }
+        const int O = motion_obstacles(a, w);
+        const bool none = bs == INT_MAX || O <= 0;
+        const MotionPair pr = motion_pair(none ? -1 : a.pidx[(long)w * a.S + bs], O);
+        clearance[w] = none ? INFINITY : best;
+        where[3 * w] = none ? -1 : bs;
+        where[3 * w + 1] = pr.link;
+        where[3 * w + 2] = pr.obs;
     }
 }
 
@@ -488,7 +473,7 @@ __global__ void episode_advance_kernel(EpisodeDev e) {
     double q[NF], qd[NF], qdd[NF];
     bool ok = true;
     for (int j = 0; j < NF; j++) {
-        bezier_joint(ex[j], ex[NF + j], ex[2 * NF + j], ex[3 * NF + j] * rp.k_range[j], t1, q[j], qd[j], qdd[j]);
+        traj_joint(rp, ex, j, t1, q[j], qd[j], qdd[j]);
         ok = ok && isfinite(q[j]) && isfinite(qd[j]) && isfinite(qdd[j]) && fabs(q[j]) <= ARMOUR_MAX_ABS_ANGLE;
     }
     if (!ok) {
@@ -506,7 +491,7 @@ __global__ void episode_advance_kernel(EpisodeDev e) {
     for (int s = 0; s < e.S; s++) {
         double qs[NF], v, a;
         const double t = motion_time(t0, t1, s, e.S);
-        for (int j = 0; j < NF; j++) bezier_joint(ex[j], ex[NF + j], ex[2 * NF + j], ex[3 * NF + j] * rp.k_range[j], t, qs[j], v, a);
+        for (int j = 0; j < NF; j++) traj_joint(rp, ex, j, t, qs[j], v, a);
         reached = reached || goal_distance(qs, goal) <= e.goal_radius;
     }
     for (int j = 0; j < NF; j++) {
@@ -603,12 +588,12 @@ __global__ void episode_track_fold_kernel(EpisodeDev e, EpisodeTrackDev t) {
     for (int s = 0; s < t.S; s++) {
         const long r = (long)w * t.S + s;
         for (int j = 0; j < NF; j++) {
-            R.max_pos_err[j] = fmax(R.max_pos_err[j], t.out[r * NF + j]);
-            R.max_vel_err[j] = fmax(R.max_vel_err[j], t.out[(NR + r) * NF + j]);
-            R.max_torque[j] = fmax(R.max_torque[j], t.out[(2 * NR + r) * NF + j]);
+            R.max_pos_err[j] = fmax(R.max_pos_err[j], t.out[track_out_max(TRACK_MAX_POS, NR, r, j)]);
+            R.max_vel_err[j] = fmax(R.max_vel_err[j], t.out[track_out_max(TRACK_MAX_VEL, NR, r, j)]);
+            R.max_torque[j] = fmax(R.max_torque[j], t.out[track_out_max(TRACK_MAX_TORQUE, NR, r, j)]);
         }
-        R.max_V = fmax(R.max_V, t.out[21 * NR + r]);
-        R.max_robust = fmax(R.max_robust, t.out[22 * NR + r]);
+        R.max_V = fmax(R.max_V, t.out[track_out_V(NR, r)]);
+        R.max_robust = fmax(R.max_robust, t.out[track_out_robust(NR, r)]);
         t.flags[r] = t.rflags[r];
         fl |= t.rflags[r];
     }

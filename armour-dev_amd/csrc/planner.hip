@@ -88,6 +88,86 @@ struct GrowSet {
     }
 };
 
+// The execution layer's state on a planner (everything that runs a plan after it is found) is one struct
+// per feature: its device pointers on this base, which holds the buffers regrown on demand and the events
+// around the feature's kernels, both made on first use, and releases them for armour_destroy.
+struct ExecState {
+    GrowSet grow;
+    hipEvent_t ev[4] = {};
+    int events(int n) {  // the first n exist from here on
+        for (int i = 0; i < n; i++)
+            if (!ev[i]) HIPCK(hipEventCreate(&ev[i]));
+        return 0;
+    }
+    void release() {
+        grow.release();
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+// device time between two recorded events (*ms is left alone when the read fails)
+static int elapsed_ms(hipEvent_t a, hipEvent_t b, double* ms) {
+    float f = 0.f;
+    HIPCK(hipEventElapsedTime(&f, a, b));
+    *ms = f;
+    return 0;
+}
+// armour_check_motion and the episodes' check of the desired arm (motion_kernels.hip): per-sample minima
+// for max_worlds x grow.cap samples; the caller's trajectories and the per-world results, allocated once
+// (the planner's `allocs` own them)
+struct MotionCheck : ExecState {
+    double* pval = nullptr;
+    int* pidx = nullptr;
+    double *traj = nullptr, *clear = nullptr;
+    int* where = nullptr;
+};
+// armour_track (track_kernels.hip): inputs and per-rollout outputs for grow.cap rollouts
+struct Rollouts : ExecState {
+    double *traj = nullptr, *scale = nullptr, *err0 = nullptr, *out = nullptr;
+    int* status = nullptr;
+    int reserve(hipStream_t stream, long NR) {
+        if (int rc = events(2)) return rc;
+        const size_t n = (size_t)NR;
+        return grow.reserve(stream, NR,
+                            {GrowSet::buf(traj, n * TRAJ_DOUBLES), GrowSet::buf(scale, n * 2 * MAX_J), GrowSet::buf(err0, n * 2 * NF),
+                             GrowSet::buf(out, n * TRACK_OUT_DOUBLES), GrowSet::buf(status, n)},
+                            "hipMalloc failed for the tracking rollouts' buffers (num_traj x num_samples)");
+    }
+};
+// armour_track_motion (the recording track kernels, motion_state_*_kernel): the recorded check points,
+// their per-check-point minima and the per-rollout and per-world results, for grow.cap = rollouts x
+// check points (check points >= 2, so at most cap / 2 rollouts: the per-rollout arrays are sized by the
+// cells as well, which holds for every split)
+struct TrueArmCheck : ExecState {
+    double *rec = nullptr, *pval = nullptr, *clear = nullptr, *wclear = nullptr;
+    int *pidx = nullptr, *where = nullptr, *flags = nullptr, *wwhere = nullptr;
+    int reserve(hipStream_t stream, long cells, int Wmax) {
+        if (int rc = events(2)) return rc;
+        const size_t n = (size_t)cells, Wm = (size_t)Wmax;
+        return grow.reserve(stream, cells,
+                            {GrowSet::buf(rec, n * 2 * NF), GrowSet::buf(pval, n), GrowSet::buf(pidx, n), GrowSet::buf(clear, n),
+                             GrowSet::buf(where, n * 3), GrowSet::buf(flags, n), GrowSet::buf(wclear, Wm), GrowSet::buf(wwhere, Wm * 4)},
+                            "hipMalloc failed for the true-arm check's buffers (worlds x num_samples x check_samples)");
+    }
+};
+// armour_episode_*: the episode's own arrays are allocated by the first begin (the planner's `allocs`)
+struct Episode : ExecState {
+    bool on = false;       // an episode is running (armour_episode_begin .. any other reach / plan entry)
+    bool stepped = false;  // it has taken a step
+    EpisodeDev dev{};
+    int* accept = nullptr;
+    std::vector<armour_episode_state> host;  // the states after the last begin / step
+};
+// armour_episode_track: what a tracked episode keeps between steps (the true arms' states, their scales,
+// the worlds' records), for grow.cap = max_worlds x num_samples rollouts
+struct TrackedEpisode : ExecState {
+    bool on = false;  // armour_episode_track .. the next armour_episode_begin
+    EpisodeTrackDev dev{};
+    int steps = 0;
+    double *state = nullptr, *scale = nullptr;
+    bool scaled = false;
+};
+
 // planners alive per device (armour_create / armour_destroy): the bundle kernel's shape depends on
 // whether the GPU is shared (lane_shape_for)
 static std::atomic<int> g_planners[64];
@@ -319,41 +399,12 @@ struct armour_planner {
     // first use, regrown when a call brings more candidates per world)
     CandDev cd{};
     GrowSet cand;
-    // armour_check_motion and the episodes (motion_kernels.hip): per-sample minima for max_worlds x
-    // motion.cap samples (allocated on first use, regrown for more samples), the caller's
-    // trajectories and the per-world results; the episode's own arrays, allocated by the first begin
-    double* mo_pval = nullptr;
-    int* mo_pidx = nullptr;
-    GrowSet motion;
-    double *mo_traj = nullptr, *mo_clear = nullptr;
-    int* mo_where = nullptr;
-    bool episode = false;      // an episode is running (armour_episode_begin .. any other reach / plan entry)
-    EpisodeDev ep{};
-    int* ep_accept = nullptr;
-    hipEvent_t ep_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    std::vector<armour_episode_state> ep_host;  // the states after the last begin / step
-    // armour_track (track_kernels.hip): inputs and per-rollout outputs for track.cap rollouts,
-    // allocated on first use and regrown on demand
-    double *tr_traj = nullptr, *tr_scale = nullptr, *tr_err0 = nullptr, *tr_out = nullptr;
-    int* tr_status = nullptr;
-    GrowSet track;
-    hipEvent_t tr_ev[2] = {nullptr, nullptr};
-    // armour_track_motion (the recording track kernels, motion_state_*_kernel): the recorded check points,
-    // their per-check-point minima and the per-rollout and per-world results, for tracked.cap =
-    // rollouts x check points, allocated on first use and regrown on demand
-    double *tm_rec = nullptr, *tm_pval = nullptr, *tm_clear = nullptr, *tm_wclear = nullptr;
-    int *tm_pidx = nullptr, *tm_where = nullptr, *tm_flags = nullptr, *tm_wwhere = nullptr;
-    GrowSet tracked;
-    hipEvent_t tm_ev[2] = {nullptr, nullptr};
-    // armour_episode_track: what a tracked episode keeps between steps (the true arms' states, their
-    // scales, the worlds' records), for ep_tracked.cap = max_worlds x num_samples rollouts
-    bool ep_track_on = false;  // armour_episode_track .. the next armour_episode_begin
-    bool ep_stepped = false;   // the episode has taken a step
-    EpisodeTrackDev ept{};
-    int ept_steps = 0;
-    double *ept_state = nullptr, *ept_scale = nullptr;
-    bool ept_scaled = false;
-    GrowSet ep_tracked;
+    // the execution layer (the structs above)
+    MotionCheck motion;
+    Rollouts track;
+    TrueArmCheck tracked;
+    Episode ep;
+    TrackedEpisode ept;
     std::vector<void*> allocs;
     long long paths[PATH_N] = {};  // the path census (armour_get_path_counts)
     void took(PathId c, long long n = 1) { paths[c] += n; }
@@ -1501,18 +1552,6 @@ static int run_solver(armour_planner* p) {
     return 0;
 }
 
-// buffers of armour_track for NR rollouts
-static int track_reserve(armour_planner* p, long NR) {
-    if (!p->tr_ev[0])
-        for (int i = 0; i < 2; i++) HIPCK(hipEventCreate(&p->tr_ev[i]));
-    const size_t n = (size_t)NR;
-    return p->track.reserve(p->stream, NR,
-                            {GrowSet::buf(p->tr_traj, n * TRAJ_DOUBLES), GrowSet::buf(p->tr_scale, n * 2 * MAX_J),
-                             GrowSet::buf(p->tr_err0, n * 2 * NF), GrowSet::buf(p->tr_out, n * TRACK_OUT_DOUBLES),
-                             GrowSet::buf(p->tr_status, n)},
-                            "hipMalloc failed for the tracking rollouts' buffers (num_traj x num_samples)");
-}
-
 // Every entry point runs on its planner's device, whatever the calling thread's current device is
 // (handles may be driven from other host threads); the caller's device is restored.
 // The device-level entries (create, self-check, copy bandwidth) name their device themselves.
@@ -1663,13 +1702,8 @@ void armour_destroy(armour_planner* p) {
     if (!p) return;
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     for (void* a : p->allocs) (void)hipFree(a);
-    for (GrowSet* g : {&p->cand, &p->motion, &p->track, &p->tracked, &p->ep_tracked}) g->release();
-    for (hipEvent_t e : p->ep_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : p->tr_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : p->tm_ev)
-        if (e) (void)hipEventDestroy(e);
+    p->cand.release();
+    for (ExecState* x : std::initializer_list<ExecState*>{&p->motion, &p->track, &p->tracked, &p->ep, &p->ept}) x->release();
     if (p->h_flags) (void)hipHostFree(p->h_flags);
     if (p->h_sum) (void)hipHostFree(p->h_sum);
     if (p->h_ws) (void)hipHostFree(p->h_ws);
@@ -1737,7 +1771,7 @@ static int run_batch(armour_planner* p, BatchKind kind, bool plan, int W, const 
     if (kind == BATCH_UNIFORM && p->armtd)
         return fail(ARMOUR_E_ARG, plan ? "an ARMTD planner takes armour_armtd_world (armour_plan_armtd_batch)"
                                        : "an ARMTD planner takes armour_armtd_world (armour_reach_armtd_batch)");
-    p->reached = p->planned = p->evaluated = p->episode = false;
+    p->reached = p->planned = p->evaluated = p->ep.on = false;
     auto t0 = std::chrono::steady_clock::now();
     const int rc = kind == BATCH_ARMTD ? upload_armtd(p, W, (const armour_armtd_world*)worlds)
                                        : upload_worlds(p, W, (const armour_world*)worlds, kind == BATCH_MIXED);
@@ -1867,6 +1901,46 @@ int armour_eval_constraints(armour_planner* p, int w, const double* x, double* g
     return 0;
 }
 
+// ---- checks shared by the candidate and execution entries: the messages are part of the interface
+//  ----
+// `what_is`: the feature and its verb ("episodes are")
+static int not_available(const armour_planner* p, const char* what_is) {
+    if (p->armtd) return fail(ARMOUR_E_ARG, std::string(what_is) + " not available on an ARMTD planner");
+    if (p->set.eval_f32) return fail(ARMOUR_E_ARG, std::string(what_is) + " not available with the fp32 study (ARMOUR_EVAL_F32)");
+    return 0;
+}
+static int no_episode() {
+    return fail(ARMOUR_E_STATE, "no episode: call armour_episode_begin first (any other reach or plan entry ends one)");
+}
+// N trajectories [4][NF]: every value finite and every k inside [-1, 1]; the rollouts, whose messages
+// name the array, also hold |q0| to ARMOUR_MAX_ABS_ANGLE
+static int check_traj(const double* traj, int N, bool rollouts) {
+    for (int n = 0; n < N; n++) {
+        const double* t = traj + (size_t)n * TRAJ_DOUBLES;
+        for (int i = 0; i < TRAJ_DOUBLES; i++)
+            if (!std::isfinite(t[i])) return fail(ARMOUR_E_ARG, "traj holds a value that is not finite");
+        for (int i = 0; i < NF; i++) {
+            if (rollouts && !(std::fabs(t[i]) <= ARMOUR_MAX_ABS_ANGLE))
+                return fail(ARMOUR_E_ARG, "traj: every |q0| must be at most ARMOUR_MAX_ABS_ANGLE");
+            if (!(std::fabs(t[3 * NF + i]) <= 1.0))
+                return fail(ARMOUR_E_ARG, std::string(rollouts ? "traj: " : "") + "every k must lie inside [-1, 1]");
+        }
+    }
+    return 0;
+}
+// the optional scales [NR][2][NJ] and start errors [NR][2][NF] of NR rollouts
+static int check_scale_err0(const double* scale, const double* err0, size_t NR, int NJ) {
+    if (scale)
+        for (size_t i = 0; i < NR * 2 * NJ; i++) {
+            if (!std::isfinite(scale[i])) return fail(ARMOUR_E_ARG, "scale holds a value that is not finite");
+            if (!(scale[i] > 0)) return fail(ARMOUR_E_ARG, "every scale must be positive");
+        }
+    if (err0)
+        for (size_t i = 0; i < NR * 2 * NF; i++)
+            if (!std::isfinite(err0[i])) return fail(ARMOUR_E_ARG, "err0 holds a value that is not finite");
+    return 0;
+}
+
 // buffers of armour_eval_candidates for N candidates per world
 static int cand_reserve(armour_planner* p, int N) {
     CandDev& c = p->cd;
@@ -1882,8 +1956,7 @@ int armour_eval_candidates(armour_planner* p, int N, const double* x, double* co
                            int* best) {
     DeviceScope device_scope(p);
     if (!p || !x) return fail(ARMOUR_E_ARG, "null planner / x");
-    if (p->armtd) return fail(ARMOUR_E_ARG, "candidate evaluation is not available on an ARMTD planner");
-    if (p->set.eval_f32) return fail(ARMOUR_E_ARG, "candidate evaluation is not available with the fp32 study (ARMOUR_EVAL_F32)");
+    if (int rc = not_available(p, "candidate evaluation is")) return rc;
     if (N < 1) return fail(ARMOUR_E_ARG, "num_candidates must be at least 1");
     if (!p->reached) return fail(ARMOUR_E_STATE, "no batch: call a reach or plan entry first");
     const int W = p->W;
@@ -1924,18 +1997,19 @@ int armour_eval_candidates(armour_planner* p, int N, const double* x, double* co
 
 // buffers of the execution check for S samples per world
 static int motion_reserve(armour_planner* p, int S) {
+    MotionCheck& m = p->motion;
     int rc = 0;
-    if (!p->mo_traj && ((rc = p->alloc(&p->mo_traj, (size_t)p->Wmax * TRAJ_DOUBLES)) ||
-                        (rc = p->alloc(&p->mo_clear, (size_t)p->Wmax)) || (rc = p->alloc(&p->mo_where, 3 * (size_t)p->Wmax))))
+    if (!m.traj && ((rc = p->alloc(&m.traj, (size_t)p->Wmax * TRAJ_DOUBLES)) || (rc = p->alloc(&m.clear, (size_t)p->Wmax)) ||
+                    (rc = p->alloc(&m.where, 3 * (size_t)p->Wmax))))
         return rc;
     const size_t n = (size_t)p->Wmax * S;
-    return p->motion.reserve(p->stream, S, {GrowSet::buf(p->mo_pval, n), GrowSet::buf(p->mo_pidx, n)},
-                             "hipMalloc failed for the execution check's buffers (max_worlds x samples)");
+    return m.grow.reserve(p->stream, S, {GrowSet::buf(m.pval, n), GrowSet::buf(m.pidx, n)},
+                          "hipMalloc failed for the execution check's buffers (max_worlds x samples)");
 }
 
-// the execution check of the resident batch over S samples of `traj` (device, [W][4][7]): per-world
-// windows `win` (device, [W][2]) or [t0, t1] for every world; results in mo_clear / mo_where
-static void launch_motion(armour_planner* p, const double* traj, const double* win, double t0, double t1, int S) {
+// the check kernels' view of the resident batch: S samples per world, per-world windows `win` (device,
+// [W][2]; null: none), the minima in pval / pidx
+static MotionArgs motion_args(const armour_planner* p, int S, const double* win, double* pval, int* pidx) {
     MotionArgs a{};
     a.rp = p->d_rp;
     a.W = p->W;
@@ -1943,40 +2017,41 @@ static void launch_motion(armour_planner* p, const double* traj, const double* w
     a.O = p->d.O;
     a.Ow = p->d.Ow;
     a.obs = p->obs;
-    a.traj = traj;
     a.win = win;
+    a.pval = pval;
+    a.pidx = pidx;
+    return a;
+}
+
+// the execution check of the resident batch over S samples of `traj` (device, [W][4][7]): per-world
+// windows `win` or [t0, t1] for every world; results in motion.clear / motion.where
+static void launch_motion(armour_planner* p, const double* traj, const double* win, double t0, double t1, int S) {
+    MotionArgs a = motion_args(p, S, win, p->motion.pval, p->motion.pidx);
+    a.traj = traj;
     a.t0 = t0;
     a.t1 = t1;
-    a.pval = p->mo_pval;
-    a.pidx = p->mo_pidx;
     p->took(PATH_MOTION_CHUNKS, S);
     hipLaunchKernelGGL(motion_check_kernel, dim3(S, p->W), dim3(MOTION_THREADS), 0, p->stream, a);
-    hipLaunchKernelGGL(motion_finish_kernel, dim3(p->W), dim3(64), 0, p->stream, a, p->mo_clear, p->mo_where);
+    hipLaunchKernelGGL(motion_finish_kernel, dim3(p->W), dim3(64), 0, p->stream, a, p->motion.clear, p->motion.where);
 }
 
 int armour_check_motion(armour_planner* p, const double* traj, double t0, double t1, int samples, double* clearance,
                         int* where) {
     DeviceScope device_scope(p);
     if (!p || !traj) return fail(ARMOUR_E_ARG, "null planner / traj");
-    if (p->armtd) return fail(ARMOUR_E_ARG, "the execution check is not available on an ARMTD planner");
-    if (p->set.eval_f32) return fail(ARMOUR_E_ARG, "the execution check is not available with the fp32 study (ARMOUR_EVAL_F32)");
+    if (int rc = not_available(p, "the execution check is")) return rc;
     if (samples < 1 || samples > 65535) return fail(ARMOUR_E_ARG, "samples must lie in 1 .. 65535");
     if (!(t0 >= 0.0 && t1 <= 1.0 && t0 <= t1)) return fail(ARMOUR_E_ARG, "the window must satisfy 0 <= t0 <= t1 <= 1");
     if (!p->reached) return fail(ARMOUR_E_STATE, "no batch: call a reach or plan entry first");
     const int W = p->W;
-    for (int w = 0; w < W; w++) {
-        const double* t = traj + (size_t)w * TRAJ_DOUBLES;
-        for (int i = 0; i < TRAJ_DOUBLES; i++)
-            if (!std::isfinite(t[i])) return fail(ARMOUR_E_ARG, "traj holds a value that is not finite");
-        for (int i = 0; i < NF; i++)
-            if (!(std::fabs(t[3 * NF + i]) <= 1.0)) return fail(ARMOUR_E_ARG, "every k must lie inside [-1, 1]");
-    }
+    if (int rc = check_traj(traj, W, false)) return rc;
     if (int rc = motion_reserve(p, samples)) return rc;
-    HIPCK(hipMemcpyAsync(p->mo_traj, traj, sizeof(double) * W * TRAJ_DOUBLES, hipMemcpyHostToDevice, p->stream));
-    launch_motion(p, p->mo_traj, nullptr, t0, t1, samples);
+    const MotionCheck& m = p->motion;
+    HIPCK(hipMemcpyAsync(m.traj, traj, sizeof(double) * W * TRAJ_DOUBLES, hipMemcpyHostToDevice, p->stream));
+    launch_motion(p, m.traj, nullptr, t0, t1, samples);
     HIPCK(hipGetLastError());
-    if (clearance) HIPCK(hipMemcpyAsync(clearance, p->mo_clear, sizeof(double) * W, hipMemcpyDeviceToHost, p->stream));
-    if (where) HIPCK(hipMemcpyAsync(where, p->mo_where, sizeof(int) * 3 * W, hipMemcpyDeviceToHost, p->stream));
+    if (clearance) HIPCK(hipMemcpyAsync(clearance, m.clear, sizeof(double) * W, hipMemcpyDeviceToHost, p->stream));
+    if (where) HIPCK(hipMemcpyAsync(where, m.where, sizeof(int) * 3 * W, hipMemcpyDeviceToHost, p->stream));
     HIPCK(hipStreamSynchronize(p->stream));
     return 0;
 }
@@ -1991,46 +2066,27 @@ static bool track_serial_asked() {
 // the argument checks of the tracking entries after their null checks: before any device work
 static int track_check_args(armour_planner* p, int N, const double* traj, int S, const double* scale, const double* err0,
                             double t0, double t1, int steps) {
-    if (p->armtd) return fail(ARMOUR_E_ARG, "tracking rollouts are not available on an ARMTD planner");
-    if (p->set.eval_f32) return fail(ARMOUR_E_ARG, "tracking rollouts are not available with the fp32 study (ARMOUR_EVAL_F32)");
+    if (int rc = not_available(p, "tracking rollouts are")) return rc;
     if (N < 1 || S < 1) return fail(ARMOUR_E_ARG, "num_traj and num_samples must be at least 1");
     if ((long)N * S > ARMOUR_TRACK_MAX_ROLLOUTS) return fail(ARMOUR_E_ARG, "num_traj x num_samples exceeds ARMOUR_TRACK_MAX_ROLLOUTS");
     if (steps < 1 || steps > ARMOUR_TRACK_MAX_STEPS) return fail(ARMOUR_E_ARG, "steps must lie in 1 .. ARMOUR_TRACK_MAX_STEPS");
     if (!(t0 >= 0.0 && t0 < t1 && t1 <= 1.0)) return fail(ARMOUR_E_ARG, "the window must satisfy 0 <= t0 < t1 <= 1");
-    const long NR = (long)N * S;
-    const int NJ = p->NJ;
-    for (int n = 0; n < N; n++) {
-        const double* t = traj + (size_t)n * TRAJ_DOUBLES;
-        for (int i = 0; i < TRAJ_DOUBLES; i++)
-            if (!std::isfinite(t[i])) return fail(ARMOUR_E_ARG, "traj holds a value that is not finite");
-        for (int i = 0; i < NF; i++) {
-            if (!(std::fabs(t[i]) <= ARMOUR_MAX_ABS_ANGLE)) return fail(ARMOUR_E_ARG, "traj: every |q0| must be at most ARMOUR_MAX_ABS_ANGLE");
-            if (!(std::fabs(t[3 * NF + i]) <= 1.0)) return fail(ARMOUR_E_ARG, "traj: every k must lie inside [-1, 1]");
-        }
-    }
-    if (scale)
-        for (size_t i = 0; i < (size_t)NR * 2 * NJ; i++) {
-            if (!std::isfinite(scale[i])) return fail(ARMOUR_E_ARG, "scale holds a value that is not finite");
-            if (!(scale[i] > 0)) return fail(ARMOUR_E_ARG, "every scale must be positive");
-        }
-    if (err0)
-        for (size_t i = 0; i < (size_t)NR * 2 * NF; i++)
-            if (!std::isfinite(err0[i])) return fail(ARMOUR_E_ARG, "err0 holds a value that is not finite");
-    return 0;
+    if (int rc = check_traj(traj, N, true)) return rc;
+    return check_scale_err0(scale, err0, (size_t)N * S, p->NJ);
 }
 
 // launches the rollouts of `a` (device pointers; out and status are filled in here) between the events
-// tr_ev[0] and tr_ev[1]: the plain kernels, the recording ones (x.rec) or a tracked episode's (x.win)
+// track.ev[0] and track.ev[1]: the plain kernels, the recording ones (x.rec) or a tracked episode's (x.win)
 static int track_launch(armour_planner* p, TrackArgs a, const TrackExtra& x) {
     const long NR = (long)a.N * a.S;
     a.rp = p->d_rp;
-    a.out = p->tr_out;
-    a.status = p->tr_status;
+    a.out = p->track.out;
+    a.status = p->track.status;
     // the row form is the default (DESIGN.md section 4 has the measurement)
     const bool serial = track_serial_asked();
     const dim3 grid((unsigned)(serial ? (NR + TRACK_THREADS - 1) / TRACK_THREADS : (NR + TRACK_ROWS - 1) / TRACK_ROWS));
     const dim3 block(TRACK_THREADS);
-    HIPCK(hipEventRecord(p->tr_ev[0], p->stream));
+    HIPCK(hipEventRecord(p->track.ev[0], p->stream));
     p->took(x.win ? (serial ? PATH_TRACK_SERIAL_EPISODE : PATH_TRACK_ROW_EPISODE)
             : x.rec ? (serial ? PATH_TRACK_SERIAL_REC : PATH_TRACK_ROW_REC) : (serial ? PATH_TRACK_SERIAL : PATH_TRACK_ROW));
     if (x.win && serial)
@@ -2046,7 +2102,7 @@ static int track_launch(armour_planner* p, TrackArgs a, const TrackExtra& x) {
     else
         hipLaunchKernelGGL(track_row_kernel, grid, block, 0, p->stream, a);
     HIPCK(hipGetLastError());
-    HIPCK(hipEventRecord(p->tr_ev[1], p->stream));
+    HIPCK(hipEventRecord(p->track.ev[1], p->stream));
     return 0;
 }
 
@@ -2056,16 +2112,17 @@ static int track_upload_launch(armour_planner* p, int N, const double* traj, int
                                double t0, double t1, int steps, double* rec, int stride) {
     const long NR = (long)N * S;
     const int NJ = p->NJ;
-    if (int rc = track_reserve(p, NR)) return rc;
-    HIPCK(hipMemcpyAsync(p->tr_traj, traj, sizeof(double) * N * TRAJ_DOUBLES, hipMemcpyHostToDevice, p->stream));
-    if (scale) HIPCK(hipMemcpyAsync(p->tr_scale, scale, sizeof(double) * NR * 2 * NJ, hipMemcpyHostToDevice, p->stream));
-    if (err0) HIPCK(hipMemcpyAsync(p->tr_err0, err0, sizeof(double) * NR * 2 * NF, hipMemcpyHostToDevice, p->stream));
+    Rollouts& r = p->track;
+    if (int rc = r.reserve(p->stream, NR)) return rc;
+    HIPCK(hipMemcpyAsync(r.traj, traj, sizeof(double) * N * TRAJ_DOUBLES, hipMemcpyHostToDevice, p->stream));
+    if (scale) HIPCK(hipMemcpyAsync(r.scale, scale, sizeof(double) * NR * 2 * NJ, hipMemcpyHostToDevice, p->stream));
+    if (err0) HIPCK(hipMemcpyAsync(r.err0, err0, sizeof(double) * NR * 2 * NF, hipMemcpyHostToDevice, p->stream));
     TrackArgs a{};
     a.N = N;
     a.S = S;
-    a.traj = p->tr_traj;
-    a.scale = scale ? p->tr_scale : nullptr;
-    a.err0 = err0 ? p->tr_err0 : nullptr;
+    a.traj = r.traj;
+    a.scale = scale ? r.scale : nullptr;
+    a.err0 = err0 ? r.err0 : nullptr;
     a.t0 = t0;
     a.t1 = t1;
     a.steps = steps;
@@ -2075,13 +2132,14 @@ static int track_upload_launch(armour_planner* p, int N, const double* traj, int
 // queues the copies of the rollouts' outputs the caller asked for
 static int track_copy_out(armour_planner* p, long NR, armour_track_output* out) {
     const size_t n = (size_t)NR;
-    struct { double* dst; size_t off, len; } parts[] = {
-        {out->max_pos_err, 0, n * NF},       {out->max_vel_err, n * NF, n * NF}, {out->max_torque, 2 * n * NF, n * NF},
-        {out->max_V, 21 * n, n},             {out->max_robust, 22 * n, n},       {out->end_state, 23 * n, n * 2 * NF}};
+    struct { double* dst; long off; size_t len; } parts[] = {  // each field from its first element on
+        {out->max_pos_err, track_out_max(TRACK_MAX_POS, NR, 0, 0), n * NF}, {out->max_vel_err, track_out_max(TRACK_MAX_VEL, NR, 0, 0), n * NF},
+        {out->max_torque, track_out_max(TRACK_MAX_TORQUE, NR, 0, 0), n * NF}, {out->max_V, track_out_V(NR, 0), n},
+        {out->max_robust, track_out_robust(NR, 0), n}, {out->end_state, track_out_end(NR, 0, 0, 0), n * 2 * NF}};
     for (const auto& part : parts)
         if (part.dst)
-            HIPCK(hipMemcpyAsync(part.dst, p->tr_out + part.off, sizeof(double) * part.len, hipMemcpyDeviceToHost, p->stream));
-    if (out->status) HIPCK(hipMemcpyAsync(out->status, p->tr_status, sizeof(int) * n, hipMemcpyDeviceToHost, p->stream));
+            HIPCK(hipMemcpyAsync(part.dst, p->track.out + part.off, sizeof(double) * part.len, hipMemcpyDeviceToHost, p->stream));
+    if (out->status) HIPCK(hipMemcpyAsync(out->status, p->track.status, sizeof(int) * n, hipMemcpyDeviceToHost, p->stream));
     return 0;
 }
 
@@ -2093,46 +2151,22 @@ int armour_track(armour_planner* p, int N, const double* traj, int S, const doub
     if (int rc = track_upload_launch(p, N, traj, S, scale, err0, t0, t1, steps, nullptr, 1)) return rc;
     if (int rc = track_copy_out(p, (long)N * S, out)) return rc;
     HIPCK(hipStreamSynchronize(p->stream));
-    float ms = 0.f;
-    HIPCK(hipEventElapsedTime(&ms, p->tr_ev[0], p->tr_ev[1]));
-    out->track_ms = ms;
-    return 0;
-}
-
-// buffers of armour_track_motion for `cells` = rollouts x check points (check points >= 2, so at most
-// cells / 2 rollouts: the per-rollout arrays are sized by cells as well, which holds for every split)
-static int tracked_reserve(armour_planner* p, long cells) {
-    if (!p->tm_ev[0])
-        for (int i = 0; i < 2; i++) HIPCK(hipEventCreate(&p->tm_ev[i]));
-    const size_t n = (size_t)cells, Wm = (size_t)p->Wmax;
-    return p->tracked.reserve(p->stream, cells,
-                              {GrowSet::buf(p->tm_rec, n * 2 * NF), GrowSet::buf(p->tm_pval, n), GrowSet::buf(p->tm_pidx, n),
-                               GrowSet::buf(p->tm_clear, n), GrowSet::buf(p->tm_where, n * 3), GrowSet::buf(p->tm_flags, n),
-                               GrowSet::buf(p->tm_wclear, Wm), GrowSet::buf(p->tm_wwhere, Wm * 4)},
-                              "hipMalloc failed for the true-arm check's buffers (worlds x num_samples x check_samples)");
+    return elapsed_ms(p->track.ev[0], p->track.ev[1], &out->track_ms);
 }
 
 // the true-arm check of the resident batch over the C recorded check points of its W x S rollouts
-// (tm_rec, with the rollouts' outputs in tr_out / tr_status), between the events tm_ev[0] and tm_ev[1];
+// (tracked.rec, with the rollouts' outputs in track.out / track.status), between the events tracked.ev[0] and [1];
 // win (device, [W][2]; a tracked episode's step): worlds with an empty window are skipped
 static int launch_state_check(armour_planner* p, int S, int C, const double* win) {
-    MotionArgs a{};
-    a.rp = p->d_rp;
-    a.W = p->W;
-    a.S = S;
-    a.O = p->d.O;
-    a.Ow = p->d.Ow;
-    a.obs = p->obs;
-    a.win = win;
-    a.pval = p->tm_pval;
-    a.pidx = p->tm_pidx;
-    TrackedFinish f{C, p->tm_rec, p->tr_out, p->tr_status, p->tm_clear, p->tm_where, p->tm_flags, p->tm_wclear, p->tm_wwhere};
-    HIPCK(hipEventRecord(p->tm_ev[0], p->stream));
+    const TrueArmCheck& k = p->tracked;
+    const MotionArgs a = motion_args(p, S, win, k.pval, k.pidx);
+    TrackedFinish f{C, k.rec, p->track.out, p->track.status, k.clear, k.where, k.flags, k.wclear, k.wwhere};
+    HIPCK(hipEventRecord(k.ev[0], p->stream));
     hipLaunchKernelGGL(motion_state_check_kernel, dim3(C, S, p->W), dim3(MOTION_THREADS), 0, p->stream, a,
-                       (const double*)p->tm_rec, C);
+                       (const double*)k.rec, C);
     hipLaunchKernelGGL(motion_state_finish_kernel, dim3(p->W), dim3(64), 0, p->stream, a, f);
     HIPCK(hipGetLastError());
-    HIPCK(hipEventRecord(p->tm_ev[1], p->stream));
+    HIPCK(hipEventRecord(k.ev[1], p->stream));
     return 0;
 }
 
@@ -2149,29 +2183,26 @@ int armour_track_motion(armour_planner* p, const double* traj, int S, const doub
     if (S > 65535) return fail(ARMOUR_E_ARG, "num_samples must be at most 65535");
     const int C = check_samples, stride = steps / (C - 1);
     const long NR = (long)W * S;
-    if (int rc = tracked_reserve(p, NR * C)) return rc;
-    if (int rc = track_upload_launch(p, W, traj, S, scale, err0, t0, t1, steps, p->tm_rec, stride)) return rc;
+    TrueArmCheck& k = p->tracked;
+    if (int rc = k.reserve(p->stream, NR * C, p->Wmax)) return rc;
+    if (int rc = track_upload_launch(p, W, traj, S, scale, err0, t0, t1, steps, k.rec, stride)) return rc;
     if (int rc = launch_state_check(p, S, C, nullptr)) return rc;
     if (int rc = track_copy_out(p, NR, &out->track)) return rc;
     const size_t n = (size_t)NR;
-    if (out->clearance) HIPCK(hipMemcpyAsync(out->clearance, p->tm_clear, sizeof(double) * n, hipMemcpyDeviceToHost, p->stream));
-    if (out->where) HIPCK(hipMemcpyAsync(out->where, p->tm_where, sizeof(int) * 3 * n, hipMemcpyDeviceToHost, p->stream));
-    if (out->flags) HIPCK(hipMemcpyAsync(out->flags, p->tm_flags, sizeof(int) * n, hipMemcpyDeviceToHost, p->stream));
+    if (out->clearance) HIPCK(hipMemcpyAsync(out->clearance, k.clear, sizeof(double) * n, hipMemcpyDeviceToHost, p->stream));
+    if (out->where) HIPCK(hipMemcpyAsync(out->where, k.where, sizeof(int) * 3 * n, hipMemcpyDeviceToHost, p->stream));
+    if (out->flags) HIPCK(hipMemcpyAsync(out->flags, k.flags, sizeof(int) * n, hipMemcpyDeviceToHost, p->stream));
     if (out->world_clearance)
-        HIPCK(hipMemcpyAsync(out->world_clearance, p->tm_wclear, sizeof(double) * W, hipMemcpyDeviceToHost, p->stream));
-    if (out->world_where) HIPCK(hipMemcpyAsync(out->world_where, p->tm_wwhere, sizeof(int) * 4 * W, hipMemcpyDeviceToHost, p->stream));
+        HIPCK(hipMemcpyAsync(out->world_clearance, k.wclear, sizeof(double) * W, hipMemcpyDeviceToHost, p->stream));
+    if (out->world_where) HIPCK(hipMemcpyAsync(out->world_where, k.wwhere, sizeof(int) * 4 * W, hipMemcpyDeviceToHost, p->stream));
     HIPCK(hipStreamSynchronize(p->stream));
-    float ms = 0.f;
-    HIPCK(hipEventElapsedTime(&ms, p->tr_ev[0], p->tr_ev[1]));
-    out->track.track_ms = ms;
-    HIPCK(hipEventElapsedTime(&ms, p->tm_ev[0], p->tm_ev[1]));
-    out->check_ms = ms;
-    return 0;
+    if (int rc = elapsed_ms(p->track.ev[0], p->track.ev[1], &out->track.track_ms)) return rc;
+    return elapsed_ms(k.ev[0], k.ev[1], &out->check_ms);
 }
 
 static int episode_read(armour_planner* p) {
-    p->ep_host.resize(p->W);
-    HIPCK(hipMemcpyAsync(p->ep_host.data(), p->ep.st, sizeof(armour_episode_state) * p->W, hipMemcpyDeviceToHost, p->stream));
+    p->ep.host.resize(p->W);
+    HIPCK(hipMemcpyAsync(p->ep.host.data(), p->ep.dev.st, sizeof(armour_episode_state) * p->W, hipMemcpyDeviceToHost, p->stream));
     HIPCK(hipStreamSynchronize(p->stream));
     return 0;
 }
@@ -2180,13 +2211,12 @@ int armour_episode_begin(armour_planner* p, int W, const armour_world* worlds, c
                          const armour_episode_config* cfg) {
     DeviceScope device_scope(p);
     if (!p || !worlds || !goals || !cfg) return fail(ARMOUR_E_ARG, "null argument");
-    if (p->armtd) return fail(ARMOUR_E_ARG, "episodes are not available on an ARMTD planner");
-    if (p->set.eval_f32) return fail(ARMOUR_E_ARG, "episodes are not available with the fp32 study (ARMOUR_EVAL_F32)");
+    if (int rc = not_available(p, "episodes are")) return rc;
     if (!(cfg->lookahead > 0.0) || !std::isfinite(cfg->lookahead) || !(cfg->goal_radius >= 0.0) ||
         !std::isfinite(cfg->goal_radius) || cfg->check_samples < 2 || cfg->check_samples > 65535)
         return fail(ARMOUR_E_ARG, "episode config: lookahead > 0, goal_radius >= 0, 2 <= check_samples <= 65535");
     if (W <= 0 || W > p->Wmax) return fail(ARMOUR_E_ARG, "num_worlds out of range");
-    p->reached = p->planned = p->evaluated = p->episode = false;
+    p->reached = p->planned = p->evaluated = p->ep.on = false;
     int rc = 0;
     if ((rc = check_values("goals", goals, W * NF, ARMOUR_MAX_ABS_ANGLE))) return rc;
     // the worlds' q_des is ignored: the waypoints are written on the device
@@ -2194,59 +2224,49 @@ int armour_episode_begin(armour_planner* p, int W, const armour_world* worlds, c
     for (armour_world& w : ws) std::memcpy(w.q_des, w.q0, sizeof(w.q_des));
     if ((rc = upload_worlds(p, W, ws.data(), true))) return rc;
     if ((rc = motion_reserve(p, cfg->check_samples))) return rc;
-    EpisodeDev& e = p->ep;
+    EpisodeDev& e = p->ep.dev;
     if (!e.st) {
         double* goal = nullptr;
-        int* accept = nullptr;
         const size_t Wm = (size_t)p->Wmax;
         if ((rc = p->alloc(&e.st, Wm)) || (rc = p->alloc(&goal, Wm * NF)) || (rc = p->alloc(&e.pend, Wm * TRAJ_DOUBLES)) ||
             (rc = p->alloc(&e.has_pend, Wm)) || (rc = p->alloc(&e.kind, Wm)) || (rc = p->alloc(&e.exec, Wm * TRAJ_DOUBLES)) ||
-            (rc = p->alloc(&e.win, 2 * Wm)) || (rc = p->alloc(&accept, Wm)))
+            (rc = p->alloc(&e.win, 2 * Wm)) || (rc = p->alloc(&p->ep.accept, Wm)) || (rc = p->ep.events(4)))
             return rc;
         e.goal = goal;
-        p->ep_accept = accept;
-        e.accept = accept;
-        for (hipEvent_t& ev : p->ep_ev) HIPCK(hipEventCreate(&ev));
+        e.accept = p->ep.accept;
     }
     e.rp = p->d_rp;
     e.W = W;
     e.S = cfg->check_samples;
     e.lookahead = cfg->lookahead;
     e.goal_radius = cfg->goal_radius;
-    e.clearance = p->mo_clear;
-    e.where = p->mo_where;
+    e.clearance = p->motion.clear;
+    e.where = p->motion.where;
     HIPCK(hipMemcpyAsync(const_cast<double*>(e.goal), goals, sizeof(double) * W * NF, hipMemcpyHostToDevice, p->stream));
     hipLaunchKernelGGL(episode_begin_kernel, dim3((W + 63) / 64), dim3(64), 0, p->stream, e, p->q0, p->qd0, p->qdd0);
     HIPCK(hipGetLastError());
     if ((rc = episode_read(p))) return rc;  // (also: `goals` is the caller's, its copy has finished)
-    p->episode = true;
-    p->ep_track_on = p->ep_stepped = false;
+    p->ep.on = true;
+    p->ept.on = p->ep.stepped = false;
     return 0;
 }
 
 int armour_episode_track(armour_planner* p, const armour_episode_track_config* cfg) {
     DeviceScope device_scope(p);
     if (!p || !cfg) return fail(ARMOUR_E_ARG, "null argument");
-    if (!p->episode) return fail(ARMOUR_E_STATE, "no episode: call armour_episode_begin first (any other reach or plan entry ends one)");
-    if (p->ep_stepped) return fail(ARMOUR_E_STATE, "the episode has taken a step: tracking is enabled before the first step");
-    const int W = p->W, S = cfg->num_samples, NJ = p->NJ, C = p->ep.S;
+    if (!p->ep.on) return no_episode();
+    if (p->ep.stepped) return fail(ARMOUR_E_STATE, "the episode has taken a step: tracking is enabled before the first step");
+    const int W = p->W, S = cfg->num_samples, NJ = p->NJ, C = p->ep.dev.S;
     if (S < 1 || S > 65535) return fail(ARMOUR_E_ARG, "num_samples must lie in 1 .. 65535");
     if ((long)W * S > ARMOUR_TRACK_MAX_ROLLOUTS) return fail(ARMOUR_E_ARG, "num_worlds x num_samples exceeds ARMOUR_TRACK_MAX_ROLLOUTS");
     if (cfg->steps < 1 || cfg->steps > ARMOUR_TRACK_MAX_STEPS) return fail(ARMOUR_E_ARG, "steps must lie in 1 .. ARMOUR_TRACK_MAX_STEPS");
     if (cfg->steps % (C - 1) != 0) return fail(ARMOUR_E_ARG, "steps must be a multiple of the episode's check_samples - 1");
     const size_t NR = (size_t)W * S;
-    if (cfg->scale)
-        for (size_t i = 0; i < NR * 2 * NJ; i++) {
-            if (!std::isfinite(cfg->scale[i])) return fail(ARMOUR_E_ARG, "scale holds a value that is not finite");
-            if (!(cfg->scale[i] > 0)) return fail(ARMOUR_E_ARG, "every scale must be positive");
-        }
-    if (cfg->err0)
-        for (size_t i = 0; i < NR * 2 * NF; i++)
-            if (!std::isfinite(cfg->err0[i])) return fail(ARMOUR_E_ARG, "err0 holds a value that is not finite");
+    if (int rc = check_scale_err0(cfg->scale, cfg->err0, NR, NJ)) return rc;
     // the true arms start from the episode's start states plus err0
     std::vector<double> start(NR * 2 * NF);
     for (size_t r = 0; r < NR; r++) {
-        const armour_episode_state& st = p->ep_host[r / S];
+        const armour_episode_state& st = p->ep.host[r / S];
         for (int j = 0; j < NF; j++) {
             const double* e0 = cfg->err0 ? cfg->err0 + r * 2 * NF : nullptr;
             start[r * 2 * NF + j] = e0 ? st.q[j] + e0[j] : st.q[j];
@@ -2255,55 +2275,56 @@ int armour_episode_track(armour_planner* p, const armour_episode_track_config* c
                 return fail(ARMOUR_E_ARG, "err0 leads to a start state that is not finite");
         }
     }
-    EpisodeTrackDev& t = p->ept;
+    TrackedEpisode& te = p->ept;
+    EpisodeTrackDev& t = te.dev;
     const size_t n = (size_t)p->Wmax * S, Wm = (size_t)p->Wmax;
-    if (int rc = p->ep_tracked.reserve(p->stream, (long)n,
-                                       {GrowSet::buf(p->ept_state, n * 2 * NF), GrowSet::buf(p->ept_scale, n * 2 * MAX_J),
-                                        GrowSet::buf(t.flags, n), GrowSet::buf(t.traj, Wm * TRAJ_DOUBLES), GrowSet::buf(t.win, Wm * 2),
-                                        GrowSet::buf(t.rec, Wm)},
-                                       "hipMalloc failed for the tracked episode's buffers (max_worlds x num_samples)"))
+    if (int rc = te.grow.reserve(p->stream, (long)n,
+                                 {GrowSet::buf(te.state, n * 2 * NF), GrowSet::buf(te.scale, n * 2 * MAX_J), GrowSet::buf(t.flags, n),
+                                  GrowSet::buf(t.traj, Wm * TRAJ_DOUBLES), GrowSet::buf(t.win, Wm * 2), GrowSet::buf(t.rec, Wm)},
+                                 "hipMalloc failed for the tracked episode's buffers (max_worlds x num_samples)"))
         return rc;
-    if (int rc = track_reserve(p, (long)NR)) return rc;
-    if (int rc = tracked_reserve(p, (long)NR * C)) return rc;
+    if (int rc = p->track.reserve(p->stream, (long)NR)) return rc;
+    if (int rc = p->tracked.reserve(p->stream, (long)NR * C, p->Wmax)) return rc;
     t.S = S;
     t.stop_input = cfg->stop_on_input != 0;
     t.stop_bound = cfg->stop_on_bound != 0;
     t.stop_limit = cfg->stop_on_limit != 0;
-    p->ept_steps = cfg->steps;
-    p->ept_scaled = cfg->scale != nullptr;
-    HIPCK(hipMemcpyAsync(p->ept_state, start.data(), sizeof(double) * NR * 2 * NF, hipMemcpyHostToDevice, p->stream));
-    if (cfg->scale) HIPCK(hipMemcpyAsync(p->ept_scale, cfg->scale, sizeof(double) * NR * 2 * NJ, hipMemcpyHostToDevice, p->stream));
-    hipLaunchKernelGGL(episode_track_begin_kernel, dim3((W + 63) / 64), dim3(64), 0, p->stream, p->ep, t);
+    te.steps = cfg->steps;
+    te.scaled = cfg->scale != nullptr;
+    HIPCK(hipMemcpyAsync(te.state, start.data(), sizeof(double) * NR * 2 * NF, hipMemcpyHostToDevice, p->stream));
+    if (cfg->scale) HIPCK(hipMemcpyAsync(te.scale, cfg->scale, sizeof(double) * NR * 2 * NJ, hipMemcpyHostToDevice, p->stream));
+    hipLaunchKernelGGL(episode_track_begin_kernel, dim3((W + 63) / 64), dim3(64), 0, p->stream, p->ep.dev, t);
     HIPCK(hipGetLastError());
     HIPCK(hipStreamSynchronize(p->stream));  // (`start` and the caller's arrays outlive their copies)
-    p->ep_track_on = true;
+    te.on = true;
     return 0;
 }
 
 // step (c) of a tracked episode, after episode_advance_kernel: the true arms along what each running
 // world executes, the check of their recorded states, and the fold into the records and the status
 static int episode_track_step(armour_planner* p) {
-    const int W = p->W, C = p->ep.S;
-    EpisodeTrackDev& t = p->ept;
+    const int W = p->W, C = p->ep.dev.S;
+    const TrackedEpisode& te = p->ept;
+    EpisodeTrackDev& t = p->ept.dev;
     const long NR = (long)W * t.S;
     // (another tracking entry between two steps may have regrown these; their contents live one step)
-    if (int rc = track_reserve(p, NR)) return rc;
-    if (int rc = tracked_reserve(p, NR * C)) return rc;
-    t.out = p->tr_out;
-    t.rflags = p->tm_flags;
-    t.wclear = p->tm_wclear;
-    t.wwhere = p->tm_wwhere;
+    if (int rc = p->track.reserve(p->stream, NR)) return rc;
+    if (int rc = p->tracked.reserve(p->stream, NR * C, p->Wmax)) return rc;
+    t.out = p->track.out;
+    t.rflags = p->tracked.flags;
+    t.wclear = p->tracked.wclear;
+    t.wwhere = p->tracked.wwhere;
     const dim3 wg((W + 63) / 64), wb(64);
-    hipLaunchKernelGGL(episode_track_choose_kernel, wg, wb, 0, p->stream, p->ep, t);
+    hipLaunchKernelGGL(episode_track_choose_kernel, wg, wb, 0, p->stream, p->ep.dev, t);
     TrackArgs a{};
     a.N = W;
     a.S = t.S;
     a.traj = t.traj;
-    a.scale = p->ept_scaled ? p->ept_scale : nullptr;
-    a.steps = p->ept_steps;
-    if (int rc = track_launch(p, a, TrackExtra{p->tm_rec, p->ept_steps / (C - 1), t.win, p->ept_state})) return rc;
+    a.scale = te.scaled ? te.scale : nullptr;
+    a.steps = te.steps;
+    if (int rc = track_launch(p, a, TrackExtra{p->tracked.rec, te.steps / (C - 1), t.win, te.state})) return rc;
     if (int rc = launch_state_check(p, t.S, C, t.win)) return rc;
-    hipLaunchKernelGGL(episode_track_fold_kernel, wg, wb, 0, p->stream, p->ep, t);
+    hipLaunchKernelGGL(episode_track_fold_kernel, wg, wb, 0, p->stream, p->ep.dev, t);
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -2311,21 +2332,20 @@ static int episode_track_step(armour_planner* p) {
 int armour_episode_get_tracked(armour_planner* p, armour_episode_tracked* records, double* true_state, int* flags, double* ms) {
     DeviceScope device_scope(p);
     if (!p || !records) return fail(ARMOUR_E_ARG, "null argument");
-    if (!p->episode) return fail(ARMOUR_E_STATE, "no episode: call armour_episode_begin first (any other reach or plan entry ends one)");
-    if (!p->ep_track_on) return fail(ARMOUR_E_STATE, "tracking is not enabled: call armour_episode_track after armour_episode_begin");
-    const size_t W = (size_t)p->W, NR = W * p->ept.S;
-    HIPCK(hipMemcpyAsync(records, p->ept.rec, sizeof(armour_episode_tracked) * W, hipMemcpyDeviceToHost, p->stream));
-    if (true_state) HIPCK(hipMemcpyAsync(true_state, p->ept_state, sizeof(double) * NR * 2 * NF, hipMemcpyDeviceToHost, p->stream));
-    if (flags) HIPCK(hipMemcpyAsync(flags, p->ept.flags, sizeof(int) * NR, hipMemcpyDeviceToHost, p->stream));
+    if (!p->ep.on) return no_episode();
+    if (!p->ept.on) return fail(ARMOUR_E_STATE, "tracking is not enabled: call armour_episode_track after armour_episode_begin");
+    const EpisodeTrackDev& t = p->ept.dev;
+    const size_t W = (size_t)p->W, NR = W * t.S;
+    HIPCK(hipMemcpyAsync(records, t.rec, sizeof(armour_episode_tracked) * W, hipMemcpyDeviceToHost, p->stream));
+    if (true_state) HIPCK(hipMemcpyAsync(true_state, p->ept.state, sizeof(double) * NR * 2 * NF, hipMemcpyDeviceToHost, p->stream));
+    if (flags) HIPCK(hipMemcpyAsync(flags, t.flags, sizeof(int) * NR, hipMemcpyDeviceToHost, p->stream));
     HIPCK(hipStreamSynchronize(p->stream));
     if (ms) {
-        float a = 0, b = 0;
-        if (p->ep_stepped) {
-            (void)hipEventElapsedTime(&a, p->tr_ev[0], p->tr_ev[1]);
-            (void)hipEventElapsedTime(&b, p->tm_ev[0], p->tm_ev[1]);
+        ms[0] = ms[1] = 0.0;  // (before the first step; a failed read leaves 0 too)
+        if (p->ep.stepped) {
+            (void)elapsed_ms(p->track.ev[0], p->track.ev[1], &ms[0]);
+            (void)elapsed_ms(p->tracked.ev[0], p->tracked.ev[1], &ms[1]);
         }
-        ms[0] = a;
-        ms[1] = b;
     }
     return 0;
 }
@@ -2334,9 +2354,10 @@ int armour_episode_step(armour_planner* p, const int* reject, armour_result* res
                         double* episode_ms) {
     DeviceScope device_scope(p);
     if (!p) return fail(ARMOUR_E_ARG, "null planner");
-    if (!p->episode) return fail(ARMOUR_E_STATE, "no episode: call armour_episode_begin first (any other reach or plan entry ends one)");
+    if (!p->ep.on) return no_episode();
     const int W = p->W;
-    const EpisodeDev& e = p->ep;
+    const EpisodeDev& e = p->ep.dev;
+    const hipEvent_t* ev = p->ep.ev;
     int rc = 0;
     auto t0 = std::chrono::steady_clock::now();
     // (a) the pending state becomes the batch input; reach and solve on the resident arrays
@@ -2351,43 +2372,43 @@ int armour_episode_step(armour_planner* p, const int* reject, armour_result* res
         results = own.data();
     }
     if ((rc = plan_uploaded(p, results, timing, t0))) {
-        p->episode = false;
+        p->ep.on = false;
         return rc;
     }
     // (b) what each running world executes; (c) check, advance
     std::vector<int> accept(W);
     for (int w = 0; w < W; w++) accept[w] = results[w].feasible && !(reject && reject[w]) ? 1 : 0;
-    HIPCK(hipMemcpyAsync(p->ep_accept, accept.data(), sizeof(int) * W, hipMemcpyHostToDevice, p->stream));
+    HIPCK(hipMemcpyAsync(p->ep.accept, accept.data(), sizeof(int) * W, hipMemcpyHostToDevice, p->stream));
     const dim3 wg((W + 63) / 64), wb(64);
-    HIPCK(hipEventRecord(p->ep_ev[0], p->stream));
+    HIPCK(hipEventRecord(ev[0], p->stream));
     hipLaunchKernelGGL(episode_choose_kernel, wg, wb, 0, p->stream, e, (const double*)p->d.ws,
                        (long)(sizeof(WorldState) / sizeof(double)), p->q0, p->qd0, p->qdd0);
-    HIPCK(hipEventRecord(p->ep_ev[1], p->stream));
+    HIPCK(hipEventRecord(ev[1], p->stream));
     launch_motion(p, e.exec, e.win, 0.0, 0.0, e.S);
-    HIPCK(hipEventRecord(p->ep_ev[2], p->stream));
+    HIPCK(hipEventRecord(ev[2], p->stream));
     hipLaunchKernelGGL(episode_advance_kernel, wg, wb, 0, p->stream, e);
-    HIPCK(hipEventRecord(p->ep_ev[3], p->stream));
+    HIPCK(hipEventRecord(ev[3], p->stream));
     HIPCK(hipGetLastError());
-    p->ep_stepped = true;
-    if (p->ep_track_on && (rc = episode_track_step(p))) return rc;
+    p->ep.stepped = true;
+    if (p->ept.on && (rc = episode_track_step(p))) return rc;
     if ((rc = episode_read(p))) return rc;  // (ends in a synchronisation: `accept` outlives its copy)
     if (episode_ms) {
-        float a = 0, b = 0, c = 0;
-        (void)hipEventElapsedTime(&a, p->ep_ev[0], p->ep_ev[1]);
-        (void)hipEventElapsedTime(&b, p->ep_ev[1], p->ep_ev[2]);
-        (void)hipEventElapsedTime(&c, p->ep_ev[2], p->ep_ev[3]);
+        double a = 0, b = 0, c = 0;  // (a failed read leaves 0)
+        (void)elapsed_ms(ev[0], ev[1], &a);
+        (void)elapsed_ms(ev[1], ev[2], &b);
+        (void)elapsed_ms(ev[2], ev[3], &c);
         episode_ms[0] = b;
-        episode_ms[1] = (double)a + c;
+        episode_ms[1] = a + c;
     }
     int running = 0;
-    for (const armour_episode_state& s : p->ep_host) running += s.status == 0;
+    for (const armour_episode_state& s : p->ep.host) running += s.status == 0;
     return running;
 }
 
 int armour_episode_get(armour_planner* p, armour_episode_state* states) {
     if (!p || !states) return fail(ARMOUR_E_ARG, "null argument");
-    if (!p->episode) return fail(ARMOUR_E_STATE, "no episode: call armour_episode_begin first (any other reach or plan entry ends one)");
-    std::memcpy(states, p->ep_host.data(), sizeof(armour_episode_state) * p->ep_host.size());
+    if (!p->ep.on) return no_episode();
+    std::memcpy(states, p->ep.host.data(), sizeof(armour_episode_state) * p->ep.host.size());
     return 0;
 }
 

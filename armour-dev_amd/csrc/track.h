@@ -27,7 +27,18 @@ namespace armour {
 constexpr int TRACK_ROLES = 10;                  // 7 columns of M, b, tau (+ rho), Mr (+ rMr)
 constexpr int TRACK_ROLE_B = NF, TRACK_ROLE_TAU = NF + 1, TRACK_ROLE_MR = NF + 2;
 constexpr int TRACK_GATHER = 2 * NF;             // per role: u[7], radius[7]
-constexpr int TRACK_OUT_DOUBLES = 3 * NF + 2 + 2 * NF;  // per rollout: three maxima [7], V, lambda, end state
+// The rollouts' outputs, out [TRACK_OUT_DOUBLES][NR] by field: max_pos_err, max_vel_err, max_torque
+// [NR][NF], max_V, max_robust [NR], end_state [NR][2][NF]. Index of rollout i's element of each field
+// (the whole index in the function: with `+ j` left to the caller the tracking kernels' address
+// arithmetic came out differently, profiles/exec_layer_resources.txt):
+constexpr int TRACK_MAX_POS = 0, TRACK_MAX_VEL = 1, TRACK_MAX_TORQUE = 2;  // the three maxima, joint j
+AD constexpr long track_out_max(int which, long NR, long i, int j) { return (which * NR + i) * NF + j; }
+AD constexpr long track_out_V(long NR, long i) { return 3 * NF * NR + i; }
+AD constexpr long track_out_robust(long NR, long i) { return (3 * NF + 1) * NR + i; }
+// end state: half 0 is q, half 1 is qd
+AD constexpr long track_out_end(long NR, long i, int half, int j) { return (3 * NF + 2) * NR + i * 2 * NF + half * NF + j; }
+constexpr int TRACK_OUT_DOUBLES = 3 * NF + 2 + 2 * NF;  // per rollout: three maxima [NF], V, lambda, end state
+static_assert(track_out_end(1, 1, 0, 0) == TRACK_OUT_DOUBLES, "the last field of one rollout ends where the array does");
 
 // finite: neither NaN nor infinite (written with a comparison: host + device)
 AD bool track_finite(double x) { return fabs(x) < INFINITY; }
@@ -193,8 +204,7 @@ struct TrackPre {
 AD void track_pre(const RobotParams& rp, const double* traj, double t, const double* q, const double* qd, TrackPre& P) {
     for (int j = 0; j < NF; j++) {
         double qdd_des;
-        bezier_joint(traj[j], traj[NF + j], traj[2 * NF + j], traj[3 * NF + j] * rp.k_range[j], t, P.q_des[j], P.qd_des[j],
-                     qdd_des);
+        traj_joint(rp, traj, j, t, P.q_des[j], P.qd_des[j], qdd_des);
         double e = P.q_des[j] - q[j];
         if (rp.state_lb[j] <= -1000.0) e = wrap_diff(e);  // a continuous joint: one remainder, no loop
         const double de = P.qd_des[j] - qd[j];
@@ -304,7 +314,7 @@ AD void track_init(const RobotParams& rp, const double* traj, const double* err0
     bool ok = true;
     for (int j = 0; j < NF; j++) {
         double q, qd, qdd;
-        bezier_joint(traj[j], traj[NF + j], traj[2 * NF + j], traj[3 * NF + j] * rp.k_range[j], t0, q, qd, qdd);
+        traj_joint(rp, traj, j, t0, q, qd, qdd);
         X.q[j] = err0 ? q + err0[j] : q;
         X.qd[j] = err0 ? qd + err0[NF + j] : qd;
         if (!(track_finite(X.q[j]) && track_finite(X.qd[j]))) {
@@ -478,18 +488,17 @@ AD void track_rollout_serial(const RobotParams& rp, const double* traj, const do
     track_run(ev, t0, t1, steps, X);
 }
 
-// the per-rollout outputs as the kernels store them: out [TRACK_OUT_DOUBLES][NR] by field
-// (max_pos_err, max_vel_err, max_torque [NR][7]; max_V, max_robust [NR]; end_state [NR][2][7])
+// the per-rollout outputs as the kernels store them (the layout at the top)
 AD void track_store(const TrackState& X, long i, long NR, double* out, int* status) {
     for (int j = 0; j < NF; j++) {
-        out[i * NF + j] = X.max_pos_err[j];
-        out[(NR + i) * NF + j] = X.max_vel_err[j];
-        out[(2 * NR + i) * NF + j] = X.max_torque[j];
-        out[23 * NR + i * 2 * NF + j] = X.q[j];
-        out[23 * NR + i * 2 * NF + NF + j] = X.qd[j];
+        out[track_out_max(TRACK_MAX_POS, NR, i, j)] = X.max_pos_err[j];
+        out[track_out_max(TRACK_MAX_VEL, NR, i, j)] = X.max_vel_err[j];
+        out[track_out_max(TRACK_MAX_TORQUE, NR, i, j)] = X.max_torque[j];
+        out[track_out_end(NR, i, 0, j)] = X.q[j];
+        out[track_out_end(NR, i, 1, j)] = X.qd[j];
     }
-    out[21 * NR + i] = X.max_V;
-    out[22 * NR + i] = X.max_robust;
+    out[track_out_V(NR, i)] = X.max_V;
+    out[track_out_robust(NR, i)] = X.max_robust;
     status[i] = X.status;
 }
 

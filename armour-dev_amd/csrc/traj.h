@@ -11,9 +11,13 @@ namespace armour {
 
 constexpr int TRAJ_DOUBLES = 4 * NF;     // q0, qd0, qdd0, k (normalised)
 
-// position, velocity and acceleration of one joint on the Bezier curve at s in [0, 1], from the
-// Bernstein form (at s = 1 the velocity and the acceleration are exactly 0 and q is exactly q0 + k)
-AD void bezier_joint(double q0, double qd0, double qdd0, double k, double s, double& q, double& qd, double& qdd) {
+// position, velocity and acceleration of joint j of the trajectory traj [4][NF] (q0, qd0, qdd0, then k
+// normalised to [-1, 1], scaled here by the robot's k_range: the one place that knows this layout) on the
+// Bezier curve at s in [0, 1], from the Bernstein form (at s = 1 the velocity and the acceleration are
+// exactly 0 and q is exactly q0 + k). One function, not a wrapper of a scalar one: behind a wrapper the
+// tracking kernels' sums came out with commuted operands (profiles/exec_layer_resources.txt).
+AD void traj_joint(const RobotParams& rp, const double* traj, int j, double s, double& q, double& qd, double& qdd) {
+    const double q0 = traj[j], qd0 = traj[NF + j], qdd0 = traj[2 * NF + j], k = traj[3 * NF + j] * rp.k_range[j];
     const double b[6] = {q0, q0 + qd0 / 5, q0 + 2 * qd0 / 5 + qdd0 / 20, q0 + k, q0 + k, q0 + k};
     double d1[5], d2[4], ps[6], pr[6];
     for (int i = 0; i < 5; i++) d1[i] = 5 * (b[i + 1] - b[i]);

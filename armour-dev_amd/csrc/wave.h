@@ -90,6 +90,11 @@ WAVE_FN double wave_sum(double v) {
     for (int m = 1; m < 64; m <<= 1) v = v + xor_f64(v, m);
     return v;
 }
+WAVE_FN int wave_or(int v) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v |= xor_i32(v, m);
+    return v;
+}
 WAVE_FN int wave_max(int v) {
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) v = max(v, xor_i32(v, m));

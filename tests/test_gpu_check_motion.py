@@ -137,6 +137,37 @@ def test_samples_chunking(batch):
             assert np.all(singles[first[w]][1][w] == [0, where[w, 1], where[w, 2]])
 
 
+@pytest.mark.parametrize("samples", [64, 65, 130])
+def test_samples_chunking_past_one_wave(batch, samples):
+    """the same identity with a full wave of samples, one more, and a third trip of the finish kernel's
+    lane-strided loop: clearance and first minimiser are those of the single-sample calls, exactly"""
+    P = batch["P"]
+    traj = np.array([np.stack(t) for t in batch["trajs"]["moving"]])
+    clear, where = P.check_motion(traj, 0.0, 1.0, samples)
+    singles = [P.check_motion(traj, t, t, 1) for t in E.sample_times(0.0, 1.0, samples)]
+    cs = np.array([c for c, _ in singles])                 # [S, W]
+    first = np.argmin(cs, axis=0)
+    print(samples, "first minimisers", first.tolist())
+    np.testing.assert_array_equal(clear, cs.min(axis=0))
+    np.testing.assert_array_equal(where[:, 0], first)
+    for w in range(len(clear)):
+        assert np.all(singles[first[w]][1][w] == [0, where[w, 1], where[w, 2]])
+
+
+def test_a_trajectory_at_rest_ties_in_every_sample(batch):
+    """qd0 = qdd0 = 0 and k = 0 at q0 = 0: all 130 samples are the same configuration bit for bit, a tie
+    across the lanes and the trips of the finish kernel, which the lowest sample wins. (At another q0 the
+    Bernstein sum of six equal control points rounds differently from sample to sample; at 0 every term
+    is 0, so the tie is exact.)"""
+    P = batch["P"]
+    traj = np.zeros((len(batch["worlds"]), 4, 7))
+    clear, where = P.check_motion(traj, 0.0, 1.0, 130)
+    one, where1 = P.check_motion(traj, 0.0, 0.0, 1)
+    assert np.all(where[:, 0] == 0)
+    np.testing.assert_array_equal(clear, one)
+    np.testing.assert_array_equal(where, where1)
+
+
 def test_state_is_undisturbed(batch):
     """the getters and the next plan are bitwise what they were"""
     P, worlds = batch["P"], batch["worlds"]

@@ -120,6 +120,29 @@ def test_parity_with_the_model(robot, shape):
     print(robot, shape, " ".join(f"{k} {v:.2e}" for k, v in worst.items()))
 
 
+def test_parity_with_more_check_points_than_lanes():
+    """tracked_cases' long record: 65 and 129 check points, the second and third trip of the finish kernel's
+    lane-strided loop over them (its minimisers lie at check points 79 .. 81 of 129), with the tolerances and
+    the admission of the list (tests/test_tracked_model.py asserts the latter for this case)"""
+    tb, traj, scale, err0, obs = KC.long_inputs()
+    t0, t1 = KC.LONG_WINDOW
+    P = planner("kinova", 2)
+    P.reach_mixed(KC.worlds(traj, obs))
+    plain = P.track(traj, scale, err0, t0, t1, KC.LONG_STEPS)
+    worst, got = {}, {}
+    for C in KC.LONG_CHECKS:
+        got[C] = P.track_motion(traj, scale, err0, t0, t1, KC.LONG_STEPS, C)
+        same(got[C], plain, TC.FIELDS + ("status",))       # the rollouts are armour_track's, bit for bit
+        compare(("long", C), got[C], KC.long_reference(C), worst)
+    print("long record", " ".join(f"{k} {v:.2e}" for k, v in worst.items()), "where", got[129]["where"].reshape(-1, 3).tolist())
+    half, full = got[65], got[129]
+    # the even check points of 129 are the 65: a minimiser found among them is the same record, bit for bit
+    even = full["where"][..., 0] % 2 == 0
+    assert np.array_equal(full["where"][..., 0][even], 2 * half["where"][..., 0][even])
+    assert full["clearance"][even].tobytes() == half["clearance"][even].tobytes()
+    assert np.all(full["clearance"] <= half["clearance"])
+
+
 # ---- bitwise agreement and independence -------------------------------------------------------------
 @pytest.mark.parametrize("shape", KC.SHAPES)
 def test_row_kernel_is_bitwise_the_serial_kernel_and_reruns(shape):

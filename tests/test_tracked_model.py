@@ -92,6 +92,19 @@ def test_the_list_sits_clear_of_every_threshold(robot):
                 assert np.all((ref["world_where"] >= 0).all(axis=1) == (counts > 0))
 
 
+def test_the_long_record_sits_clear_of_every_threshold():
+    """the case with more check points than a wave has lanes meets the list's conditions, and its 65 check
+    points are the even ones of its 129"""
+    full, half = (KC.long_reference(C) for C in reversed(KC.LONG_CHECKS))
+    for C, ref in zip(reversed(KC.LONG_CHECKS), (full, half)):
+        assert ref["rec"].shape[0] == C and not ref["status"].any()
+        check_case(("long", C), ref)
+        assert np.all(np.isfinite(ref["clearance"]))
+    assert np.array_equal(full["rec"][::2], half["rec"])
+    # some minimiser lies past the first trip of a lane-strided loop over the check points
+    assert full["where"][..., 0].max() >= 64 or half["where"][..., 0].max() >= 64
+
+
 @pytest.mark.parametrize("name", KC.FLAG_CASES)
 def test_each_flag_case_raises_its_flag_and_only_where_it_should(name):
     case, ref = KC.flag_reference(name)

@@ -91,8 +91,9 @@ def chained_err0(traj, end_state):
 
 
 def subsample(robot, full, obs, C):
-    """the outputs for check_samples = C from a model run with 51 (the rollouts do not depend on C)"""
-    stride = (CHECKS[-1] - 1) // (C - 1)
+    """the outputs for check_samples = C from a model run with more (51 on the main list; the rollouts do
+    not depend on C)"""
+    stride = (full["rec"].shape[0] - 1) // (C - 1)
     W, S = full["status"].shape
     rec = full["rec"][::stride].reshape(C, W * S, 2, NF)
     flat = {k: full[k].reshape((W * S,) + full[k].shape[2:]) for k in TC.FIELDS + ("status",)}
@@ -136,6 +137,36 @@ def reference(robot, shape, window, C):
         tb, _, _, _, obs = case_inputs(robot, shape)
         _REF[key] = subsample(tb, _REF[(robot, shape)][window], obs, C)
     return _REF[key]
+
+
+# ---- the long record --------------------------------------------------------------------------------
+# More check points than a wave has lanes, so that the finish kernel's lane-strided loop takes a second
+# trip (65) and a third (129): two Kinova worlds with 3 and 1 obstacles, 2 samples, 128 steps on [0, 0.5].
+# The check points of 65 are the even ones of 129, so one model run serves both. The seed is fixed; the CPU
+# test asserts the list's conditions (a unique minimiser among them) for it.
+LONG_STEPS = 128
+LONG_CHECKS = (65, 129)
+LONG_WINDOW = (0.0, 0.5)
+LONG_SEED = 11
+
+
+def long_inputs():
+    """(tables, traj [2, 4, 7], scale [2, 2, 2, NJ], err0 [2, 2, 2, 7], obstacles with 3 and 1 boxes)"""
+    tb = TC.tables("kinova")
+    scale, err0 = TC.samples(tb, 2, 2, LONG_SEED)
+    obs = obstacles(3, LONG_SEED)
+    return tb, TC.trajectories(2, LONG_SEED), scale, err0, [obs[0], obs[2]]
+
+
+def long_reference(C):
+    """the model's outputs of the long record with C check points; the rollouts are computed once"""
+    if "long" not in _REF:
+        tb, traj, scale, err0, obs = long_inputs()
+        _REF["long"] = KM.track_motion(tb, traj, obs, scale, err0, LONG_WINDOW[0], LONG_WINDOW[1], LONG_STEPS, LONG_CHECKS[-1])
+    if ("long", C) not in _REF:
+        tb, _, _, _, obs = long_inputs()
+        _REF[("long", C)] = subsample(tb, _REF["long"], obs, C)
+    return _REF[("long", C)]
 
 
 # ---- flag cases -----------------------------------------------------------------------------------
