@@ -9,54 +9,13 @@
 //                       deterministic block partials and one wave per world for the 7x7 algebra
 //   feasible_kernel     finalize_solution's re-check (KPR/NLPclass.cu:449-538)
 #include "nlp.h"
+#include "block_reduce.h"
 
 namespace armour {
 
 // ------------------------------------------------------------------------------------------
 // helpers
-// wave_sum (wave.h): DPP / permlane butterfly
-__device__ inline double wave_max(double v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v = fmax(v, xor_f64(v, m));
-    return v;
-}
-__device__ inline double wave_min(double v) {
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v = fmin(v, xor_f64(v, m));
-    return v;
-}
-// N values at once, the arithmetic of N block_reduce calls (wave reduction, then the waves in
-// order) with one barrier: the N wave reductions are independent and interleave. kinds[i]: 0 sum,
-// 1 max, 2 min. out[i] written by thread i; lds holds (blockDim / 64) * N doubles.
-template <int N>
-__device__ inline void block_reduce_n(double (&v)[N], const int (&kinds)[N], double* lds, double* out) {
-    const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    // groups of 8 interleave; a scheduling barrier between groups bounds the live registers
-#pragma unroll
-    for (int g = 0; g < N; g += 8) {
-#pragma unroll
-        for (int i = g; i < (g + 8 < N ? g + 8 : N); i++)
-            v[i] = kinds[i] == 0 ? wave_sum(v[i]) : kinds[i] == 1 ? wave_max(v[i]) : wave_min(v[i]);
-        if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-            for (int i = g; i < (g + 8 < N ? g + 8 : N); i++) lds[wave * N + i] = v[i];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    __syncthreads();
-    const int i = threadIdx.x;
-    if (i < N) {
-        int kind = 0;
-#pragma unroll
-        for (int q = 0; q < N; q++) if (q == i) kind = kinds[q];
-        double s = lds[i];
-        for (int k = 1; k < nw; k++) {
-            const double t = lds[k * N + i];
-            s = kind == 0 ? s + t : kind == 1 ? fmax(s, t) : fmin(s, t);
-        }
-        out[i] = s;
-    }
-}
+// block_reduce_n, block_reduce_get: block_reduce.h
 
 // row bounds: a collision row's are the constants bounds_kernel stores (-1e19, 0), not re-read
 __device__ inline void row_bounds(const NlpDev& d, const Shape& sh, long i, int r, double& L, double& U) {
@@ -1596,11 +1555,13 @@ __device__ inline void reduce_A(const NlpDev& d, int w, AAcc& c, double* lds, co
     for (int j = 0; j < NF; j++) { v[j] = c.rdp[j]; v[39 + j] = c.u1[j]; v[46 + j] = c.u2[j]; }
     v[7] = c.inf_p; v[8] = c.compl0; v[9] = c.cm; v[10] = c.sumz;
 #pragma unroll
-    for (int k = 0; k < 28; k++) v[11 + k] = k < ML ? ml[k * ROW_THREADS] : c.M[k];
+    for (int k = ML; k < 28; k++) v[11 + k] = c.M[k];
     v[53] = c.sumc; v[54] = c.minc;
 #pragma unroll
     for (int k = 0; k < NA; k++) kinds[k] = (k >= 7 && k <= 9) ? 1 : k == 54 ? 2 : 0;
-    block_reduce_n(v, kinds, lds, out);
+    // an LDS-resident accumulator is read where the reduction consumes its pair, not before
+    block_reduce_get<NA>([&](int i) __attribute__((always_inline)) { return i >= 11 && i < 11 + ML ? ml[(i - 11) * ROW_THREADS] : v[i]; },
+                         kinds, lds, out);
 }
 // pass B's multiplier step of one side, dz = mu / s - z - (z / s) ds, exactly as ipm_rows_B forms
 // it: pass D forms it again from the same s, z, ds and mu (pass A's barrier update comes after D)

@@ -90,6 +90,97 @@ WAVE_FN double wave_sum(double v) {
     for (int m = 1; m < 64; m <<= 1) v = v + xor_f64(v, m);
     return v;
 }
+
+// Reduce-scatter sum of N doubles per lane (N <= 64, padded to the next power of two P): the
+// butterfly's tree, each node computed once. wave_sum has every lane compute every level of every
+// value; here, at xor step m, a lane keeps one half of its live values (the upper half where its
+// bit m is set), receives the partner's copies of those and adds them, so the live set halves per
+// step while the levels still run 1, 2, 4, ... Each node is own + partner where the butterfly had
+// own + partner on one lane and partner + own on the other: IEEE addition commutes, so every total
+// has wave_sum's bits (a NaN's payload aside). Once one value is left the remaining steps are the
+// butterfly's. Lane l ends with the total of index scatter_index(P, l).
+//   get(i)   value of slot i; called once, at the first step, with i a constant after unrolling
+//   live     bit i set: slot i is wanted. A pair whose two slots are both unwanted (or padding)
+//            costs nothing; a pair with one wanted slot is a plain butterfly step on it.
+// Everything unrolls to static register indices.
+constexpr int scatter_width(int n) {
+    int p = 1;
+    while (p < n) p <<= 1;
+    return p;
+}
+// the index whose total lane `lane` holds: step m kept the upper half (+h) where bit m is set; for
+// P = 64 the 6-bit reversal of the lane
+__host__ __device__ constexpr int scatter_index(int P, int lane) {
+    int idx = 0;
+    for (int m = 1, h = P >> 1; h >= 1; m <<= 1, h >>= 1)
+        if (lane & m) idx += h;
+    return idx;
+}
+// what lane ^ m sends: its x where this lane's bit m is clear, its y where it is set
+WAVE_FN uint32_t scatter_recv_u32(uint32_t x, uint32_t y, int m, bool b) {
+    switch (m) {
+        case 4: {  // bank masks pick the lanes by bit 2: one move per side, no select
+            const int t = __builtin_amdgcn_update_dpp(0, (int)x, 0x104, 0xF, 0x5, false);  // row_shl:4 into banks 0, 2
+            return (uint32_t)__builtin_amdgcn_update_dpp(t, (int)y, 0x114, 0xF, 0xA, false);  // row_shr:4 into banks 1, 3
+        }
+        case 8: {
+            const int t = __builtin_amdgcn_update_dpp(0, (int)x, 0x108, 0xF, 0x3, false);  // row_shl:8 into banks 0, 1
+            return (uint32_t)__builtin_amdgcn_update_dpp(t, (int)y, 0x118, 0xF, 0xC, false);  // row_shr:8 into banks 2, 3
+        }
+        default: return xor_u32(b ? x : y, m);  // every lane sends the half it does not keep
+    }
+}
+// one pair of a step: the node this lane keeps, own + partner
+WAVE_FN double scatter_pair(double x, double y, int m, bool b) {
+    const uint64_t xb = __builtin_bit_cast(uint64_t, x), yb = __builtin_bit_cast(uint64_t, y);
+    if (m >= 16) {
+        // the swap delivers both operands: {own x, partner's x} where bit m is clear,
+        // {partner's y, own y} where it is set
+        const auto lo = m == 16 ? __builtin_amdgcn_permlane16_swap((uint32_t)xb, (uint32_t)yb, false, false)
+                                : __builtin_amdgcn_permlane32_swap((uint32_t)xb, (uint32_t)yb, false, false);
+        const auto hi = m == 16 ? __builtin_amdgcn_permlane16_swap((uint32_t)(xb >> 32), (uint32_t)(yb >> 32), false, false)
+                                : __builtin_amdgcn_permlane32_swap((uint32_t)(xb >> 32), (uint32_t)(yb >> 32), false, false);
+        const uint64_t p = ((uint64_t)hi[0] << 32) | lo[0], q = ((uint64_t)hi[1] << 32) | lo[1];
+        return __builtin_bit_cast(double, p) + __builtin_bit_cast(double, q);
+    }
+    const uint64_t r = ((uint64_t)scatter_recv_u32((uint32_t)(xb >> 32), (uint32_t)(yb >> 32), m, b) << 32) |
+                       scatter_recv_u32((uint32_t)xb, (uint32_t)yb, m, b);
+    return (b ? y : x) + __builtin_bit_cast(double, r);
+}
+template <int N, class Get>
+WAVE_FN double scatter_sum(const Get& get, uint64_t live) {
+    static_assert(N >= 1 && N <= 64, "one wave's lanes hold the totals");
+    constexpr int P = scatter_width(N);
+    const int l = lane_id();
+    double v[P];
+    int m = 1;
+#pragma unroll
+    for (int h = P >> 1; h >= 1; h >>= 1, m <<= 1) {
+        const bool b = (l & m) != 0;
+#pragma unroll
+        for (int i = 0; i < h; i++) {
+            const bool la = (live >> i) & 1, lb = (live >> (i + h)) & 1;
+            if (!la && !lb) continue;
+            double x = 0, y = 0;
+            if (la) x = h == P >> 1 ? get(i) : v[i];
+            if (lb) y = h == P >> 1 ? get(i + h) : v[i + h];
+            if (la && lb) {
+                v[i] = scatter_pair(x, y, m, b);
+            } else {
+                const double t = la ? x : y;
+                v[i] = t + xor_f64(t, m);
+            }
+        }
+        live = (live | (live >> h)) & ((1ull << h) - 1);
+    }
+    double r;
+    if constexpr (P == 1) r = get(0);
+    else r = v[0];
+#pragma unroll
+    for (; m < 64; m <<= 1) r = r + xor_f64(r, m);
+    return r;
+}
+
 WAVE_FN int wave_or(int v) {
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) v |= xor_i32(v, m);
