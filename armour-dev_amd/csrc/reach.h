@@ -63,23 +63,34 @@ AD double bz_qdd(double q0, double Tqd0, double TTqdd0, double k, double t) {
     const double u = 1.0 - t;
     return 20 * (u * u * u * (b2 - 2 * b1 + b0) + 3 * t * u * u * (b3 - 2 * b2 + b1) + 3 * t * t * u * (b2 - b3));
 }
+// Interior critical points: the roots (p +- disc) / den of a quadratic whose leading coefficient den
+// vanishes on 6 Tqd0 + TTqdd0 = 12 k. There the quadratic is linear: big / den, big = p + sign(p) disc,
+// leaves [0, 1] through +-inf, and the other root's numerator p - sign(p) disc cancels to nothing over
+// a vanishing den. Once that numerator has cancelled (below 2^-16 |big|) the root is taken from the
+// product of the roots, (p^2 - disc^2) / (big den), whose numerator is den times prod exactly; outside
+// the guard both roots are the expressions they always were, bit for bit, in the same slots.
+AD void root_pair(double p, double disc, double den, double prod, double* r2, double* r3) {
+    const double hi = p + disc, lo = p - disc;
+    const bool pos = p >= 0;
+    const double big = pos ? hi : lo, sm = pos ? lo : hi;
+    const double rs = fabs(sm) < 0x1p-16 * fabs(big) ? prod / big : sm / den;
+    *r2 = pos ? hi / den : rs;
+    *r3 = pos ? rs : lo / den;
+}
 AD void q_roots(double Tqd0, double TTqdd0, double k, double* r2, double* r3) {
     const double disc = sqrt(64 * Tqd0 * Tqd0 + 14 * Tqd0 * TTqdd0 - 120 * k * Tqd0 + TTqdd0 * TTqdd0);
     const double den = 5 * (6 * Tqd0 - 12 * k + TTqdd0);
-    *r2 = (2 * Tqd0 + TTqdd0 + disc) / den;
-    *r3 = (2 * Tqd0 + TTqdd0 - disc) / den;
+    root_pair(2 * Tqd0 + TTqdd0, disc, den, -2 * Tqd0, r2, r3);
 }
 AD void qd_roots(double Tqd0, double TTqdd0, double k, double* r2, double* r3) {
     const double disc = sqrt(6 * (150 * k * k - 180 * k * Tqd0 - 20 * k * TTqdd0 + 54 * Tqd0 * Tqd0 + 14 * Tqd0 * TTqdd0 + TTqdd0 * TTqdd0));
     const double den = 10 * (6 * Tqd0 - 12 * k + TTqdd0);
-    *r2 = (18 * Tqd0 - 30 * k + 4 * TTqdd0 + disc) / den;
-    *r3 = (18 * Tqd0 - 30 * k + 4 * TTqdd0 - disc) / den;
+    root_pair(18 * Tqd0 - 30 * k + 4 * TTqdd0, disc, den, TTqdd0, r2, r3);
 }
 AD void qdd_roots_k0(double Tqd0, double TTqdd0, double* r1, double* r2) {
     const double disc = sqrt(2 * (152 * Tqd0 * Tqd0 + 42 * Tqd0 * TTqdd0 + 3 * TTqdd0 * TTqdd0));
     const double den = 10 * (6 * Tqd0 + TTqdd0);
-    *r1 = (32 * Tqd0 + 6 * TTqdd0 + disc) / den;
-    *r2 = (32 * Tqd0 + 6 * TTqdd0 - disc) / den;
+    root_pair(32 * Tqd0 + 6 * TTqdd0, disc, den, 3 * (4 * Tqd0 + TTqdd0), r1, r2);
 }
 AD void bound_k_indep(double vlb, double vub, double s_lb, double s_ub, double e1, double v1, double e2, double v2, double* lo, double* hi) {
     if (vlb > vub) { const double t = vlb; vlb = vub; vub = t; }
@@ -147,6 +158,9 @@ __host__ __device__ __attribute__((noinline)) JrsJoint jrs_joint(const RobotPara
     kc_lb = (30 * s_lb * s_lb * (s_lb - 1) * (s_lb - 1)) / D;
     kc_ub = (30 * s_ub * s_ub * (s_ub - 1) * (s_ub - 1)) / D;
     if (kc_ub < kc_lb) { const double t = kc_lb; kc_lb = kc_ub; kc_ub = t; }
+    // 30 s^2 (s - 1)^2 peaks at s = 1/2: an end of an interval when T is even (the reference's case),
+    // inside the middle interval when T is odd, where the ends alone would miss it
+    if (s_lb < 0.5 && 0.5 < s_ub) kc_ub = fmax(kc_ub, 1.875 / D);
     kdc = (kc_ub + kc_lb) * 0.5 * kr;
     kdr = (kc_ub - kc_lb) * 0.5 * kr;
     bound_k_indep(bz_qd(qr, Tqd0, TTqdd0, 0.0, s_lb) / D, bz_qd(qr, Tqd0, TTqdd0, 0.0, s_ub) / D, s_lb, s_ub, qde1, qdv1, qde2, qdv2, &ki_lb, &ki_ub);

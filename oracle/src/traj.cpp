@@ -50,27 +50,38 @@ double qdd_des_func(double q0, double Tqd0, double TTqdd0, double k, double t) {
                  3 * t * t * u * (b[2] - b[3]));
 }
 
+// Interior critical points: the roots (p +- disc) / den of a quadratic whose leading coefficient den
+// vanishes on 6 Tqd0 + TTqdd0 = 12 k. There the quadratic is linear: big / den, big = p + sign(p) disc,
+// leaves [0, 1] through +-inf, and the other root's numerator p - sign(p) disc cancels to nothing over
+// a vanishing den. Once that numerator has cancelled (below 2^-16 |big|) the root is taken from the
+// product of the roots, (p^2 - disc^2) / (big den), whose numerator is den times prod exactly; outside
+// the guard both roots are the expressions they always were, bit for bit, in the same slots.
+static inline void root_pair(double p, double disc, double den, double prod, double* r2, double* r3) {
+    const double hi = p + disc, lo = p - disc;
+    const bool pos = p >= 0;
+    const double big = pos ? hi : lo, sm = pos ? lo : hi;
+    const double rs = std::fabs(sm) < 0x1p-16 * std::fabs(big) ? prod / big : sm / den;
+    *r2 = pos ? hi / den : rs;
+    *r3 = pos ? rs : lo / den;
+}
 // interior critical points of q(t) (roots of dq/dt besides t = 1), Trajectory.cu:263-264
 static inline void q_roots(double Tqd0, double TTqdd0, double k, double* r2, double* r3) {
     const double disc = std::sqrt(64 * Tqd0 * Tqd0 + 14 * Tqd0 * TTqdd0 - 120 * k * Tqd0 + TTqdd0 * TTqdd0);
     const double den = 5 * (6 * Tqd0 - 12 * k + TTqdd0);
-    *r2 = (2 * Tqd0 + TTqdd0 + disc) / den;
-    *r3 = (2 * Tqd0 + TTqdd0 - disc) / den;
+    root_pair(2 * Tqd0 + TTqdd0, disc, den, -2 * Tqd0, r2, r3);
 }
 // interior critical points of qd(t) (roots of d2q/dt2), Trajectory.cu:406-407
 static inline void qd_roots(double Tqd0, double TTqdd0, double k, double* r2, double* r3) {
     const double disc = std::sqrt(6 * (150 * k * k - 180 * k * Tqd0 - 20 * k * TTqdd0 + 54 * Tqd0 * Tqd0 +
                                        14 * Tqd0 * TTqdd0 + TTqdd0 * TTqdd0));
     const double den = 10 * (6 * Tqd0 - 12 * k + TTqdd0);
-    *r2 = (18 * Tqd0 - 30 * k + 4 * TTqdd0 + disc) / den;
-    *r3 = (18 * Tqd0 - 30 * k + 4 * TTqdd0 - disc) / den;
+    root_pair(18 * Tqd0 - 30 * k + 4 * TTqdd0, disc, den, TTqdd0, r2, r3);
 }
 // interior critical points of qdd(t) at k = 0 (Trajectory.cu:54-55)
 static inline void qdd_roots_k0(double Tqd0, double TTqdd0, double* r1, double* r2) {
     const double disc = std::sqrt(2 * (152 * Tqd0 * Tqd0 + 42 * Tqd0 * TTqdd0 + 3 * TTqdd0 * TTqdd0));
     const double den = 10 * (6 * Tqd0 + TTqdd0);
-    *r1 = (32 * Tqd0 + 6 * TTqdd0 + disc) / den;
-    *r2 = (32 * Tqd0 + 6 * TTqdd0 - disc) / den;
+    root_pair(32 * Tqd0 + 6 * TTqdd0, disc, den, 3 * (4 * Tqd0 + TTqdd0), r1, r2);
 }
 
 double q_des_extrema2_k_derivative(double q0, double Tqd0, double TTqdd0, double k) {
@@ -197,10 +208,13 @@ void Bezier::makePolyZono(int s_ind) {
         R[i * T + t] = Ri;
         R_t[i * T + t] = Ri.transpose();
 
-        // Part 2: qd_des (:151-192); even-T bounding trick of the reference kept as is
+        // Part 2: qd_des (:151-192); the reference bounds the slope by its values at the interval's ends
         kc_lb = (30 * s_lb * s_lb * (s_lb - 1) * (s_lb - 1)) / D;
         kc_ub = (30 * s_ub * s_ub * (s_ub - 1) * (s_ub - 1)) / D;
         if (kc_ub < kc_lb) std::swap(kc_lb, kc_ub);
+        // 30 s^2 (s - 1)^2 peaks at s = 1/2: an end of an interval when T is even (the reference's case),
+        // inside the middle interval when T is odd, where the ends alone would miss it
+        if (s_lb < 0.5 && 0.5 < s_ub) kc_ub = std::max(kc_ub, 1.875 / D);
         kdc = (kc_ub + kc_lb) * 0.5 * kr;
         kdr = (kc_ub - kc_lb) * 0.5 * kr;
         bound_k_indep(qd_des_k_indep(q0[i], Tqd0[i], TTqdd0[i], s_lb, D), qd_des_k_indep(q0[i], Tqd0[i], TTqdd0[i], s_ub, D),

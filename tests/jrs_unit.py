@@ -82,19 +82,17 @@ def jrs_outputs(lib):
     return lib.jrs(T, joint, c[:, 0], c[:, 1], c[:, 2], c[:, 3].astype(np.int32))
 
 
-def jrs_slack():
-    """16 * 2^-52 * max(1, |q0| + |qd0| + |qdd0|) per case: the round-to-nearest operations on the
-    centres and the rounding of q0 + ... in the Bernstein differences"""
-    c = fixture()["cases"]
-    return 16 * 2.0 ** -52 * np.maximum(1.0, np.abs(c[:, :3]).sum(axis=1))
+def slack_of(states):
+    """16 * 2^-52 * max(1, |q0| + |qd0| + |qdd0|) per row of states [n, >= 3]: the round-to-nearest
+    operations on the centres and the rounding of q0 + ... in the Bernstein differences"""
+    return 16 * 2.0 ** -52 * np.maximum(1.0, np.abs(states[:, :3]).sum(axis=1))
 
 
-def jrs_excess(out):
-    """[n, 12, 4] long double: |exact - (centre + slope * khat)| - |radius| for cos, sin, qd, qdd at
-    every sample of every case (<= slack: the scalars enclose the trajectory)"""
-    fx = fixture()
-    kh = LD(fx["points"][:, :, 1])
-    ex = _ld(fx["exact"])
+def excess_of(out, kh, ex):
+    """[n, p, 4] long double: |exact - (centre + slope * khat)| - |radius| for cos, sin, qd, qdd, of the
+    13 doubles out [n, 13] at samples with khat kh [n, p] and exact values ex [n, p, 4] (long double)
+    (<= slack: the scalars enclose the trajectory)"""
+    kh = LD(kh)
     res = np.zeros(ex.shape, dtype=LD)
     for n, col in enumerate((COS, SIN, QD, QDD)):
         col_e = col + 2
@@ -103,17 +101,35 @@ def jrs_excess(out):
     return res
 
 
-def check_jrs(out, report):
-    """the enclosure and no NaN; report: a callable for the measured figures"""
-    assert np.all(np.isfinite(out)), "non-finite JRS scalar"
-    ex = jrs_excess(out)
-    slack = jrs_slack()
-    worst = ex.max(axis=1).astype(np.float64)                    # [n, 4]
+def check_enclosure(out, states, kh, ex, report):
+    """the enclosure of any fixture's samples (states [n, >= 3] = q0, qd0, qdd0, ...; kh, ex as
+    excess_of) and no NaN; report: a callable for the measured figures. Returns the worst excess
+    [n, 4]"""
+    assert np.all(np.isfinite(out)), ("non-finite JRS scalar", states[~np.isfinite(out).all(axis=1)][:5].tolist())
+    slack = slack_of(states)
+    worst = excess_of(out, kh, ex).max(axis=1).astype(np.float64)   # [n, 4]
     units = worst / slack[:, None]
     report(f"worst excess: cos {worst[:, 0].max():.3e} sin {worst[:, 1].max():.3e} qd {worst[:, 2].max():.3e} "
            f"qdd {worst[:, 3].max():.3e}; in units of the slack: {units.max(axis=0)}")
     bad = np.argwhere(worst > slack[:, None])
-    assert bad.size == 0, [(fixture()["cases"][i].tolist(), int(k), float(worst[i, k]), float(slack[i])) for i, k in bad[:5]]
+    assert bad.size == 0, (len(bad), [(states[i].tolist(), int(k), float(worst[i, k]), float(slack[i])) for i, k in bad[:5]])
+    return worst
+
+
+def jrs_slack():
+    return slack_of(fixture()["cases"])
+
+
+def jrs_excess(out):
+    """excess_of on the samples of tests/golden/jrs_samples.npz"""
+    fx = fixture()
+    return excess_of(out, fx["points"][:, :, 1], _ld(fx["exact"]))
+
+
+def check_jrs(out, report):
+    """the enclosure and no NaN on tests/golden/jrs_samples.npz"""
+    fx = fixture()
+    check_enclosure(out, fx["cases"], fx["points"][:, :, 1], _ld(fx["exact"]), report)
 
 
 # ---- directed operations -------------------------------------------------------------------------
