@@ -33,6 +33,10 @@ class Config(ctypes.Structure):
                 ("max_worlds", ctypes.c_int), ("device", ctypes.c_int), ("max_iter", ctypes.c_int)]
 
 
+class SolverOptions(ctypes.Structure):  # armour_solver_options
+    _fields_ = [("mu_strategy", ctypes.c_int), ("qf_grid", ctypes.c_int), ("lbfgs_history", ctypes.c_int)]
+
+
 class World(ctypes.Structure):
     _fields_ = [("q0", ctypes.c_double * NF), ("qd0", ctypes.c_double * NF), ("qdd0", ctypes.c_double * NF),
                 ("q_des", ctypes.c_double * NF), ("num_obstacles", ctypes.c_int), ("obstacles", _dp)]
@@ -196,6 +200,9 @@ def lib():
             L.armour_get_path_counts.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong), ctypes.c_int]
             L.armour_path_name.restype = ctypes.c_char_p
             L.armour_path_name.argtypes = [ctypes.c_int]
+        if hasattr(L, "armour_set_solver_options"):  # absent from older libraries loaded through ARMOUR_LIB
+            L.armour_get_solver_options.argtypes = [ctypes.c_void_p, ctypes.POINTER(SolverOptions)]
+            L.armour_set_solver_options.argtypes = [ctypes.c_void_p, ctypes.POINTER(SolverOptions)]
         L.armour_get_reach_dump.argtypes = [ctypes.c_void_p, _dp, ctypes.c_int]
         L.armour_get_reach_profile.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_int]
         for name in ("armour_get_constraints", "armour_get_link_centers", "armour_get_link_generators",
@@ -220,7 +227,7 @@ ABI_SYMBOLS = ["armour_copy_bandwidth", "armour_create", "armour_create_robot", 
                "armour_eval_candidates", "armour_sq_selfcheck", "armour_check_world", "armour_check_armtd_world",
                "armour_check_motion", "armour_episode_begin", "armour_episode_step", "armour_episode_get",
                "armour_track", "armour_track_motion", "armour_episode_track", "armour_episode_get_tracked",
-               "armour_get_path_counts", "armour_path_name"]
+               "armour_get_path_counts", "armour_path_name", "armour_get_solver_options", "armour_set_solver_options"]
 
 
 def default_batch(T: int, device: int = 0, waves: int = 2) -> int:
@@ -349,8 +356,9 @@ class Planner:
     """Batched MI355X planner. A world is (q0, qd0, qdd0, q_des, obstacles[O, 12]). plan / reach take
     worlds that all carry the same O; plan_mixed / reach_mixed take any mix of counts."""
 
-    def __init__(self, T=100, max_obstacles=20, max_worlds=1, device=0, max_iter=0, robot=None, _armtd=False):
-        """robot: None (built-in Kinova Gen3 tables) or a robot-table dict (armour_amd.robot_tables)"""
+    def __init__(self, T=100, max_obstacles=20, max_worlds=1, device=0, max_iter=0, robot=None, _armtd=False, solver=None):
+        """robot: None (built-in Kinova Gen3 tables) or a robot-table dict (armour_amd.robot_tables);
+        solver: None or a dict of solver options (set_solver_options)"""
         cfg = Config(0, T, max_obstacles, max_worlds, device, max_iter)
         if _armtd:
             self.h = lib().armour_create_armtd(ctypes.byref(cfg))
@@ -368,6 +376,27 @@ class Planner:
         self._keep = []
         self.O = 0
         self._W = 0   # worlds of the last batch handed to the library
+        if solver:
+            self.set_solver_options(**solver)
+
+    def solver_options(self):
+        """armour_get_solver_options: dict(mu_strategy=, qf_grid=, lbfgs_history=)"""
+        o = SolverOptions()
+        _check(lib().armour_get_solver_options(self.h, ctypes.byref(o)))
+        return dict(mu_strategy=o.mu_strategy, qf_grid=o.qf_grid, lbfgs_history=o.lbfgs_history)
+
+    def set_solver_options(self, **options):
+        """armour_set_solver_options: the named fields change, the others keep their values; from the
+        next plan on. mu_strategy 0 monotone, 1 adaptive (default), 2 Ipopt's quality-function pair (with
+        lbfgs_history=6 the reference's configuration), 3 that pair with the default's floor and mu grid;
+        qf_grid 2..32 sigma candidates; lbfgs_history 0 (damped full BFGS) or 1..6"""
+        cur = self.solver_options()
+        unknown = set(options) - set(cur)
+        if unknown:
+            raise TypeError(f"set_solver_options: unknown option(s) {sorted(unknown)}")
+        cur.update({k: int(v) for k, v in options.items()})
+        o = SolverOptions(cur["mu_strategy"], cur["qf_grid"], cur["lbfgs_history"])
+        _check(lib().armour_set_solver_options(self.h, ctypes.byref(o)))
 
     def close(self):
         if getattr(self, "h", None) and _LIB is not None:  # (module teardown may have cleared _LIB)
@@ -793,9 +822,9 @@ class ArmtdPlanner(Planner):
     (q0, qd0, q_des, jrs_tables[7, 6, T], k_range[7], obstacles[O, 12]) with the tables per joint
     c_cos, g_cos, r_cos, c_sin, g_sin, r_sin (ACMP/armtd_main.cu:37-102)."""
 
-    def __init__(self, T=100, max_obstacles=20, max_worlds=1, device=0, max_iter=0):
+    def __init__(self, T=100, max_obstacles=20, max_worlds=1, device=0, max_iter=0, solver=None):
         super().__init__(T=T, max_obstacles=max_obstacles, max_worlds=max_worlds, device=device, max_iter=max_iter,
-                         _armtd=True)
+                         _armtd=True, solver=solver)
 
     def _worlds(self, worlds):
         n = len(worlds)

@@ -28,7 +28,10 @@ struct IpmOpts {
     // barrier strategy: 1 adaptive (default: the reference's IPOPT_MU_STRATEGY "adaptive",
     // KPR/Parameters.h:57, restated with Ipopt's LOQO mu oracle and kkt-error globalisation, mu on a
     // 2^(1/8) grid with floor tol / 10, as oracle/src/ipm.cpp); 0 monotone
-    // (ARMOUR_MU_STRATEGY=monotone)
+    // (ARMOUR_MU_STRATEGY=monotone); 2 Ipopt's default adaptive pair, the quality-function oracle with
+    // the obj-constr-filter globalisation and mu_min 1e-11 (ARMOUR_MU_STRATEGY=quality); 3 that pair
+    // with the floor tol / 10 and the mu grid (quality-floor). armour_set_solver_options; the other two
+    // options and the state they need: OptDev
     int mu_strategy = 1;
     // restoration phase (nlp_kernels.hip resto_*, oracle/src/ipm.cpp restoration): phases per
     // solve (ARMOUR_RESTORATION=0: none), violation target inside the bounds, box barrier weight,
@@ -67,6 +70,35 @@ struct WorldState {
     double rphi;
 };
 constexpr int WS_RESTO = 6;
+// The optional solver configurations' per-world state (armour_solver_options: the quality-function
+// barrier oracle, strategies 2 and 3, and the limited-memory BFGS), in an array of its own beside ws
+// so that WorldState, which every world kernel stages in LDS, keeps its size. Only lane 0 of a world
+// kernel touches it, and only under those options.
+constexpr int QF_GMAX = 32;  // most sigma candidates
+constexpr int QF_TILE = 8;   // candidates a sweep of ipm_rows_Q carries in registers
+constexpr int LB_MAX = 6;    // longest L-BFGS history
+constexpr int QP = 3 * QF_GMAX + 1;  // ipm_rows_Q's sums per world: cc, a_P, a_D per candidate, sum r_p^2
+struct QfState {
+    double mu_max;             // Ipopt's mu_max, min(1e5, 1e3 avg(s z)) at the first iteration (-1: not set)
+    double avg;                // avg(s z) of this iteration
+    double dx0[NF], dx1[NF];   // the affine step and the step per unit mu of this iteration
+    double lb_s[LB_MAX][NF], lb_y[LB_MAX][NF];  // the L-BFGS pairs, oldest first
+    int ngf;                   // entries of the free-mode filter of (f, theta) (NlpDev::gf)
+    int nlb, lb_skips;         // stored pairs, updates skipped in a row
+    int pending;               // this iteration's mu waits for the sigma search (ipm_rows_Q, ipm_world_Q)
+};
+// What the kernels of the optional configurations take beside the NlpDev (the world steps of passes A
+// and D, the sigma search, ipm_world_init, resto_world_G): the two options, the per-world state and the
+// sigma candidates. Kept out of NlpDev, which every other kernel takes by value and keeps as it was.
+struct OptDev {
+    QfState* qs;            // [W]
+    double* gf;             // [W][2][gf_cap]: the free-mode filter's f, then theta (strategies 2, 3)
+    double* qpart;          // [W][QP]: ipm_rows_Q's sums
+    int gf_cap;             // max_iter + 1: at most one entry per iteration
+    int qf_grid;            // sigma candidates of the quality function (strategies 2, 3), 2 .. QF_GMAX
+    int lbfgs_history;      // 0 damped full BFGS; 1 .. LB_MAX Ipopt's limited-memory BFGS (world_D_body)
+    double sig[QF_GMAX];    // the candidates, formed on the host (std::pow, as oracle/src/ipm.cpp forms them)
+};
 // A world whose restoration phase reached a point within every bound waits for its slacks and
 // multipliers (ipm_rows_init) before it runs again: status 0 would let a phase run inside the
 // interior-point loop hand it back to lists that still name it (planner.hip ipm_loop)

@@ -1389,7 +1389,7 @@ __global__ __launch_bounds__(EVAL_THREADS) __attribute__((amdgpu_waves_per_eu(5,
 
 // ------------------------------------------------------------------------------------------
 // armour-IPM
-__global__ __launch_bounds__(64) void ipm_world_init(NlpDev d, Round r) {
+__global__ __launch_bounds__(64) void ipm_world_init(NlpDev d, Round r, OptDev o) {
     const int w = blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= d.W) return;
     WorldState& S = d.ws[w];
@@ -1415,8 +1415,14 @@ __global__ __launch_bounds__(64) void ipm_world_init(NlpDev d, Round r) {
     S.iter = 0;
     S.nevals = 1;
     S.kkt = 0;
-    S.free_mode = d.opt.mu_strategy == 1 ? 1 : 0;
+    S.free_mode = d.opt.mu_strategy >= 1 ? 1 : 0;
     S.nref = 0;
+    QfState& Q = o.qs[w];
+    Q.mu_max = -1;
+    Q.ngf = 0;
+    Q.nlb = 0;
+    Q.lb_skips = 0;
+    Q.pending = 0;
     S.nresto = 0;
     S.rstall = 0;
     S.rpend = 0;
@@ -1482,7 +1488,9 @@ struct AAcc {
     double rdp[NF], M[28], u1[NF], u2[NF];
     double inf_p, compl0, cm, sumz;
     double sumc, minc;  // sum and minimum of s z over the finite sides (the adaptive barrier's oracle)
+    double theta;       // sum |r_p| (QF: the obj-constr-filter globalisation of strategies 2, 3)
     __device__ void zero() {
+        theta = 0;
 #pragma unroll
         for (int j = 0; j < NF; j++) { rdp[j] = 0; u1[j] = 0; u2[j] = 0; }
 #pragma unroll
@@ -1492,7 +1500,7 @@ struct AAcc {
     }
 };
 // pass A's row accumulation with the row's slacks and multipliers given (registers)
-template <int ML = 0>
+template <int ML = 0, bool QF = false>
 __device__ inline __attribute__((always_inline)) void row_A_sz(const NlpDev& d, long i, double v, const double* a, double L,
                                                                double U, double mu, double slo, double zlo, double shi,
                                                                double zhi, AAcc& c, double* ml = nullptr) {
@@ -1507,6 +1515,7 @@ __device__ inline __attribute__((always_inline)) void row_A_sz(const NlpDev& d, 
         c.sumz += z;
         c.sumc += s * z;
         c.minc = fmin(c.minc, s * z);
+        if constexpr (QF) c.theta += fabs(rp);
         const double sg = z / s;
         sig += sg;
         c1 += 1.0 / s;
@@ -1522,6 +1531,7 @@ __device__ inline __attribute__((always_inline)) void row_A_sz(const NlpDev& d, 
         c.sumz += z;
         c.sumc += s * z;
         c.minc = fmin(c.minc, s * z);
+        if constexpr (QF) c.theta += fabs(rp);
         const double sg = z / s;
         sig += sg;
         c1 -= 1.0 / s;
@@ -1540,14 +1550,17 @@ __device__ inline __attribute__((always_inline)) void row_A_sz(const NlpDev& d, 
         }
     }
 }
+template <bool QF = false>
 __device__ inline __attribute__((always_inline)) void row_A(const NlpDev& d, long i, double v, const double* a, double L,
                                                             double U, double mu, AAcc& c) {
-    row_A_sz(d, i, v, a, L, U, mu, d.slo[i], d.zlo[i], d.shi[i], d.zhi[i], c);
+    row_A_sz<0, QF>(d, i, v, a, L, U, mu, d.slo[i], d.zlo[i], d.shi[i], d.zhi[i], c);
 }
 constexpr int NA = 55;  // pass A's partial sums per row block (<= KA)
-static_assert(NA <= KA, "pass A partials fit the partial slots");
-template <int ML = 0>
+constexpr int NAQ = 56; // with theta in slot 55 (the _qf instantiations: strategies 2, 3)
+static_assert(NAQ <= KA, "pass A partials fit the partial slots");
+template <int ML = 0, bool QF = false>
 __device__ inline void reduce_A(const NlpDev& d, int w, AAcc& c, double* lds, const double* ml = nullptr) {
+    constexpr int NA = QF ? NAQ : armour::NA;
     double* out = d.partial + ((long)w * d.nblk + blockIdx.x) * KA;
     double v[NA];
     int kinds[NA];
@@ -1557,6 +1570,7 @@ __device__ inline void reduce_A(const NlpDev& d, int w, AAcc& c, double* lds, co
 #pragma unroll
     for (int k = ML; k < 28; k++) v[11 + k] = c.M[k];
     v[53] = c.sumc; v[54] = c.minc;
+    if constexpr (QF) v[55] = c.theta;
 #pragma unroll
     for (int k = 0; k < NA; k++) kinds[k] = (k >= 7 && k <= 9) ? 1 : k == 54 ? 2 : 0;
     // an LDS-resident accumulator is read where the reduction consumes its pair, not before
@@ -1571,13 +1585,13 @@ __device__ inline double dual_step(double mu, double s, double z, double ds) {
     return mu / s - z - sg * ds;
 }
 
-template <bool MX>
+template <bool MX, bool QF = false>
 __device__ __attribute__((always_inline)) void ipm_rows_A_body(const NlpDev& d, const Round& r) {
     const auto [w, sh, r0, wb, rows] = row_block<MX>(d, r, blockIdx.y, false);
     if (!rows) return;
     const WorldState& S = d.ws[w];
     if (S.status != 0) return;
-    __shared__ double lds[(ROW_THREADS / 64) * NA];
+    __shared__ double lds[(ROW_THREADS / 64) * (QF ? NAQ : NA)];
     AAcc c;
     c.zero();
     const double mu = S.mu;
@@ -1587,12 +1601,14 @@ __device__ __attribute__((always_inline)) void ipm_rows_A_body(const NlpDev& d, 
         const long i = wb + r;
         double L, U;
         row_bounds(d, sh, i, (int)r, L, U);
-        row_A(d, i, v, a, L, U, mu, c);
+        row_A<QF>(d, i, v, a, L, U, mu, c);
     }
-    reduce_A(d, w, c, lds);
+    reduce_A<0, QF>(d, w, c, lds);
 }
 __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_A(NlpDev d, Round r) { ipm_rows_A_body<false>(d, r); }
 __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_A_mx(NlpDev d, Round r) { ipm_rows_A_body<true>(d, r); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_A_qf(NlpDev d, Round r) { ipm_rows_A_body<false, true>(d, r); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_A_qf_mx(NlpDev d, Round r) { ipm_rows_A_body<true, true>(d, r); }
 
 // passes D (of the previous iteration) and A (of this one) in one sweep over the rows: the trial
 // point D accepts is the point A works at, so each row's value and gradient are read once; the
@@ -1604,13 +1620,13 @@ __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_A_mx(NlpDev d, Round r) 
 // launch 744 -> 651 us, but a small grid's latency 17.2 -> 19.9 us (the slots' LDS round trips), so
 // grids below four blocks per CU keep the register form (planner.hip ipm_loop)
 constexpr int DA_ML = 20;
-template <int ML, bool MX = false>
+template <int ML, bool MX = false, bool QF = false>
 __device__ __attribute__((always_inline)) void rows_DA_body(const NlpDev& d, const Round& r) {
     const auto [w, sh, r0, wb, rows] = row_block<MX>(d, r, blockIdx.y, true);
     if (!rows) return;
     const WorldState& S = d.ws[w];
     if (S.status != 0) return;
-    __shared__ double lds[(ROW_THREADS / 64) * NA];
+    __shared__ double lds[(ROW_THREADS / 64) * (QF ? NAQ : NA)];
     double* ml = nullptr;
     if constexpr (ML > 0) {
         __shared__ double mls[ML * ROW_THREADS];
@@ -1654,18 +1670,23 @@ __device__ __attribute__((always_inline)) void rows_DA_body(const NlpDev& d, con
         }
 #pragma unroll
         for (int j = 0; j < NF; j++) wn[j] += wv * a[j];
-        row_A_sz<ML>(d, i, v, a, L, U, mu, sl, zl, sh, zh, c, ml);
+        row_A_sz<ML, QF>(d, i, v, a, L, U, mu, sl, zl, sh, zh, c, ml);
         if constexpr (ML > 0) __asm__ volatile("" ::: "memory");  // the slots stay in LDS across rows
     }
     const int kinds[NF] = {};
     block_reduce_n(wn, kinds, lds, d.partial2 + ((long)w * d.nblk + blockIdx.x) * KA2);
     __syncthreads();
-    reduce_A<ML>(d, w, c, lds, ml);
+    reduce_A<ML, QF>(d, w, c, lds, ml);
 }
 __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_DA(NlpDev d, Round r) { rows_DA_body<0>(d, r); }
 __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_DA_lds(NlpDev d, Round r) { rows_DA_body<DA_ML>(d, r); }
 __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_DA_mx(NlpDev d, Round r) { rows_DA_body<0, true>(d, r); }
 __global__ __launch_bounds__(ROW_THREADS) void ipm_rows_DA_lds_mx(NlpDev d, Round r) { rows_DA_body<DA_ML, true>(d, r); }
+// the same passes with theta = sum |r_p| in slot 55 (strategies 2 and 3)
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_DA_qf(NlpDev d, Round r) { rows_DA_body<0, false, true>(d, r); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_DA_lds_qf(NlpDev d, Round r) { rows_DA_body<DA_ML, false, true>(d, r); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_DA_qf_mx(NlpDev d, Round r) { rows_DA_body<0, true, true>(d, r); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_DA_lds_qf_mx(NlpDev d, Round r) { rows_DA_body<DA_ML, true, true>(d, r); }
 
 __device__ bool chol_solve7(const double* M, double shift, const double* b, double* x) {
     double L[NF * NF];
@@ -1740,7 +1761,7 @@ __device__ inline void world_partials(const NlpDev& d, int w, int nblk, const do
 }
 
 template <bool MX>
-__device__ inline void world_A_body(const NlpDev& d, WorldState& S, int w, int nside);
+__device__ inline void world_A_body(const NlpDev& d, const OptDev& o, WorldState& S, int w, int nside);
 // The adaptive barrier parameter on a fixed logarithmic grid 2^(j/8) x 2^e (oracle/src/ipm.cpp
 // mu_grid, the same constants and comparisons): a rounding-level difference in the complementarity
 // sums leaves mu's bits unchanged unless it straddles a midpoint
@@ -1804,18 +1825,103 @@ __device__ __attribute__((always_inline)) void last_block(const NlpDev& d, F&& p
     }
 }
 template <bool MX>
-__device__ __attribute__((always_inline)) void ipm_world_A_body(const NlpDev& d, const Round& r, int nside) {
+__device__ __attribute__((always_inline)) void ipm_world_A_body(const NlpDev& d, const Round& r, int nside, const OptDev& o) {
     const int w = world_of(r, blockIdx.x);
-    world_step(d, true, w, 0, [&](WorldState& S) { world_A_body<MX>(d, S, w, nside); });
+    world_step(d, true, w, 0, [&](WorldState& S) { world_A_body<MX>(d, o, S, w, nside); });
 }
-__global__ __launch_bounds__(64) void ipm_world_A(NlpDev d, Round r, int nside) { ipm_world_A_body<false>(d, r, nside); }
-__global__ __launch_bounds__(64) void ipm_world_A_mx(NlpDev d, Round r, int nside) { ipm_world_A_body<true>(d, r, nside); }
+__global__ __launch_bounds__(64) void ipm_world_A(NlpDev d, Round r, int nside, OptDev o) { ipm_world_A_body<false>(d, r, nside, o); }
+__global__ __launch_bounds__(64) void ipm_world_A_mx(NlpDev d, Round r, int nside, OptDev o) { ipm_world_A_body<true>(d, r, nside, o); }
 // pass A's world step: convergence test, barrier update, Newton step; every lane of the wave calls it.
 // nside: the finite constraint sides of a world, a batch constant from the host (planner.hip
 // nside_count); a mixed batch's world counts its own: torque 2 per row, collision 1, extrema 2,
 // box 2 per variable
+// the reduced Newton system of pass A's partials P at the barrier parameter S.mu, solved into S.dx
+// (lane 0)
+__device__ inline void world_A_newton(const NlpDev& d, WorldState& S, const double* P, const double* grad) {
+    double M[NF * NF], rhs[NF];
+    int k = 0;
+    for (int p = 0; p < NF; p++)
+        for (int q = p; q < NF; q++) {
+            M[p * NF + q] = S.H[p * NF + q] + P[11 + k];
+            M[q * NF + p] = S.H[q * NF + p] + P[11 + k];
+            k++;
+        }
+    for (int j = 0; j < NF; j++) rhs[j] = -grad[j] + S.mu * P[39 + j] - P[46 + j];
+    // inertia correction: shift the diagonal until the factorisation succeeds (bounded)
+    double shift = 0.0;
+    bool ok = false;
+    for (int tries = 0; tries < 40 && !ok; tries++) {
+        ok = chol_solve7(M, shift, rhs, S.dx);
+        shift = (shift == 0.0) ? 1e-8 : shift * 10;
+    }
+    if (!ok) {
+        for (int j = 0; j < NF; j++) S.dx[j] = 0.0;
+        S.status = 3;
+    }
+}
+// strategies 2 and 3 (oracle/src/ipm.cpp, the `qf` branch): the barrier parameter's floor and grid
+__device__ inline double qf_mu_min(const NlpDev& d) { return d.opt.mu_strategy == 2 ? 1e-11 : d.opt.tol / 10; }
+__device__ inline double qf_mu_grid(const NlpDev& d, double v) { return d.opt.mu_strategy == 3 ? mu_grid(v) : v; }
+// The head of pass A's world step under strategies 2 and 3 (lane 0; oracle/src/ipm.cpp, same order of
+// decisions): the obj-constr-filter globalisation on the free-mode filter of (f, theta), fixed mode
+// from 0.8 avg(s z), and in free mode the two solves dx_aff, dx_1 the sigma search reads (same matrix
+// and shift loop). Returns true when mu is known (the Newton solve follows at once), false when it
+// waits for the search (Q.pending; ipm_rows_Q, ipm_world_Q).
+__device__ inline bool world_A_quality(const NlpDev& d, const OptDev& o, WorldState& S, int w, int nside, const double* P,
+                                       double theta, const double* grad, double Emu) {
+    QfState& Q = o.qs[w];
+    double* gf_f = o.gf + (long)w * 2 * o.gf_cap;
+    double* gf_t = gf_f + o.gf_cap;
+    const double mu_min = qf_mu_min(d);
+    const double f = d.f[S.cur * d.W + w];
+    const double avg = P[53] / (double)(nside > 0 ? nside : 1);
+    if (Q.mu_max < 0) Q.mu_max = fmin(1e5, 1e3 * avg);
+    const double margin = 1e-5 * fmin(1.0, theta);
+    bool acceptable = true;
+    for (int q = 0; q < Q.ngf; q++)
+        if (!(f + margin < gf_f[q] || theta + margin < gf_t[q])) acceptable = false;
+    const double mu_old = S.mu;
+    if (S.free_mode && !acceptable) {
+        S.free_mode = 0;
+        S.mu = fmax(mu_min, qf_mu_grid(d, 0.8 * avg));
+    } else if (!S.free_mode && acceptable) {
+        S.free_mode = 1;
+    }
+    if (S.free_mode) {
+        if (Q.ngf < o.gf_cap) {  // (one entry per iteration at most, gf_cap = max_iter + 1)
+            gf_f[Q.ngf] = f;
+            gf_t[Q.ngf] = theta;
+            Q.ngf++;
+        }
+        double M[NF * NF], b0[NF], b1[NF];
+        int k = 0;
+        for (int p = 0; p < NF; p++)
+            for (int q = p; q < NF; q++) {
+                M[p * NF + q] = S.H[p * NF + q] + P[11 + k];
+                M[q * NF + p] = S.H[q * NF + p] + P[11 + k];
+                k++;
+            }
+        for (int j = 0; j < NF; j++) { b0[j] = -grad[j] - P[46 + j]; b1[j] = P[39 + j]; }
+        double shift = 0.0;
+        bool ok = false;
+        for (int tries = 0; tries < 40 && !ok; tries++) {
+            ok = chol_solve7(M, shift, b0, Q.dx0) && chol_solve7(M, shift, b1, Q.dx1);
+            shift = (shift == 0.0) ? 1e-8 : shift * 10;
+        }
+        if (ok) {
+            Q.avg = avg;
+            Q.pending = 1;
+            return false;
+        }
+        S.mu = fmax(mu_min, fmin(qf_mu_grid(d, 0.1 * avg), Q.mu_max));  // (the oracle's sigma without the two steps)
+    } else if (Emu <= d.opt.kappa_eps * S.mu && S.mu > mu_min) {
+        S.mu = fmax(mu_min, fmin(d.opt.kappa_mu * S.mu, pow(S.mu, d.opt.theta_mu)));
+    }
+    if (S.mu != mu_old) S.nfilt = 0;
+    return true;
+}
 template <bool MX>
-__device__ inline void world_A_body(const NlpDev& d, WorldState& S, int w, int nside) {
+__device__ inline void world_A_body(const NlpDev& d, const OptDev& o, WorldState& S, int w, int nside) {
     if (S.status != 0) return;
     const Shape sh = shape_of<MX>(d, w);
     if constexpr (MX) nside = 2 * d.nt + d.T * d.NJ * sh.O + 2 * 4 * NF + 2 * NF;
@@ -1837,7 +1943,11 @@ __device__ inline void world_A_body(const NlpDev& d, WorldState& S, int w, int n
     S.kkt = E0;
     if (E0 <= d.opt.tol) { S.status = 1; return; }
     const double Emu = fmax(fmax(inf_d / sd, P[7]), P[9] / sd);
-    if (d.opt.mu_strategy == 1) {
+    if (d.opt.mu_strategy >= 2) {
+        // theta: slot 55 of the _qf row passes' partials, the blocks in order
+        const double theta = fold_blocks(d.partial + (long)w * d.nblk * KA + 55, sh.nblk, KA, 0.0, 0);
+        if (!world_A_quality(d, o, S, w, nside, P, theta, grad, Emu)) return;
+    } else if (d.opt.mu_strategy == 1) {
         // adaptive barrier (oracle/src/ipm.cpp, same order of decisions): free mode takes mu from
         // the LOQO oracle; the kkt-error globalisation switches to fixed (monotone) mode when E0 has
         // not fallen below 0.9999 x the largest of the last four, back once below the switch value.
@@ -1878,27 +1988,190 @@ __device__ inline void world_A_body(const NlpDev& d, WorldState& S, int w, int n
         S.mu = fmax(d.opt.tol / 10, fmin(d.opt.kappa_mu * S.mu, pow(S.mu, d.opt.theta_mu)));
         S.nfilt = 0;
     }
-    double M[NF * NF], rhs[NF];
-    int k = 0;
-    for (int p = 0; p < NF; p++)
-        for (int q = p; q < NF; q++) {
-            M[p * NF + q] = S.H[p * NF + q] + P[11 + k];
-            M[q * NF + p] = S.H[q * NF + p] + P[11 + k];
-            k++;
+    world_A_newton(d, S, P, grad);
+}
+
+// ------------------------------------------------------------------------------------------
+// The quality function's sigma search (strategies 2 and 3; oracle/src/ipm.cpp qf_sigma with qf_grid):
+// between pass A's world step and pass B, for the worlds whose mu waits for it (QfState::pending).
+// One workgroup per world sweeps the world's rows: once for a . dx_aff and a . dx_1 of every row
+// (kept in dslo / dshi, which are dead between pass D and pass B) and sum r_p^2; then, QF_TILE
+// candidates at a time, once for the fraction-to-boundary step sizes a_P, a_D of each candidate's
+// step dx_aff + mu_sigma dx_1 and once more for sum ((s + a_P ds)(z + a_D dz))^2 with them (not
+// expanded into moments: the square cancels where the affine step drives s z to 0). A thread takes
+// rows tid, tid + 256, ... of the world in every sweep, so it reads back only what it wrote itself,
+// and every sum is the thread's rows in order, then block_reduce_n's tree: a world's sums depend on
+// its own rows alone, whatever the batch, the list or the loop form.
+template <bool MX>
+__device__ __attribute__((always_inline)) void ipm_rows_Q_body(const NlpDev& d, const Round& r, const OptDev& o) {
+    if (r.lcount && blockIdx.x >= *r.lcount) return;
+    const int w = world_of(r, blockIdx.x);
+    const WorldState& S = d.ws[w];
+    if (S.status != 0) return;
+    const QfState& Q = o.qs[w];
+    if (!Q.pending) return;
+    const Shape sh = shape_of<MX>(d, w);
+    const long wb = (long)w * d.R;
+    __shared__ double lds[(ROW_THREADS / 64) * 2 * QF_TILE];
+    __shared__ double step[2 * QF_TILE];
+    double* out = o.qpart + (long)w * QP;
+    const double avg = Q.avg, tau_min = d.opt.tau_min;
+    const int G = o.qf_grid;
+    {
+        double dx0[NF], dx1[NF];
+#pragma unroll
+        for (int j = 0; j < NF; j++) { dx0[j] = Q.dx0[j]; dx1[j] = Q.dx1[j]; }
+        double np[1] = {0.0};
+        for (long row = threadIdx.x; row < sh.R; row += blockDim.x) {
+            const long i = wb + row;
+            const RowBounds B(d, sh, i, wb, (int)row);
+            const double slo = d.slo[B.lo], shi = d.shi[i];
+            double a[NF];
+            const double v = row_va(d, sh, S.cur, w, (int)row, S.x, a);
+            double u0 = 0, u1 = 0;
+#pragma unroll
+            for (int j = 0; j < NF; j++) { u0 += a[j] * dx0[j]; u1 += a[j] * dx1[j]; }
+            d.dslo[i] = u0;
+            d.dshi[i] = u1;
+            const double L = B.L(), U = B.U();
+            if (has_lo(d, L)) { const double rp = (v - L) - slo; np[0] += rp * rp; }
+            if (has_hi(d, U)) { const double rp = (U - v) - shi; np[0] += rp * rp; }
         }
-    for (int j = 0; j < NF; j++) rhs[j] = -grad[j] + S.mu * P[39 + j] - P[46 + j];
-    // inertia correction: shift the diagonal until the factorisation succeeds (bounded)
-    double shift = 0.0;
-    bool ok = false;
-    for (int tries = 0; tries < 40 && !ok; tries++) {
-        ok = chol_solve7(M, shift, rhs, S.dx);
-        shift = (shift == 0.0) ? 1e-8 : shift * 10;
+        const int kinds[1] = {0};
+        block_reduce_n(np, kinds, lds, out + 3 * QF_GMAX);
+        __syncthreads();
     }
-    if (!ok) {
-        for (int j = 0; j < NF; j++) S.dx[j] = 0.0;
-        S.status = 3;
+    const int m = sh.m;
+    for (int k0 = 0; k0 < G; k0 += QF_TILE) {
+        double mus[QF_TILE], tau[QF_TILE];
+#pragma unroll
+        for (int k = 0; k < QF_TILE; k++) {
+            mus[k] = o.sig[min(k0 + k, G - 1)] * avg;
+            tau[k] = fmax(tau_min, 1.0 - mus[k]);
+        }
+        double am[2 * QF_TILE];
+#pragma unroll
+        for (int k = 0; k < 2 * QF_TILE; k++) am[k] = 1.0;
+        for (long row = threadIdx.x; row < sh.R; row += blockDim.x) {
+            const long i = wb + row;
+            const RowBounds B(d, sh, i, wb, (int)row);
+            const double slo = d.slo[B.lo], zlo = d.zlo[B.lo], shi = d.shi[i], zhi = d.zhi[i];
+            const double u0 = d.dslo[i], u1 = d.dshi[i];
+            const double v = row < m ? d.g[gidx(d, S.cur, w, row)] : S.x[row - m];
+            const double L = B.L(), U = B.U();
+            if (has_lo(d, L)) {
+                const double rp = (v - L) - slo, sg = zlo / slo;
+#pragma unroll
+                for (int k = 0; k < QF_TILE; k++) {
+                    const double ds = (u0 + mus[k] * u1) + rp, dz = mus[k] / slo - zlo - sg * ds;
+                    if (ds < 0) am[2 * k] = fmin(am[2 * k], -tau[k] * slo / ds);
+                    if (dz < 0) am[2 * k + 1] = fmin(am[2 * k + 1], -tau[k] * zlo / dz);
+                }
+            }
+            if (has_hi(d, U)) {
+                const double rp = (U - v) - shi, sg = zhi / shi;
+#pragma unroll
+                for (int k = 0; k < QF_TILE; k++) {
+                    const double ds = -(u0 + mus[k] * u1) + rp, dz = mus[k] / shi - zhi - sg * ds;
+                    if (ds < 0) am[2 * k] = fmin(am[2 * k], -tau[k] * shi / ds);
+                    if (dz < 0) am[2 * k + 1] = fmin(am[2 * k + 1], -tau[k] * zhi / dz);
+                }
+            }
+        }
+        {
+            int kinds[2 * QF_TILE];
+#pragma unroll
+            for (int k = 0; k < 2 * QF_TILE; k++) kinds[k] = 2;
+            block_reduce_n(am, kinds, lds, step);
+            __syncthreads();
+        }
+        double ap[QF_TILE], ad[QF_TILE], cc[QF_TILE];
+#pragma unroll
+        for (int k = 0; k < QF_TILE; k++) { ap[k] = step[2 * k]; ad[k] = step[2 * k + 1]; cc[k] = 0; }
+        for (long row = threadIdx.x; row < sh.R; row += blockDim.x) {
+            const long i = wb + row;
+            const RowBounds B(d, sh, i, wb, (int)row);
+            const double slo = d.slo[B.lo], zlo = d.zlo[B.lo], shi = d.shi[i], zhi = d.zhi[i];
+            const double u0 = d.dslo[i], u1 = d.dshi[i];
+            const double v = row < m ? d.g[gidx(d, S.cur, w, row)] : S.x[row - m];
+            const double L = B.L(), U = B.U();
+            if (has_lo(d, L)) {
+                const double rp = (v - L) - slo, sg = zlo / slo;
+#pragma unroll
+                for (int k = 0; k < QF_TILE; k++) {
+                    const double ds = (u0 + mus[k] * u1) + rp, dz = mus[k] / slo - zlo - sg * ds;
+                    const double c = (slo + ap[k] * ds) * (zlo + ad[k] * dz);
+                    cc[k] += c * c;
+                }
+            }
+            if (has_hi(d, U)) {
+                const double rp = (U - v) - shi, sg = zhi / shi;
+#pragma unroll
+                for (int k = 0; k < QF_TILE; k++) {
+                    const double ds = -(u0 + mus[k] * u1) + rp, dz = mus[k] / shi - zhi - sg * ds;
+                    const double c = (shi + ap[k] * ds) * (zhi + ad[k] * dz);
+                    cc[k] += c * c;
+                }
+            }
+        }
+        // (every tile's slots lie inside the world's QP: k0 + QF_TILE <= QF_GMAX)
+        if (threadIdx.x < QF_TILE) {
+            out[QF_GMAX + k0 + threadIdx.x] = step[2 * threadIdx.x];
+            out[2 * QF_GMAX + k0 + threadIdx.x] = step[2 * threadIdx.x + 1];
+        }
+        const int kinds[QF_TILE] = {};
+        block_reduce_n(cc, kinds, lds, out + k0);
+        __syncthreads();
     }
 }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_Q(NlpDev d, Round r, OptDev o) { ipm_rows_Q_body<false>(d, r, o); }
+__global__ __launch_bounds__(ROW_THREADS) void ipm_rows_Q_mx(NlpDev d, Round r, OptDev o) { ipm_rows_Q_body<true>(d, r, o); }
+// the search's world step: the quality function of every candidate from ipm_rows_Q's sums, the first
+// argmin clipped to [sigma_min, sigma_max] as the oracle clips it, mu, the line-search filter cleared
+// if mu changed, then pass A's Newton solve at that mu (pass A's partials are still in place)
+template <bool MX>
+__device__ inline void world_Q_body(const NlpDev& d, const OptDev& o, WorldState& S, int w, int nside) {
+    if (S.status != 0) return;
+    QfState& Q = o.qs[w];
+    if (!Q.pending) return;
+    const Shape sh = shape_of<MX>(d, w);
+    if constexpr (MX) nside = 2 * d.nt + d.T * d.NJ * sh.O + 2 * 4 * NF + 2 * NF;
+    double P[NA], init[NA];
+    int op[NA];
+#pragma unroll
+    for (int k = 0; k < NA; k++) { init[k] = k == 54 ? 1e300 : 0; op[k] = (k >= 7 && k <= 9) ? 1 : k == 54 ? 2 : 0; }
+    world_partials(d, w, sh.nblk, init, op, P);
+    if (threadIdx.x != 0) return;
+    const double* grad = d.grad + ((long)S.cur * d.W + w) * NF;
+    const double* qp = o.qpart + (long)w * QP;
+    double nd = 0;
+    for (int j = 0; j < NF; j++) { const double rd = grad[j] - P[j]; nd += rd * rd; }
+    const int ns = nside > 0 ? nside : 1;
+    nd /= (double)NF;
+    const double np = qp[3 * QF_GMAX] / (double)ns;
+    const double avg = Q.avg, mu_min = qf_mu_min(d);
+    double best = 1.0, fb = 1e300;
+    for (int k = 0; k < o.qf_grid; k++) {
+        const double ap = qp[QF_GMAX + k], ad = qp[2 * QF_GMAX + k];
+        const double fq = (1 - ad) * (1 - ad) * nd + (1 - ap) * (1 - ap) * np + qp[k] / (double)ns;
+        if (fq < fb) { fb = fq; best = o.sig[k]; }
+    }
+    const double smin = fmax(1e-6, mu_min / avg), smax = fmin(100.0, Q.mu_max / avg);
+    const double sg = fmin(fmax(best, smin), fmax(smax, smin));
+    const double mu_old = S.mu;
+    S.mu = fmax(mu_min, fmin(qf_mu_grid(d, sg * avg), Q.mu_max));
+    if (S.mu != mu_old) S.nfilt = 0;
+    Q.pending = 0;
+    world_A_newton(d, S, P, grad);
+}
+template <bool MX>
+__device__ __attribute__((always_inline)) void ipm_world_Q_body(const NlpDev& d, const Round& r, int nside, const OptDev& o) {
+    if (r.lcount && blockIdx.x >= *r.lcount) return;
+    const int w = world_of(r, blockIdx.x);
+    world_step(d, true, w, 0, [&](WorldState& S) { world_Q_body<MX>(d, o, S, w, nside); });
+}
+__global__ __launch_bounds__(64) void ipm_world_Q(NlpDev d, Round r, int nside, OptDev o) { ipm_world_Q_body<false>(d, r, nside, o); }
+__global__ __launch_bounds__(64) void ipm_world_Q_mx(NlpDev d, Round r, int nside, OptDev o) { ipm_world_Q_body<true>(d, r, nside, o); }
 
 // pass B: step components, fraction to boundary, line-search ingredients. Held to four waves per
 // SIMD (128 VGPRs, 2 spilled): 3.66 ms per 327-world solve against 3.95 at three. ipm_rows_DA held
@@ -2233,13 +2506,67 @@ __device__ inline void world_Cs_body(const NlpDev& d, const Round& r, WorldState
     if (threadIdx.x == 0) S.spec_k = chosen;
 }
 
+// the trial point becomes the current one (lane 0, after the Hessian update)
+__device__ inline void world_D_accept(WorldState& S) {
+    for (int j = 0; j < NF; j++) S.x[j] = S.xt[j];
+    S.cur = 1 - S.cur;
+    S.nfail = S.accepted_ok ? 0 : S.nfail + 1;
+    S.iter++;
+    if (S.nfail >= 3) S.status = 3;
+}
+// Ipopt's limited-memory BFGS of the Lagrangian Hessian (armour_solver_options::lbfgs_history;
+// oracle/src/ipm.cpp lbfgs_hist, same order of decisions; lane 0): the pair (s, y) is skipped when
+// s'y <= sqrt(eps) |s| |y|, the history is dropped after more than two skips in a row, and S.H, the
+// matrix the Newton system reads, is rebuilt as sigma I followed by the stored pairs' BFGS updates,
+// oldest first, sigma = s'y / s's of the newest pair within [1e-8, 1e8]
+__device__ inline void lbfgs_rebuild(WorldState& S, const QfState& Q, double sigma) {
+    for (int i = 0; i < NF * NF; i++) S.H[i] = 0;
+    for (int j = 0; j < NF; j++) S.H[j * NF + j] = sigma;
+    for (int q = 0; q < Q.nlb; q++) {
+        const double* sv = Q.lb_s[q];
+        const double* y = Q.lb_y[q];
+        double Hs[NF], sHs = 0, sy = 0;
+        for (int i = 0; i < NF; i++) {
+            Hs[i] = 0;
+            for (int j = 0; j < NF; j++) Hs[i] += S.H[i * NF + j] * sv[j];
+            sHs += sv[i] * Hs[i];
+            sy += sv[i] * y[i];
+        }
+        for (int i = 0; i < NF; i++)
+            for (int j = 0; j < NF; j++) S.H[i * NF + j] += -Hs[i] * Hs[j] / sHs + y[i] * y[j] / sy;
+    }
+}
+__device__ inline void lbfgs_update(const OptDev& o, WorldState& S, QfState& Q, const double* sv, const double* y, double ss,
+                                    double sy) {
+    double yy = 0;
+    for (int j = 0; j < NF; j++) yy += y[j] * y[j];
+    if (sy <= sqrt(2.220446049250313e-16) * sqrt(ss) * sqrt(yy) || ss <= 0) {
+        if (++Q.lb_skips > 2) {
+            Q.nlb = 0;
+            Q.lb_skips = 0;
+            lbfgs_rebuild(S, Q, 1.0);
+        }
+        return;
+    }
+    Q.lb_skips = 0;
+    const int hist = min(o.lbfgs_history, LB_MAX);
+    if (Q.nlb >= hist) {  // the oldest pair leaves
+        for (int q = 0; q + 1 < Q.nlb; q++)
+            for (int j = 0; j < NF; j++) { Q.lb_s[q][j] = Q.lb_s[q + 1][j]; Q.lb_y[q][j] = Q.lb_y[q + 1][j]; }
+        Q.nlb = hist - 1;
+    }
+    for (int j = 0; j < NF; j++) { Q.lb_s[Q.nlb][j] = sv[j]; Q.lb_y[Q.nlb][j] = y[j]; }
+    Q.nlb++;
+    lbfgs_rebuild(S, Q, fmin(fmax(sy / ss, 1e-8), 1e8));
+}
+
 // pass D's world step (its rows: rows_DA_body): BFGS update, accept the trial point; every lane of
 // the wave calls it. The vectors and scalars are formed by every lane alike (the same arithmetic in the same order, so the
 // same values on every lane, at the cost of one lane), and lane l < 49 updates H's element l: the
 // update's 98 divisions run side by side instead of one after another on lane 0. Within the one
 // wave, every lane's reads of H precede the first write in program order.
 template <bool MX>
-__device__ inline void world_D_body(const NlpDev& d, WorldState& S, int w) {
+__device__ inline void world_D_body(const NlpDev& d, const OptDev& o, WorldState& S, int w) {
     if (S.status != 0) return;
     double wn[NF];
     const double init[NF] = {};
@@ -2256,6 +2583,12 @@ __device__ inline void world_D_body(const NlpDev& d, WorldState& S, int w) {
         ss += sv[j] * sv[j];
     }
     for (int j = 0; j < NF; j++) sy += sv[j] * y[j];
+    if (o.lbfgs_history > 0) {
+        if (lane != 0) return;
+        lbfgs_update(o, S, o.qs[w], sv, y, ss, sy);
+        world_D_accept(S);
+        return;
+    }
     double Hm[NF * NF];
 #pragma unroll
     for (int e = 0; e < NF * NF; e++) Hm[e] = S.H[e];
@@ -2302,25 +2635,21 @@ __device__ inline void world_D_body(const NlpDev& d, WorldState& S, int w) {
     if (lane < NF * NF) S.H[lane] = h;
     if (lane != 0) return;
     if (first) S.first_update = 0;
-    for (int j = 0; j < NF; j++) S.x[j] = S.xt[j];
-    S.cur = 1 - S.cur;
-    S.nfail = S.accepted_ok ? 0 : S.nfail + 1;
-    S.iter++;
-    if (S.nfail >= 3) S.status = 3;
+    world_D_accept(S);
 }
 // the fused passes' world step: D's (of the previous iteration), then A's, one wave
 template <bool MX>
-__device__ __attribute__((always_inline)) void ipm_world_DA_body(const NlpDev& d, const Round& r, int nside) {
+__device__ __attribute__((always_inline)) void ipm_world_DA_body(const NlpDev& d, const Round& r, int nside, const OptDev& o) {
     if (r.lcount && blockIdx.x >= *r.lcount) return;
     const int w = world_of(r, blockIdx.x);
     world_step(d, true, w, 0, [&](WorldState& S) {
-        world_D_body<MX>(d, S, w);
+        world_D_body<MX>(d, o, S, w);
         __syncthreads();  // lane 0's WorldState stores before every lane's reads in world_A_body
-        world_A_body<MX>(d, S, w, nside);
+        world_A_body<MX>(d, o, S, w, nside);
     });
 }
-__global__ __launch_bounds__(64) void ipm_world_DA(NlpDev d, Round r, int nside) { ipm_world_DA_body<false>(d, r, nside); }
-__global__ __launch_bounds__(64) void ipm_world_DA_mx(NlpDev d, Round r, int nside) { ipm_world_DA_body<true>(d, r, nside); }
+__global__ __launch_bounds__(64) void ipm_world_DA(NlpDev d, Round r, int nside, OptDev o) { ipm_world_DA_body<false>(d, r, nside, o); }
+__global__ __launch_bounds__(64) void ipm_world_DA_mx(NlpDev d, Round r, int nside, OptDev o) { ipm_world_DA_body<true>(d, r, nside, o); }
 
 // ------------------------------------------------------------------------------------------
 // Restoration phase (oracle/src/ipm.cpp restoration). A world whose line search
@@ -2414,10 +2743,18 @@ __device__ inline void resto_restart(const NlpDev& d, WorldState& S) {
     S.theta_max = -1;
     S.theta_min = -1;
     S.nfail = 0;
-    S.free_mode = d.opt.mu_strategy == 1 ? 1 : 0;
+    S.free_mode = d.opt.mu_strategy >= 1 ? 1 : 0;
     S.nref = 0;
     S.searching = 0;
     S.spec_k = -1;
+}
+// what the oracle resets beside it: the free-mode filter, the L-BFGS pairs and the skip count
+// (not mu_max)
+__device__ inline void resto_restart_options(QfState& Q) {
+    Q.ngf = 0;
+    Q.nlb = 0;
+    Q.lb_skips = 0;
+    Q.pending = 0;
 }
 
 // pass G's world step (lane 0 after the partials): ipm.cpp restoration's order of decisions
@@ -2481,7 +2818,7 @@ __device__ inline void resto_count(const NlpDev& d, bool mine, int flag) {
 }
 
 template <bool MX>
-__device__ __attribute__((always_inline)) void resto_world_G_body(const NlpDev& d, const Round& r) {
+__device__ __attribute__((always_inline)) void resto_world_G_body(const NlpDev& d, const Round& r, const OptDev& o) {
     if (r.lcount && blockIdx.x >= *r.lcount) return;  // (one-round search: no count published)
     const int w = world_of(r, blockIdx.x);
     const WorldState* const out = world_step(d, true, w, WS_RESTO, [&](WorldState& S) {
@@ -2499,11 +2836,12 @@ __device__ __attribute__((always_inline)) void resto_world_G_body(const NlpDev& 
             S.rpend = 0;
         }
         resto_step(d, S, P);
+        if (S.status == WS_RESTART) resto_restart_options(o.qs[w]);
     });
     if (threadIdx.x == 0 && r.rflag >= 0) resto_count(d, out->status == WS_RESTO, r.rflag);
 }
-__global__ __launch_bounds__(64) void resto_world_G(NlpDev d, Round r) { resto_world_G_body<false>(d, r); }
-__global__ __launch_bounds__(64) void resto_world_G_mx(NlpDev d, Round r) { resto_world_G_body<true>(d, r); }
+__global__ __launch_bounds__(64) void resto_world_G(NlpDev d, Round r, OptDev o) { resto_world_G_body<false>(d, r, o); }
+__global__ __launch_bounds__(64) void resto_world_G_mx(NlpDev d, Round r, OptDev o) { resto_world_G_body<true>(d, r, o); }
 
 // sum e^2 of one row block at a trial point into out; value(r) is constraint row r's value there
 template <typename F>

@@ -197,7 +197,8 @@ static std::atomic<int> g_planners[64];
     X(MOTION_CHUNKS, "motion_chunks")                                                              \
     X(TRACK_ROW, "track_row") X(TRACK_ROW_REC, "track_row_rec") X(TRACK_ROW_EPISODE, "track_row_episode") \
     X(TRACK_SERIAL, "track_serial") X(TRACK_SERIAL_REC, "track_serial_rec")                        \
-    X(TRACK_SERIAL_EPISODE, "track_serial_episode")
+    X(TRACK_SERIAL_EPISODE, "track_serial_episode")                                                \
+    X(SOLVE_QUALITY, "solve_quality") X(QF_SIGMA, "qf_sigma") X(HESS_LBFGS, "hess_lbfgs")
 enum PathId {
 #define X(id, name) PATH_##id,
     ARMOUR_PATHS(X)
@@ -254,7 +255,10 @@ struct Settings {
     bool eval_f32 = false;    // ARMOUR_EVAL_F32: fp32 constraint evaluation (tolerance study only)
     bool eval_full = false;   // ARMOUR_EVAL_FULL: always the full-capacity evaluation kernels
     int eval_skip = 0;        // ARMOUR_EVAL_SKIP: skips slicing (1) / collision rows (2), for part timings (NlpDev::diag)
-    int mu_strategy = -1;     // ARMOUR_MU_STRATEGY: 0 monotone, 1 any other value (adaptive), -1 unset: IpmOptions' default
+    // ARMOUR_MU_STRATEGY: 0 monotone, 2 quality, 3 quality-floor, 1 any other value (adaptive), -1 unset:
+    // IpmOpts' default; ARMOUR_QF_GRID, ARMOUR_LBFGS: the other two fields of armour_solver_options (-1 unset)
+    int mu_strategy = -1;
+    int qf_grid = -1, lbfgs = -1;
     int resto_max = -1;       // ARMOUR_RESTORATION: restoration phases per solve (0: none), -1 unset: the default
     bool plane_cache = true;  // ARMOUR_PLANE_CACHE=0: every evaluation on the full 36-plane scan
     int pc_k = PC_K;          // ARMOUR_PC_K (1..36): plane cache pool records per (link, obstacle) pair
@@ -298,7 +302,10 @@ struct Settings {
         s.eval_f32 = on(std::getenv("ARMOUR_EVAL_F32"));
         s.eval_full = on(std::getenv("ARMOUR_EVAL_FULL"));
         s.eval_skip = num(std::getenv("ARMOUR_EVAL_SKIP"), 0);
-        if (const char* e = std::getenv("ARMOUR_MU_STRATEGY")) s.mu_strategy = is(e, "monotone") ? 0 : 1;
+        if (const char* e = std::getenv("ARMOUR_MU_STRATEGY"))
+            s.mu_strategy = is(e, "monotone") ? 0 : is(e, "quality") ? 2 : is(e, "quality-floor") ? 3 : 1;
+        if (const char* e = std::getenv("ARMOUR_QF_GRID")) s.qf_grid = std::atoi(e);
+        if (const char* e = std::getenv("ARMOUR_LBFGS")) s.lbfgs = std::atoi(e);
         if (const char* e = std::getenv("ARMOUR_RESTORATION")) s.resto_max = std::max(std::atoi(e), 0);
         s.plane_cache = !off(std::getenv("ARMOUR_PLANE_CACHE"));
         s.pc_k = num(std::getenv("ARMOUR_PC_K"), PC_K);
@@ -368,6 +375,7 @@ struct armour_planner {
 
     // nlp
     NlpDev d;
+    OptDev od{};              // the optional solver configurations (solver_options_apply, init_solver)
     int* feas = nullptr;
     int* h_flags = nullptr;   // pinned host, mapped (NlpDev::flags)
     int* d_lists = nullptr;   // [6][max_worlds] active-world lists of the solver
@@ -640,6 +648,27 @@ static int init_reach(armour_planner* p) {
     return 0;
 }
 
+// armour_solver_options: the ranges (naming the field), and the options into the solver's own. The
+// sigma table is formed here with std::pow, as oracle/src/ipm.cpp forms it, so the kernels read the
+// oracle's bits. Nothing else depends on the options: no buffer, no loop variant.
+static int solver_options_check(const armour_planner* p, const armour_solver_options* o) {
+    if (o->mu_strategy < 0 || o->mu_strategy > 3) return fail(ARMOUR_E_ARG, "solver options: mu_strategy must lie in 0 .. 3");
+    if (o->qf_grid < 2 || o->qf_grid > QF_GMAX) return fail(ARMOUR_E_ARG, "solver options: qf_grid must lie in 2 .. 32");
+    if (o->lbfgs_history < 0 || o->lbfgs_history > LB_MAX)
+        return fail(ARMOUR_E_ARG, "solver options: lbfgs_history must lie in 0 .. 6");
+    const bool dflt = o->mu_strategy <= 1 && o->lbfgs_history == 0;
+    if (p->set.eval_f32 && !dflt)
+        return fail(ARMOUR_E_ARG, "solver options: strategies 2, 3 and lbfgs_history are not available with the fp32 study (ARMOUR_EVAL_F32)");
+    return 0;
+}
+static void solver_options_apply(armour_planner* p, const armour_solver_options& o) {
+    p->d.opt.mu_strategy = o.mu_strategy;
+    p->od.qf_grid = o.qf_grid;
+    p->od.lbfgs_history = o.lbfgs_history;
+    for (int k = 0; k < QF_GMAX; k++)
+        p->od.sig[k] = std::pow(10.0, -6.0 + 8.0 * std::min(k, o.qf_grid - 1) / (o.qf_grid - 1));
+}
+
 // planner_init, phase 3: the solver's arrays, its options and the loop variants it may take
 static int init_solver(armour_planner* p) {
     const Settings& set = p->set;
@@ -653,7 +682,16 @@ static int init_solver(armour_planner* p) {
     d.NJ = NJ;
     d.ro = p->ro;
     if (p->cfg.max_iter > 0) d.opt.max_iter = p->cfg.max_iter;
-    if (set.mu_strategy >= 0) d.opt.mu_strategy = set.mu_strategy;  // adaptive (default) or monotone
+    {
+        // the solver configuration the environment asks for (armour_main and armtd_main have no other
+        // way in), checked as armour_set_solver_options checks it
+        armour_solver_options so{d.opt.mu_strategy, 16, 0};
+        if (set.mu_strategy >= 0) so.mu_strategy = set.mu_strategy;
+        if (set.qf_grid >= 0) so.qf_grid = set.qf_grid;
+        if (set.lbfgs >= 0) so.lbfgs_history = set.lbfgs;
+        if ((rc = solver_options_check(p, &so))) return rc;
+        solver_options_apply(p, so);
+    }
     if (set.resto_max >= 0) d.opt.resto_max = set.resto_max;        // restoration phases per solve (0: none)
     d.armtd = p->armtd ? 1 : 0;
     d.nt = p->armtd ? 0 : NF * T;
@@ -682,6 +720,13 @@ static int init_solver(armour_planner* p) {
     if ((rc = p->alloc(&d.partial, (size_t)Wm * nblk_max * KA)) || (rc = p->alloc(&d.partial2, (size_t)Wm * nblk_max * KA2)) ||
         (rc = p->alloc(&d.ws, (size_t)Wm)) ||
         (rc = p->alloc(&p->feas, (size_t)Wm)))
+        return rc;
+    // the optional solver configurations' state (armour_solver_options), beside ws: per world the
+    // QfState, the free-mode filter sized by the iteration cap, and the sigma search's sums
+    OptDev& od = p->od;
+    od.gf_cap = d.opt.max_iter + 1;
+    if ((rc = p->alloc(&od.qs, (size_t)Wm)) || (rc = p->alloc(&od.gf, (size_t)Wm * 2 * od.gf_cap)) ||
+        (rc = p->alloc(&od.qpart, (size_t)Wm * QP)))
         return rc;
     // the solver's counts for the host live in mapped host memory (NlpDev::flags, FlagSlot): kernels
     // store them, the host reads them after an event or a synchronised round (no fill or copy per round)
@@ -1156,7 +1201,7 @@ static void launch_resto_round(armour_planner* p, hipStream_t s, int nb, const N
     p->took(s != p->stream ? PATH_RESTO_SECOND_STREAM : PATH_RESTO_SOLVER_STREAM);
     p->took(PATH_TRIALS_ALL);
     hipLaunchKernelGGL(KSEL(resto_rows_G), dim3(d.nblk, nb), dim3(ROW_THREADS), 0, s, d, r);
-    hipLaunchKernelGGL(KSEL(resto_world_G), dim3(nb), dim3(64), 0, s, d, r);
+    hipLaunchKernelGGL(KSEL(resto_world_G), dim3(nb), dim3(64), 0, s, d, r, p->od);
     hipLaunchKernelGGL(KSEL(eval_trials_all), dim3(p->T, nb), dim3(EVAL_THREADS), 0, s, d, r);
     hipLaunchKernelGGL(KSEL(resto_rows_Vs), dim3(d.nblk, nb * r.K), dim3(ROW_THREADS), 0, s, d, r);
     hipLaunchKernelGGL(KSEL(resto_world_Vs), dim3(nb), dim3(64), 0, s, d, r);
@@ -1257,6 +1302,7 @@ static int ipm_loop(armour_planner* p, int nrun) {
     int* Li[2] = {p->d_lists, p->d_lists + p->Wmax};                  // worlds of an iteration
     int* Ls[2] = {p->d_lists + 2 * p->Wmax, p->d_lists + 3 * p->Wmax};  // worlds of a line-search round
     const int ns = nside_count(p);
+    const bool qf = d.opt.mu_strategy >= 2;
     // Restoration phases inside the loop (with the speculative machinery): after an iteration's
     // interior-point launches, one phase iteration (run_resto's one-round form) for the worlds whose
     // line search failed and are still in their phase. Failures (accept_trial) and the worlds a
@@ -1382,15 +1428,24 @@ static int ipm_loop(armour_planner* p, int nrun) {
         p->took(tl ? PATH_IPM_ITER_TAIL : PATH_IPM_ITER_SYNC);
         // pass D of the previous iteration (accept its trial point) shares one sweep over the rows
         // with this iteration's pass A
+        // (strategies 2 and 3: the _qf instantiations, which also sum theta)
         if (it == 0) {
-            hipLaunchKernelGGL(KSEL(ipm_rows_A), dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, d, di);
-            hipLaunchKernelGGL(KSEL(ipm_world_A), dim3(nrun), dim3(64), 0, p->stream, d, di, ns);
+            hipLaunchKernelGGL(qf ? KSEL(ipm_rows_A_qf) : KSEL(ipm_rows_A), dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, d, di);
+            hipLaunchKernelGGL(KSEL(ipm_world_A), dim3(nrun), dim3(64), 0, p->stream, d, di, ns, p->od);
         } else {
             // the LDS-accumulator form for grids of several blocks per CU (nlp_kernels.hip rows_DA_body)
             const bool wide = p->set.da_lds && (long)d.nblk * nrun >= 4L * p->ncu;
             p->took(wide ? PATH_DA_LDS : PATH_DA_REGS);
-            hipLaunchKernelGGL(wide ? KSEL(ipm_rows_DA_lds) : KSEL(ipm_rows_DA), dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, d, di);
-            hipLaunchKernelGGL(KSEL(ipm_world_DA), dim3(nrun), dim3(64), 0, p->stream, d, di, ns);
+            auto rows_da = qf ? (wide ? KSEL(ipm_rows_DA_lds_qf) : KSEL(ipm_rows_DA_qf)) : (wide ? KSEL(ipm_rows_DA_lds) : KSEL(ipm_rows_DA));
+            hipLaunchKernelGGL(rows_da, dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, d, di);
+            hipLaunchKernelGGL(KSEL(ipm_world_DA), dim3(nrun), dim3(64), 0, p->stream, d, di, ns, p->od);
+        }
+        if (qf) {
+            // the sigma search of the worlds in free mode (QfState::pending), over the iteration's list
+            // with its device-side length like the passes around it: no host synchronisation
+            p->took(PATH_QF_SIGMA);
+            hipLaunchKernelGGL(KSEL(ipm_rows_Q), dim3(nrun), dim3(ROW_THREADS), 0, p->stream, d, di, p->od);
+            hipLaunchKernelGGL(KSEL(ipm_world_Q), dim3(nrun), dim3(64), 0, p->stream, d, di, ns, p->od);
         }
         const bool one = tl && p->spec_all && (p->set.tail_search == 2 || backtracked > 0);
         hipLaunchKernelGGL(KSEL(ipm_rows_B), dim3(d.nblk, nrun), dim3(ROW_THREADS), 0, p->stream, d, di);
@@ -1492,7 +1547,7 @@ static int run_resto(armour_planner* p, const int* list, int n) {
         p->took(PATH_RESTO_ROUNDS);
         p->took(PATH_RESTO_SOLVER_STREAM);
         hipLaunchKernelGGL(KSEL(resto_rows_G), dim3(d.nblk, n), dim3(ROW_THREADS), 0, p->stream, d, dr);
-        hipLaunchKernelGGL(KSEL(resto_world_G), dim3(n), dim3(64), 0, p->stream, d, dr);
+        hipLaunchKernelGGL(KSEL(resto_world_G), dim3(n), dim3(64), 0, p->stream, d, dr, p->od);
         HIPCK(hipStreamSynchronize(p->stream));
         if (fl[FLAG_RUN] == 0) break;
         for (int ls = 0; ls < d.opt.max_ls; ls++) {
@@ -1515,10 +1570,11 @@ static int run_solver(armour_planner* p) {
     int* Lr = p->d_lists + 2 * p->Wmax;     // worlds of a restoration phase
     ensure_plane_cache(p);
     const NlpDev& d = p->d;
-    p->took(d.opt.mu_strategy == 0 ? PATH_SOLVE_MONOTONE : PATH_SOLVE_ADAPTIVE);
+    p->took(d.opt.mu_strategy == 0 ? PATH_SOLVE_MONOTONE : d.opt.mu_strategy == 1 ? PATH_SOLVE_ADAPTIVE : PATH_SOLVE_QUALITY);
+    if (p->od.lbfgs_history > 0) p->took(PATH_HESS_LBFGS);
     Round r0;  // ipm_world_init fills the first iteration list with every world
     r0.wl_run = Li0;
-    hipLaunchKernelGGL(ipm_world_init, dim3((W + 63) / 64), dim3(64), 0, p->stream, d, r0);
+    hipLaunchKernelGGL(ipm_world_init, dim3((W + 63) / 64), dim3(64), 0, p->stream, d, r0, p->od);
     launch_eval(p, dim3(p->T, W), d, Round{}, EVAL_POINT);
     hipLaunchKernelGGL(KSEL(ipm_rows_init), dim3(d.nblk, W), dim3(ROW_THREADS), 0, p->stream, d, Round{});
     HIPCK(hipGetLastError());
@@ -2572,6 +2628,20 @@ int armour_get_path_counts(armour_planner* p, long long* counts, int n) {
 }
 
 const char* armour_path_name(int i) { return i >= 0 && i < PATH_N ? PATH_NAMES[i] : nullptr; }
+
+int armour_get_solver_options(const armour_planner* p, armour_solver_options* o) {
+    if (!p || !o) return fail(ARMOUR_E_ARG, "null argument");
+    *o = armour_solver_options{p->d.opt.mu_strategy, p->od.qf_grid, p->od.lbfgs_history};
+    return 0;
+}
+
+int armour_set_solver_options(armour_planner* p, const armour_solver_options* o) {
+    if (!p || !o) return fail(ARMOUR_E_ARG, "null argument");
+    if (int rc = solver_options_check(p, o)) return rc;
+    if (p->ep.on) return fail(ARMOUR_E_STATE, "solver options cannot change while an episode is active");
+    solver_options_apply(p, *o);
+    return 0;
+}
 
 int armour_get_reach_program(const armour_planner* p, int* codes, int capacity) {
     DeviceScope device_scope(p);

@@ -578,16 +578,39 @@ int armour_get_reach_profile(armour_planner* p, unsigned long long* cycles_terms
  *                     resto_one_round, resto_rounds (the search's form); resto_second_stream (queued beside
  *                     an interior-point iteration), resto_solver_stream
  *   restarts          ipm_restarts (worlds the host collected to restart the interior point)
- *   solves            solve_monotone, solve_adaptive (the barrier strategy)
+ *   solves            solve_monotone, solve_adaptive (the barrier strategy: 0, 1 of armour_solver_options)
  *   plane cache       pc_builds (first builds), pc_regrows (builds repeated on a larger pool), pc_fallbacks
  *                     (builds that left the solve on the full scan)
  *   candidates        cand_small, cand_full (calls by kernel), cand_chunks (candidate chunks, summed)
  *   motion check      motion_chunks (sample blocks per world, summed over calls and episode steps)
  *   tracking          track_row, track_row_rec, track_row_episode, track_serial, track_serial_rec,
- *                     track_serial_episode (launches of the plain, recording and episode kernels) */
-#define ARMOUR_PATH_COUNT 50
+ *                     track_serial_episode (launches of the plain, recording and episode kernels)
+ *   solver options    solve_quality (solves under barrier strategy 2 or 3), qf_sigma (launches of the
+ *                     quality function's sigma search, one per interior-point iteration of such a solve),
+ *                     hess_lbfgs (solves with the limited-memory BFGS); all zero on the default dispatch */
+#define ARMOUR_PATH_COUNT 53
 int armour_get_path_counts(armour_planner* p, long long* counts, int n);
 const char* armour_path_name(int i);
+/* The interior-point solver's configuration. The default is (1, 16, 0). The reference
+ * configures Ipopt with mu_strategy adaptive and hessian_approximation limited-memory
+ * (KPR/armour_main.cu:256-261), which with Ipopt's defaults is (2, -, 6); its sigma search is a golden
+ * section, here a fixed logarithmic grid of qf_grid points over [1e-6, 100].
+ * armour_set_solver_options takes effect from the next plan entry, on any planner (ARMTD included). It
+ * touches no batch state: the getters return what they returned before. ARMOUR_E_ARG, naming the field,
+ * for a value out of range, and for anything but strategies 0, 1 with lbfgs_history 0 under the fp32
+ * study (ARMOUR_EVAL_F32); ARMOUR_E_STATE while an episode is active. A planner is created with the
+ * configuration the environment names (ARMOUR_MU_STRATEGY = monotone | quality | quality-floor,
+ * ARMOUR_QF_GRID, ARMOUR_LBFGS), checked the same way. The options change plans. */
+typedef struct armour_solver_options {
+    int mu_strategy;    /* 0 monotone; 1 adaptive, LOQO / kkt-error, floor tol/10, mu grid (default);
+                           2 Ipopt's default adaptive pair: quality-function oracle + obj-constr-filter
+                             globalisation, mu_min 1e-11 (with lbfgs_history 6: the reference's configuration);
+                           3 the pair with the product's floor tol/10 and 2^(1/8) mu grid */
+    int qf_grid;        /* sigma candidates of the quality function, 2..32, default 16 (strategies 2, 3) */
+    int lbfgs_history;  /* 0 damped full BFGS (default); 1..6 Ipopt's limited-memory BFGS */
+} armour_solver_options;
+int armour_get_solver_options(const armour_planner* p, armour_solver_options* options);
+int armour_set_solver_options(armour_planner* p, const armour_solver_options* options);
 /* Certified plane cache of the current reach sets, built on demand: for k < n
  * writes [0] planes kept over all (world, t, link, obstacle) pairs, [1] pairs, [2] (world, t) blocks
  * whose cache region held every kept plane, [3] blocks, [4] most planes kept for one pair,
