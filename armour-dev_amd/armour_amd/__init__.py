@@ -118,6 +118,23 @@ class EpisodeTracked(ctypes.Structure):
                 ("max_robust", ctypes.c_double), ("flags", ctypes.c_int), ("flag_step", ctypes.c_int * 5)]
 
 
+class RoadmapConfig(ctypes.Structure):
+    """armour_roadmap_config (include/armour_hip.h)"""
+    _fields_ = [("num_nodes", ctypes.c_int), ("connect_radius", ctypes.c_double), ("edge_step", ctypes.c_double),
+                ("margin", ctypes.c_double)]
+
+
+class RoadmapStats(ctypes.Structure):
+    """armour_roadmap_stats (include/armour_hip.h)"""
+    _fields_ = [("free_nodes", ctypes.c_longlong), ("candidate_edges", ctypes.c_longlong), ("edges", ctypes.c_longlong),
+                ("edge_samples", ctypes.c_longlong), ("reachable", ctypes.c_longlong), ("relax_rounds_max", ctypes.c_int),
+                ("build_ms", ctypes.c_double * 4)]
+
+
+ROADMAP_MAX_NODES = 1023      # ARMOUR_ROADMAP_MAX_NODES
+ROADMAP_MIN_EDGE = 1e-6       # ARMOUR_ROADMAP_MIN_EDGE
+
+
 # ARMOUR_TRACK_COLLISION .. ARMOUR_TRACK_NOT_FINITE: the bits of armour_track_motion's flags
 TRACK_COLLISION, TRACK_INPUT, TRACK_BOUND, TRACK_LIMIT, TRACK_NOT_FINITE = 1, 2, 4, 8, 16
 
@@ -179,7 +196,14 @@ def lib():
                                                     ctypes.c_double, ctypes.c_int, ctypes.c_int,
                                                     ctypes.POINTER(TrackMotionOutput)]),
                            ("armour_episode_track", [ctypes.c_void_p, ctypes.POINTER(EpisodeTrackConfig)]),
-                           ("armour_episode_get_tracked", [ctypes.c_void_p, ctypes.POINTER(EpisodeTracked), _dp, ip, _dp])):
+                           ("armour_episode_get_tracked", [ctypes.c_void_p, ctypes.POINTER(EpisodeTracked), _dp, ip, _dp]),
+                           ("armour_roadmap_build", [ctypes.c_void_p, ctypes.POINTER(RoadmapConfig), _dp, _dp,
+                                                     ctypes.POINTER(RoadmapStats)]),
+                           ("armour_roadmap_get", [ctypes.c_void_p, ctypes.c_int, _dp, ip, ctypes.POINTER(ctypes.c_uint), _dp,
+                                                   ip]),
+                           ("armour_roadmap_waypoint", [ctypes.c_void_p, _dp, ctypes.c_double, _dp, ip, _dp]),
+                           ("armour_episode_roadmap", [ctypes.c_void_p, ctypes.POINTER(RoadmapConfig), _dp]),
+                           ("armour_episode_get_roadmap", [ctypes.c_void_p, ip, _dp])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = args
         for name, args in (("armour_check_world", [ctypes.POINTER(World), ctypes.c_int]),
@@ -227,6 +251,8 @@ ABI_SYMBOLS = ["armour_copy_bandwidth", "armour_create", "armour_create_robot", 
                "armour_eval_candidates", "armour_sq_selfcheck", "armour_check_world", "armour_check_armtd_world",
                "armour_check_motion", "armour_episode_begin", "armour_episode_step", "armour_episode_get",
                "armour_track", "armour_track_motion", "armour_episode_track", "armour_episode_get_tracked",
+               "armour_roadmap_build", "armour_roadmap_get", "armour_roadmap_waypoint", "armour_episode_roadmap",
+               "armour_episode_get_roadmap",
                "armour_get_path_counts", "armour_path_name", "armour_get_solver_options", "armour_set_solver_options"]
 
 
@@ -690,6 +716,61 @@ class Planner:
         out.update(true_state=true, last_flags=flags, rollout_ms=float(ms[0]), check_ms=float(ms[1]))
         return out
 
+    def _roadmap_inputs(self, name, nodes, connect_radius, edge_step, margin):
+        nodes = np.ascontiguousarray(nodes, dtype=np.float64)
+        if nodes.ndim != 3 or nodes.shape[0] != self._W or nodes.shape[2] != NF:
+            raise ValueError(f"{name}: nodes must have shape [{self._W}, N, {NF}], got {nodes.shape}")
+        self._roadmap_N = nodes.shape[1]
+        return nodes, RoadmapConfig(nodes.shape[1], float(connect_radius), float(edge_step), float(margin))
+
+    def roadmap_build(self, nodes, goals, connect_radius=1.0, edge_step=0.05, margin=0.02):
+        """armour_roadmap_build on the worlds of the last batch: nodes [W, N, 7], goals [W, 7] (each world's
+        goal becomes vertex N); returns the stats as a dict (build_ms: the four passes' device milliseconds)"""
+        nodes, cfg = self._roadmap_inputs("roadmap_build", nodes, connect_radius, edge_step, margin)
+        goals = np.ascontiguousarray(goals, dtype=np.float64)
+        if goals.shape != (self._W, NF):
+            raise ValueError(f"roadmap_build: goals must have shape [{self._W}, {NF}], got {goals.shape}")
+        st = RoadmapStats()
+        _check(lib().armour_roadmap_build(self.h, ctypes.byref(cfg), _ptr(nodes), _ptr(goals), ctypes.byref(st)))
+        out = {k: int(getattr(st, k)) for k, _ in RoadmapStats._fields_ if k != "build_ms"}
+        out["build_ms"] = np.array(st.build_ms[:])
+        return out
+
+    def roadmap(self, w):
+        """armour_roadmap_get: world w's graph as a dict: clearance, is_free, togo, next [N + 1] and adjacency
+        [N + 1, 32] uint32 words (bit j of row i: the edge exists)"""
+        V = getattr(self, "_roadmap_N", ROADMAP_MAX_NODES) + 1   # (before any build the library says so)
+        clr, togo = np.zeros(V), np.zeros(V)
+        free, nxt = np.zeros(V, dtype=np.int32), np.zeros(V, dtype=np.int32)
+        adj = np.zeros((V, 32), dtype=np.uint32)
+        _check(lib().armour_roadmap_get(self.h, int(w), _ptr(clr), _iptr(free), adj.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)),
+                                        _ptr(togo), _iptr(nxt)))
+        return dict(clearance=clr, is_free=free, adjacency=adj, togo=togo, next=nxt)
+
+    def roadmap_waypoint(self, q, lookahead=0.1):
+        """armour_roadmap_waypoint at q [W, 7]: (q_des [W, 7], entry [W] (-1: the straight-line waypoint),
+        path_left [W])"""
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        if q.shape != (self._W, NF):
+            raise ValueError(f"roadmap_waypoint: q must have shape [{self._W}, {NF}], got {q.shape}")
+        q_des, left = np.zeros((self._W, NF)), np.zeros(self._W)
+        entry = np.zeros(self._W, dtype=np.int32)
+        _check(lib().armour_roadmap_waypoint(self.h, _ptr(q), float(lookahead), _ptr(q_des), _iptr(entry), _ptr(left)))
+        return q_des, entry, left
+
+    def episode_roadmap(self, nodes, connect_radius=1.0, edge_step=0.05, margin=0.02):
+        """armour_episode_roadmap, after episode_begin and before the first step: from then on every waypoint
+        comes from the roadmap of nodes [W, N, 7] and the episode's goals; returns the states (episode_states)"""
+        nodes, cfg = self._roadmap_inputs("episode_roadmap", nodes, connect_radius, edge_step, margin)
+        _check(lib().armour_episode_roadmap(self.h, ctypes.byref(cfg), _ptr(nodes)))
+        return self.episode_states()
+
+    def episode_roadmap_state(self):
+        """armour_episode_get_roadmap: (entry [W], path_left [W]) of each world's last waypoint"""
+        entry, left = np.zeros(self._W, dtype=np.int32), np.zeros(self._W)
+        _check(lib().armour_episode_get_roadmap(self.h, _iptr(entry), _ptr(left)))
+        return entry, left
+
     def episode_states(self):
         """armour_episode_get: dict of arrays over the worlds (q, qd, qdd, q_des [W, 7], status, mode, steps,
         failed_plans, failed_streak [W], clearance [W], clearance_at [W, 3], goal_distance [W])"""
@@ -796,15 +877,36 @@ class Planner:
         return r
 
 
-def run_episodes(planner, worlds, goals, max_steps, track=None, **config):
+def roadmap_nodes(robot, q_start, goal, N, spread, rng):
+    """One recipe for the nodes of a roadmap, [N, 7]: node n is q_start + u_n Delta(q_start -> goal) +
+    spread g_n with u uniform on [0, 1] and g standard normal (Delta angle-wrapped on continuous joints,
+    state_lb <= -1000); limited joints are clipped to their limits. Uniform sampling of the
+    seven-dimensional box is hopeless at a thousand nodes, so this samples a tube round the straight
+    line: `spread` (radians) is how far it looks for a way round. robot: a table dict with state_lb and
+    state_ub (robot_tables); rng: a numpy Generator."""
+    q_start, goal = np.asarray(q_start, dtype=np.float64), np.asarray(goal, dtype=np.float64)
+    lb, ub = np.asarray(robot["state_lb"], dtype=np.float64)[:NF], np.asarray(robot["state_ub"], dtype=np.float64)[:NF]
+    cont = lb <= -1000.0
+    d = goal - q_start
+    d[cont] = (d[cont] + np.pi) % (2 * np.pi) - np.pi
+    nodes = q_start + rng.uniform(0.0, 1.0, (N, 1)) * d + spread * rng.standard_normal((N, NF))
+    nodes[:, ~cont] = np.clip(nodes[:, ~cont], lb[~cont], ub[~cont])
+    return nodes
+
+
+def run_episodes(planner, worlds, goals, max_steps, track=None, roadmap=None, **config):
     """Drive `worlds` toward `goals` [W, 7] with receding-horizon episodes on `planner` (episode_begin,
     then episode_step until no world runs or max_steps steps were taken; config: lookahead,
     goal_radius, check_samples). track (optional): the arguments of Planner.episode_track as a dict; the
-    true arms are then rolled along every executed segment. Returns dict(status, steps, clearance: [W]
+    true arms are then rolled along every executed segment. roadmap (optional): the arguments of
+    Planner.episode_roadmap as a dict (nodes [W, N, 7], connect_radius, edge_step, margin); the waypoints then
+    come from that roadmap instead of the straight line. Returns dict(status, steps, clearance: [W]
     each), and with track also tracked: the records (Planner.episode_tracked)."""
     st = planner.episode_begin(worlds, goals, **config)
     if track is not None:
         planner.episode_track(**track)
+    if roadmap is not None:
+        st = planner.episode_roadmap(**roadmap)
     running = int(np.sum(st["status"] == 0))
     for _ in range(int(max_steps)):
         if running == 0:
@@ -854,4 +956,4 @@ class ArmtdPlanner(Planner):
         return lib().armour_reach_armtd_batch(*a)
 
 
-__all__ = ["ArmtdPlanner", "Planner", "ArmourError", "ARMOUR_E_CAPACITY", "ARMOUR_E_INTERNAL", "copy_bandwidth", "default_batch", "make_world", "example_world", "csv_world", "straight_line_waypoint", "KINOVA", "LIB_PATH", "ABI_SYMBOLS", "candidates_array", "check_world", "check_armtd_world", "run_episodes", "EpisodeConfig", "EpisodeState", "T_PLAN", "EPISODE_STATUS", "TrackMotionOutput", "EpisodeTrackConfig", "EpisodeTracked"]
+__all__ = ["ArmtdPlanner", "Planner", "ArmourError", "ARMOUR_E_CAPACITY", "ARMOUR_E_INTERNAL", "copy_bandwidth", "default_batch", "make_world", "example_world", "csv_world", "straight_line_waypoint", "KINOVA", "LIB_PATH", "ABI_SYMBOLS", "candidates_array", "check_world", "check_armtd_world", "run_episodes", "EpisodeConfig", "EpisodeState", "T_PLAN", "EPISODE_STATUS", "TrackMotionOutput", "EpisodeTrackConfig", "EpisodeTracked", "RoadmapConfig", "RoadmapStats", "roadmap_nodes"]

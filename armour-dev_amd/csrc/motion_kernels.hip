@@ -96,6 +96,22 @@ __device__ __forceinline__ double motion_separation(const double* ob, const doub
     return top;
 }
 
+// one joint of the point forward kinematics: p += R trans_i, R = R (RPY_i Rot_axis_i(q_i)) with
+// cs = (cos q_j, sin q_j) pairs, and link i's box L[12] (centre, then the three generators). The block
+// check runs it on one thread, the roadmap's point check (roadmap_kernels.hip) on every lane.
+__device__ __forceinline__ void motion_link_box(const RobotParams& rp, int i, const double* cs, double* R, double* p, double* L) {
+    const double* tr = rp.trans + 3 * i;
+    for (int r = 0; r < 3; r++) p[r] += R[3 * r] * tr[0] + R[3 * r + 1] * tr[1] + R[3 * r + 2] * tr[2];
+    double Ri[9], Rn[9];
+    track_joint_rot(rp, i, cs, Ri);
+    mat3_mul(R, Ri, Rn);
+    for (int e = 0; e < 9; e++) R[e] = Rn[e];
+    for (int r = 0; r < 3; r++)
+        L[r] = p[r] + (R[3 * r] * rp.link_c[i][0] + R[3 * r + 1] * rp.link_c[i][1] + R[3 * r + 2] * rp.link_c[i][2]);
+    for (int j = 0; j < 3; j++)
+        for (int r = 0; r < 3; r++) L[3 + 3 * j + r] = R[3 * r + j] * rp.link_g[i][j];
+}
+
 // (value, index) ordered by value, then by index: the first minimiser
 __device__ inline bool motion_before(double v, int i, double bv, int bi) { return v < bv || (v == bv && i < bi); }
 // the wave's first minimum: every lane leaves with the winning (value, index)
@@ -177,19 +193,7 @@ __device__ __forceinline__ void motion_check_body(const MotionArgs& a, int w, lo
     if (tid == 0) {
         // the chain is sequential: one thread, 2 x NJ 3x3 products
         double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, p[3] = {0, 0, 0};
-        for (int i = 0; i < NJ; i++) {
-            const double* tr = rp.trans + 3 * i;
-            for (int r = 0; r < 3; r++) p[r] += R[3 * r] * tr[0] + R[3 * r + 1] * tr[1] + R[3 * r + 2] * tr[2];
-            double Ri[9], Rn[9];
-            track_joint_rot(rp, i, &s_cs[0][0], Ri);
-            mat3_mul(R, Ri, Rn);
-            for (int e = 0; e < 9; e++) R[e] = Rn[e];
-            double* L = s_link[i];
-            for (int r = 0; r < 3; r++)
-                L[r] = p[r] + (R[3 * r] * rp.link_c[i][0] + R[3 * r + 1] * rp.link_c[i][1] + R[3 * r + 2] * rp.link_c[i][2]);
-            for (int j = 0; j < 3; j++)
-                for (int r = 0; r < 3; r++) L[3 + 3 * j + r] = R[3 * r + j] * rp.link_g[i][j];
-        }
+        for (int i = 0; i < NJ; i++) motion_link_box(rp, i, &s_cs[0][0], R, p, s_link[i]);
     }
     __syncthreads();
     double best = INFINITY;

@@ -22,6 +22,7 @@
 #include "reach_kernel.hip"
 #include "lane_kernel.hip"
 #include "motion_kernels.hip"
+#include "roadmap_kernels.hip"
 #include "track_kernels.hip"
 #include "robots.h"
 
@@ -157,6 +158,7 @@ struct Episode : ExecState {
     EpisodeDev dev{};
     int* accept = nullptr;
     std::vector<armour_episode_state> host;  // the states after the last begin / step
+    std::vector<double> goals;               // [W][NF] of the last begin (armour_episode_roadmap's vertex N)
 };
 // armour_episode_track: what a tracked episode keeps between steps (the true arms' states, their scales,
 // the worlds' records), for grow.cap = max_worlds x num_samples rollouts
@@ -166,6 +168,26 @@ struct TrackedEpisode : ExecState {
     int steps = 0;
     double *state = nullptr, *scale = nullptr;
     bool scaled = false;
+};
+
+// armour_roadmap_* and armour_episode_roadmap (roadmap_kernels.hip): the per-vertex arrays for grow.cap =
+// worlds x vertices, the edge list for edges.cap candidate edges and a byte per interior sample for
+// samples.cap of them (the host reads the build's totals and sizes the two)
+struct Roadmap : ExecState {
+    bool valid = false;    // armour_roadmap_build .. any other batch entry
+    bool episode = false;  // the running episode takes its waypoints from it (armour_episode_roadmap)
+    RoadmapDev dev{};
+    GrowSet edges, samples;
+    hipEvent_t bev[7] = {};
+    double *verts = nullptr, *q = nullptr, *q_des = nullptr, *left = nullptr, *ep_left = nullptr;
+    int *row_eoff = nullptr, *row_soff = nullptr, *entry = nullptr, *ep_entry = nullptr;
+    void release_all() {
+        release();
+        edges.release();
+        samples.release();
+        for (hipEvent_t e : bev)
+            if (e) (void)hipEventDestroy(e);
+    }
 };
 
 // planners alive per device (armour_create / armour_destroy): the bundle kernel's shape depends on
@@ -413,6 +435,7 @@ struct armour_planner {
     TrueArmCheck tracked;
     Episode ep;
     TrackedEpisode ept;
+    Roadmap roadmap;
     std::vector<void*> allocs;
     long long paths[PATH_N] = {};  // the path census (armour_get_path_counts)
     void took(PathId c, long long n = 1) { paths[c] += n; }
@@ -1760,6 +1783,7 @@ void armour_destroy(armour_planner* p) {
     for (void* a : p->allocs) (void)hipFree(a);
     p->cand.release();
     for (ExecState* x : std::initializer_list<ExecState*>{&p->motion, &p->track, &p->tracked, &p->ep, &p->ept}) x->release();
+    p->roadmap.release_all();
     if (p->h_flags) (void)hipHostFree(p->h_flags);
     if (p->h_sum) (void)hipHostFree(p->h_sum);
     if (p->h_ws) (void)hipHostFree(p->h_ws);
@@ -1828,6 +1852,7 @@ static int run_batch(armour_planner* p, BatchKind kind, bool plan, int W, const 
         return fail(ARMOUR_E_ARG, plan ? "an ARMTD planner takes armour_armtd_world (armour_plan_armtd_batch)"
                                        : "an ARMTD planner takes armour_armtd_world (armour_reach_armtd_batch)");
     p->reached = p->planned = p->evaluated = p->ep.on = false;
+    p->roadmap.valid = p->roadmap.episode = false;
     auto t0 = std::chrono::steady_clock::now();
     const int rc = kind == BATCH_ARMTD ? upload_armtd(p, W, (const armour_armtd_world*)worlds)
                                        : upload_worlds(p, W, (const armour_world*)worlds, kind == BATCH_MIXED);
@@ -2256,6 +2281,234 @@ int armour_track_motion(armour_planner* p, const double* traj, int S, const doub
     return elapsed_ms(k.ev[0], k.ev[1], &out->check_ms);
 }
 
+// ---- the roadmap high-level planner (roadmap_kernels.hip) ----
+static int roadmap_check_config(const armour_roadmap_config* c) {
+    if (c->num_nodes < 2 || c->num_nodes > ARMOUR_ROADMAP_MAX_NODES)
+        return fail(ARMOUR_E_ARG, "num_nodes must lie in 2 .. ARMOUR_ROADMAP_MAX_NODES");
+    if (!std::isfinite(c->connect_radius) || !(c->connect_radius > 0.0 && c->connect_radius <= 100.0))
+        return fail(ARMOUR_E_ARG, "connect_radius must be finite and lie in (0, 100]");
+    if (!std::isfinite(c->edge_step) || !(c->edge_step > 0.0)) return fail(ARMOUR_E_ARG, "edge_step must be finite and positive");
+    if (c->connect_radius / c->edge_step > 4096.0) return fail(ARMOUR_E_ARG, "connect_radius / edge_step must be at most 4096");
+    if (!std::isfinite(c->margin) || !(c->margin >= 0.0)) return fail(ARMOUR_E_ARG, "margin must be finite and at least 0");
+    return 0;
+}
+
+// The build on the resident worlds (upload_worlds has run): vertices, candidate edges, edge samples,
+// adjacency, cost-to-go. On any failure the previous roadmap is gone and nothing else has changed.
+static int roadmap_build(armour_planner* p, const armour_roadmap_config* cfg, const double* nodes, const double* goals,
+                         armour_roadmap_stats* stats) {
+    Roadmap& rm = p->roadmap;
+    const int W = p->W, N = cfg->num_nodes, V = N + 1;
+    int rc = 0;
+    if ((rc = check_values("nodes", nodes, W * N * NF, ARMOUR_MAX_ABS_ANGLE))) return rc;
+    if ((rc = check_values("goals", goals, W * NF, ARMOUR_MAX_ABS_ANGLE))) return rc;
+    rm.valid = false;
+    const size_t rows = (size_t)W * V;
+    std::vector<double> verts(rows * NF);
+    for (int w = 0; w < W; w++) {
+        std::memcpy(&verts[(size_t)w * V * NF], nodes + (size_t)w * N * NF, sizeof(double) * N * NF);
+        std::memcpy(&verts[((size_t)w * V + N) * NF], goals + (size_t)w * NF, sizeof(double) * NF);
+    }
+    RoadmapDev& r = rm.dev;
+    const size_t Wm = (size_t)p->Wmax;
+    if ((rc = rm.grow.reserve(p->stream, (long)rows,
+                              {GrowSet::buf(rm.verts, rows * NF), GrowSet::buf(r.clr, rows), GrowSet::buf(r.free, rows),
+                               GrowSet::buf(r.adj, rows * ROADMAP_WORDS), GrowSet::buf(r.togo, rows), GrowSet::buf(r.next, rows),
+                               GrowSet::buf(r.row_edges, rows), GrowSet::buf(r.row_samples, rows), GrowSet::buf(rm.row_eoff, rows + 1),
+                               GrowSet::buf(rm.row_soff, rows + 1), GrowSet::buf(r.stats, (size_t)ROADMAP_STATS),
+                               GrowSet::buf(rm.q, Wm * NF), GrowSet::buf(rm.q_des, Wm * NF), GrowSet::buf(rm.entry, Wm),
+                               GrowSet::buf(rm.left, Wm), GrowSet::buf(rm.ep_entry, Wm), GrowSet::buf(rm.ep_left, Wm)},
+                              "hipMalloc failed for the roadmap's buffers (worlds x vertices)")))
+        return rc;
+    for (hipEvent_t& e : rm.bev)
+        if (!e) HIPCK(hipEventCreate(&e));
+    r.m = motion_args(p, 1, nullptr, nullptr, nullptr);
+    r.N = N;
+    r.V = V;
+    r.radius = cfg->connect_radius;
+    r.step = cfg->edge_step;
+    r.margin = cfg->margin;
+    r.verts = rm.verts;
+    r.row_eoff = rm.row_eoff;
+    r.row_soff = rm.row_soff;
+    r.E = 0;
+    hipStream_t st = p->stream;
+    HIPCK(hipMemcpyAsync(rm.verts, verts.data(), sizeof(double) * verts.size(), hipMemcpyHostToDevice, st));
+    HIPCK(hipMemsetAsync(r.stats, 0, sizeof(unsigned long long) * ROADMAP_STATS, st));
+    HIPCK(hipMemsetAsync(r.adj, 0, sizeof(unsigned) * rows * ROADMAP_WORDS, st));
+    const dim3 vg((V + ROADMAP_THREADS - 1) / ROADMAP_THREADS, W), tb(ROADMAP_THREADS);
+    HIPCK(hipEventRecord(rm.bev[0], st));
+    hipLaunchKernelGGL(roadmap_vertex_kernel, vg, tb, 0, st, r);
+    HIPCK(hipEventRecord(rm.bev[1], st));
+    hipLaunchKernelGGL(roadmap_edges_kernel<false>, vg, tb, 0, st, r);
+    HIPCK(hipEventRecord(rm.bev[2], st));
+    HIPCK(hipGetLastError());
+    // the host scans the rows' counts: the edge list is in (world, i, j) order whatever ran first
+    std::vector<int> cnt(2 * rows), off(2 * (rows + 1));
+    HIPCK(hipMemcpyAsync(cnt.data(), r.row_edges, sizeof(int) * rows, hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(cnt.data() + rows, r.row_samples, sizeof(int) * rows, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    long long E = 0, S = 0, world_samples = 0, most = 0;
+    for (size_t i = 0; i < rows; i++) {
+        if (i % V == 0) world_samples = 0;
+        off[i] = (int)E;
+        off[rows + 1 + i] = (int)S;
+        E += cnt[i];
+        S += cnt[rows + i];
+        world_samples += cnt[rows + i];
+        most = std::max(most, world_samples);
+        if (E > INT_MAX || S > INT_MAX)
+            return fail(ARMOUR_E_CAPACITY, "the roadmap's candidate edges or edge samples exceed 2^31 - 1");
+    }
+    off[rows] = (int)E;
+    off[2 * rows + 1] = (int)S;
+    const size_t ne = (size_t)E, ns = (size_t)S;
+    if ((rc = rm.edges.reserve(st, (long)E, {GrowSet::buf(r.e_row, ne), GrowSet::buf(r.e_j, ne), GrowSet::buf(r.e_n, ne),
+                                            GrowSet::buf(r.e_soff, ne)},
+                               "hipMalloc failed for the roadmap's edge list (candidate edges)")))
+        return rc;
+    if ((rc = rm.samples.reserve(st, (long)S, {GrowSet::buf(r.ok, ns)}, "hipMalloc failed for the roadmap's edge samples")))
+        return rc;
+    r.E = (int)E;
+    HIPCK(hipMemcpyAsync(rm.row_eoff, off.data(), sizeof(int) * (rows + 1), hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(rm.row_soff, off.data() + rows + 1, sizeof(int) * (rows + 1), hipMemcpyHostToDevice, st));
+    HIPCK(hipEventRecord(rm.bev[3], st));
+    if (E > 0) hipLaunchKernelGGL(roadmap_edges_kernel<true>, vg, tb, 0, st, r);
+    HIPCK(hipEventRecord(rm.bev[4], st));
+    if (S > 0)
+        hipLaunchKernelGGL(roadmap_sample_kernel, dim3((unsigned)((most + ROADMAP_THREADS - 1) / ROADMAP_THREADS), W), tb, 0, st, r);
+    if (E > 0) hipLaunchKernelGGL(roadmap_fold_kernel, dim3((unsigned)((E + ROADMAP_THREADS - 1) / ROADMAP_THREADS)), tb, 0, st, r);
+    HIPCK(hipEventRecord(rm.bev[5], st));
+    hipLaunchKernelGGL(roadmap_togo_kernel, dim3(W), dim3(ROADMAP_MAX_V), 0, st, r);
+    HIPCK(hipEventRecord(rm.bev[6], st));
+    HIPCK(hipGetLastError());
+    unsigned long long hs[ROADMAP_STATS];
+    HIPCK(hipMemcpyAsync(hs, r.stats, sizeof(hs), hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));  // (also: `verts`, `off` outlive their copies)
+    if (stats) {
+        stats->free_nodes = (long long)hs[ROADMAP_STAT_FREE];
+        stats->candidate_edges = E;
+        stats->edges = (long long)hs[ROADMAP_STAT_EDGES];
+        stats->edge_samples = S;
+        stats->reachable = (long long)hs[ROADMAP_STAT_REACHABLE];
+        stats->relax_rounds_max = (int)hs[ROADMAP_STAT_ROUNDS];
+        double a = 0, b = 0;
+        for (double& ms : stats->build_ms) ms = 0.0;  // (a failed read leaves 0)
+        (void)elapsed_ms(rm.bev[0], rm.bev[1], &stats->build_ms[0]);
+        (void)elapsed_ms(rm.bev[1], rm.bev[2], &a);
+        (void)elapsed_ms(rm.bev[3], rm.bev[4], &b);
+        stats->build_ms[1] = a + b;
+        (void)elapsed_ms(rm.bev[4], rm.bev[5], &stats->build_ms[2]);
+        (void)elapsed_ms(rm.bev[5], rm.bev[6], &stats->build_ms[3]);
+    }
+    rm.valid = true;
+    return 0;
+}
+
+static void launch_roadmap_waypoint(armour_planner* p, const RoadmapQuery& y) {
+    hipLaunchKernelGGL(roadmap_waypoint_kernel, dim3(p->W), dim3(ROADMAP_THREADS), 0, p->stream, p->roadmap.dev, y);
+}
+// the episode's query: the states' own q and q_des; kind null: the running worlds (armour_episode_roadmap)
+static RoadmapQuery roadmap_episode_query(armour_planner* p, const int* kind) {
+    RoadmapQuery y{};
+    y.lookahead = p->ep.dev.lookahead;
+    y.st = p->ep.dev.st;
+    y.kind = kind;
+    y.entry = p->roadmap.ep_entry;
+    y.path_left = p->roadmap.ep_left;
+    return y;
+}
+
+int armour_roadmap_build(armour_planner* p, const armour_roadmap_config* cfg, const double* nodes, const double* goals,
+                         armour_roadmap_stats* stats) {
+    DeviceScope device_scope(p);
+    if (!p || !cfg || !nodes || !goals) return fail(ARMOUR_E_ARG, "null planner / cfg / nodes / goals");
+    if (int rc = not_available(p, "the roadmap is")) return rc;
+    if (int rc = roadmap_check_config(cfg)) return rc;
+    if (!p->reached) return fail(ARMOUR_E_STATE, "no batch: call a reach or plan entry first");
+    if (p->ep.on && p->roadmap.episode)
+        return fail(ARMOUR_E_STATE, "the running episode takes its waypoints from the roadmap (armour_episode_roadmap)");
+    return roadmap_build(p, cfg, nodes, goals, stats);
+}
+
+static int no_roadmap() {
+    return fail(ARMOUR_E_STATE, "no roadmap: call armour_roadmap_build first (any other batch entry invalidates one)");
+}
+
+int armour_roadmap_get(armour_planner* p, int w, double* node_clearance, int* is_free, unsigned* adjacency, double* togo,
+                       int* next) {
+    DeviceScope device_scope(p);
+    if (!p) return fail(ARMOUR_E_ARG, "null planner");
+    if (!p->roadmap.valid) return no_roadmap();
+    if (w < 0 || w >= p->W) return fail(ARMOUR_E_ARG, "world index out of range");
+    const RoadmapDev& r = p->roadmap.dev;
+    const size_t V = (size_t)r.V, at = (size_t)w * V;
+    hipStream_t st = p->stream;
+    if (node_clearance) HIPCK(hipMemcpyAsync(node_clearance, r.clr + at, sizeof(double) * V, hipMemcpyDeviceToHost, st));
+    if (is_free) HIPCK(hipMemcpyAsync(is_free, r.free + at, sizeof(int) * V, hipMemcpyDeviceToHost, st));
+    if (adjacency)
+        HIPCK(hipMemcpyAsync(adjacency, r.adj + at * ROADMAP_WORDS, sizeof(unsigned) * V * ROADMAP_WORDS, hipMemcpyDeviceToHost, st));
+    if (togo) HIPCK(hipMemcpyAsync(togo, r.togo + at, sizeof(double) * V, hipMemcpyDeviceToHost, st));
+    if (next) HIPCK(hipMemcpyAsync(next, r.next + at, sizeof(int) * V, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int armour_roadmap_waypoint(armour_planner* p, const double* q, double lookahead, double* q_des, int* entry,
+                            double* path_left) {
+    DeviceScope device_scope(p);
+    if (!p || !q) return fail(ARMOUR_E_ARG, "null planner / q");
+    if (!std::isfinite(lookahead) || !(lookahead > 0.0)) return fail(ARMOUR_E_ARG, "lookahead must be finite and positive");
+    if (!p->roadmap.valid) return no_roadmap();
+    const int W = p->W;
+    if (int rc = check_values("q", q, W * NF, ARMOUR_MAX_ABS_ANGLE)) return rc;
+    Roadmap& rm = p->roadmap;
+    hipStream_t st = p->stream;
+    HIPCK(hipMemcpyAsync(rm.q, q, sizeof(double) * W * NF, hipMemcpyHostToDevice, st));
+    RoadmapQuery y{};
+    y.lookahead = lookahead;
+    y.q = rm.q;
+    y.q_des = rm.q_des;
+    y.entry = rm.entry;
+    y.path_left = rm.left;
+    launch_roadmap_waypoint(p, y);
+    HIPCK(hipGetLastError());
+    if (q_des) HIPCK(hipMemcpyAsync(q_des, rm.q_des, sizeof(double) * W * NF, hipMemcpyDeviceToHost, st));
+    if (entry) HIPCK(hipMemcpyAsync(entry, rm.entry, sizeof(int) * W, hipMemcpyDeviceToHost, st));
+    if (path_left) HIPCK(hipMemcpyAsync(path_left, rm.left, sizeof(double) * W, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    return 0;
+}
+
+static int episode_read(armour_planner* p);
+int armour_episode_roadmap(armour_planner* p, const armour_roadmap_config* cfg, const double* nodes) {
+    DeviceScope device_scope(p);
+    if (!p || !cfg || !nodes) return fail(ARMOUR_E_ARG, "null planner / cfg / nodes");
+    if (int rc = not_available(p, "the roadmap is")) return rc;
+    if (int rc = roadmap_check_config(cfg)) return rc;
+    if (!p->ep.on) return no_episode();
+    if (p->ep.stepped) return fail(ARMOUR_E_STATE, "the episode has taken a step: the roadmap is given before the first step");
+    p->roadmap.episode = false;
+    if (int rc = roadmap_build(p, cfg, nodes, p->ep.goals.data(), nullptr)) return rc;
+    launch_roadmap_waypoint(p, roadmap_episode_query(p, nullptr));
+    HIPCK(hipGetLastError());
+    if (int rc = episode_read(p)) return rc;
+    p->roadmap.episode = true;
+    return 0;
+}
+
+int armour_episode_get_roadmap(armour_planner* p, int* entry, double* path_left) {
+    DeviceScope device_scope(p);
+    if (!p) return fail(ARMOUR_E_ARG, "null planner");
+    if (!p->ep.on) return no_episode();
+    if (!p->roadmap.episode) return fail(ARMOUR_E_STATE, "the episode has no roadmap: call armour_episode_roadmap after armour_episode_begin");
+    const Roadmap& rm = p->roadmap;
+    if (entry) HIPCK(hipMemcpyAsync(entry, rm.ep_entry, sizeof(int) * p->W, hipMemcpyDeviceToHost, p->stream));
+    if (path_left) HIPCK(hipMemcpyAsync(path_left, rm.ep_left, sizeof(double) * p->W, hipMemcpyDeviceToHost, p->stream));
+    HIPCK(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
 static int episode_read(armour_planner* p) {
     p->ep.host.resize(p->W);
     HIPCK(hipMemcpyAsync(p->ep.host.data(), p->ep.dev.st, sizeof(armour_episode_state) * p->W, hipMemcpyDeviceToHost, p->stream));
@@ -2273,6 +2526,7 @@ int armour_episode_begin(armour_planner* p, int W, const armour_world* worlds, c
         return fail(ARMOUR_E_ARG, "episode config: lookahead > 0, goal_radius >= 0, 2 <= check_samples <= 65535");
     if (W <= 0 || W > p->Wmax) return fail(ARMOUR_E_ARG, "num_worlds out of range");
     p->reached = p->planned = p->evaluated = p->ep.on = false;
+    p->roadmap.valid = p->roadmap.episode = false;
     int rc = 0;
     if ((rc = check_values("goals", goals, W * NF, ARMOUR_MAX_ABS_ANGLE))) return rc;
     // the worlds' q_des is ignored: the waypoints are written on the device
@@ -2304,6 +2558,7 @@ int armour_episode_begin(armour_planner* p, int W, const armour_world* worlds, c
     if ((rc = episode_read(p))) return rc;  // (also: `goals` is the caller's, its copy has finished)
     p->ep.on = true;
     p->ept.on = p->ep.stepped = false;
+    p->ep.goals.assign(goals, goals + (size_t)W * NF);
     return 0;
 }
 
@@ -2443,6 +2698,7 @@ int armour_episode_step(armour_planner* p, const int* reject, armour_result* res
     launch_motion(p, e.exec, e.win, 0.0, 0.0, e.S);
     HIPCK(hipEventRecord(ev[2], p->stream));
     hipLaunchKernelGGL(episode_advance_kernel, wg, wb, 0, p->stream, e);
+    if (p->roadmap.episode) launch_roadmap_waypoint(p, roadmap_episode_query(p, e.kind));
     HIPCK(hipEventRecord(ev[3], p->stream));
     HIPCK(hipGetLastError());
     p->ep.stepped = true;

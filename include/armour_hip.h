@@ -520,6 +520,90 @@ int armour_episode_track(armour_planner* p, const armour_episode_track_config* c
 int armour_episode_get_tracked(armour_planner* p, armour_episode_tracked* records, double* true_state, int* flags,
                                double* ms);
 
+/* The roadmap high-level planner: a joint-space graph per world and the waypoint taken from it, on the
+ * device. The shape of simulator/planners/high_level_planners/robot_arm_sampling_based_HLP.m (nodes in
+ * joint space, a collision check per node, a neighbour graph, the shortest path, the waypoint at the
+ * lookahead distance along its polyline; robot_arm_PRM_HLP.m is the neighbour-radius variant). The
+ * reference's PRM checks nodes only; here every edge is sampled and checked as well, a deliberate
+ * strengthening. The caller supplies the nodes (how to sample them is host policy); the library does the
+ * checking, the graph and the waypoint. Without these calls every episode, plan and getter is bit for bit
+ * what it is without them.
+ *
+ * Conventions. Joint j is continuous when state_lb[j] <= -1000 (the straight-line waypoint's rule).
+ *   Delta(a->b)_j = b_j - a_j, wrapped to [-pi, pi) on continuous joints; d(a, b) = sqrt(sum_j Delta_j^2),
+ *   summed in joint order 0..6; the point at fraction s of the segment is a + s Delta(a->b).
+ *   clr(q) is the clearance of a configuration: the minimum over (link, obstacle) of the separation of
+ *   armour_check_motion, link boxes from its point forward kinematics, the world's own obstacles: exactly
+ *   what armour_check_motion returns for the constant trajectory (q, 0, 0, k = 0) at t0 = 0 with
+ *   samples = 1. A world without obstacles: +infinity.
+ * Vertices. Each world has N caller nodes, nodes [W][N][7], index 0 .. N - 1; the library appends the
+ *   world's goal as vertex N. 2 <= N <= ARMOUR_ROADMAP_MAX_NODES (1024 vertices: a world's adjacency
+ *   matrix is 1024 x 1024 bits). free[i] = clr(v_i) > margin.
+ * Edge (i, j), i < j: a candidate when both vertices are free and ARMOUR_ROADMAP_MIN_EDGE <= d(v_i, v_j)
+ *   <= connect_radius. It has n = ceil(d / edge_step) pieces and the interior samples
+ *   v_i + (s / n) Delta(v_i->v_j), s = 1 .. n - 1, always from the lower index to the higher. The edge
+ *   exists when every interior sample has clr > margin; its weight is d(v_i, v_j), lower index first.
+ * Cost-to-go. togo[N] = 0 when the goal is free; otherwise togo[i] = min_j fl(d(i, j) + togo[j]) over the
+ *   existing edges of i, +infinity when the goal cannot be reached or i is not free (a goal that is not
+ *   free: every togo is +infinity). next[i] is the lowest j that attains the minimum, next[N] = N,
+ *   unreachable vertices get -1. Floating-point addition is monotone, so the fixed point reached from
+ *   +infinity does not depend on the relaxation schedule and a Dijkstra with the same additions finds it.
+ *   With connect_radius <= 100 and the minimum edge length togo strictly decreases along next.
+ * Waypoint at q. Entry candidates are the free vertices i with finite togo[i] and d(q, v_i) <=
+ *   connect_radius whose segment q -> v_i is free: ceil(d / edge_step) pieces, every interior sample with
+ *   clr > margin (q itself is not tested; d = 0 has no samples). entry = argmin fl(d(q, v_i) + togo[i]),
+ *   ties to the lowest i. No candidate: entry = -1, path_left = +infinity and q_des is the straight-line
+ *   waypoint of the episodes, bit for bit. Otherwise walk q -> entry -> next -> ... -> goal with
+ *   r = lookahead from pos = q: on a leg a -> b of length d, r > d: pos += Delta(a->b), r -= d; else
+ *   pos += (r / d) Delta(a->b) and stop (at most N + 1 legs). At the goal the walk stops (the reference
+ *   clamps there too) and q_des is its position: q plus the legs' Deltas. path_left = fl(d(q, entry) +
+ *   togo[entry]).
+ *
+ * armour_roadmap_build serves the worlds of the last batch, uniform or mixed, after any reach or plan
+ * entry (ARMOUR_E_STATE before any batch, as armour_check_motion), with goals [W][7]. It touches no plan
+ * or episode state. stats (optional): vertex and edge totals over the worlds, the largest number of
+ * relaxation rounds that changed a value, and the device milliseconds of [0] the vertex pass, [1] the
+ * candidate passes, [2] the edge samples and their fold, [3] the cost-to-go. Another batch entry
+ * invalidates the roadmap: armour_roadmap_get and armour_roadmap_waypoint then return ARMOUR_E_STATE.
+ * armour_roadmap_get: world w's arrays, all optional: node_clearance, is_free, togo, next [N + 1];
+ * adjacency [N + 1][32] 32-bit words, bit j of row i set for an existing edge, in both directions.
+ * armour_roadmap_waypoint: q [W][7] (finite, within ARMOUR_MAX_ABS_ANGLE), lookahead > 0; q_des [W][7],
+ * entry [W], path_left [W] (each optional).
+ * armour_episode_roadmap is called after armour_episode_begin and before the first step, in either order
+ * with armour_episode_track: it builds the roadmap from the episode's obstacles and goals, rewrites the
+ * q_des of every running world with the roadmap waypoint at its q, and from then on step (c) takes the
+ * next waypoint from the roadmap (episode_ms[1] includes it). Frozen worlds are untouched. A new
+ * armour_episode_begin ends it. armour_episode_state keeps its layout; armour_episode_get_roadmap gives
+ * the entry and the path left of each world's last waypoint (-1 and +infinity: the straight line, or a
+ * world that was frozen from the start). While an episode uses a roadmap, armour_roadmap_build returns
+ * ARMOUR_E_STATE.
+ *
+ * ARMOUR_E_ARG, naming the field and before any device work: a null pointer; num_nodes out of range;
+ * connect_radius, edge_step or margin not finite; connect_radius outside (0, 100]; edge_step <= 0;
+ * connect_radius / edge_step > 4096; margin < 0; a node or goal that is not finite or lies beyond
+ * ARMOUR_MAX_ABS_ANGLE; an ARMTD planner; the fp32 study (ARMOUR_EVAL_F32). A build whose candidate edges
+ * or edge samples exceed 2^31 - 1 is ARMOUR_E_CAPACITY, a failed allocation ARMOUR_E_HIP: in both cases
+ * the previous roadmap, if any, is gone and nothing else has changed. */
+#define ARMOUR_ROADMAP_MAX_NODES 1023
+#define ARMOUR_ROADMAP_MIN_EDGE 1e-6
+typedef struct armour_roadmap_config {
+    int num_nodes;
+    double connect_radius, edge_step, margin;
+} armour_roadmap_config;
+typedef struct armour_roadmap_stats {
+    long long free_nodes, candidate_edges, edges, edge_samples, reachable;
+    int relax_rounds_max;
+    double build_ms[4];
+} armour_roadmap_stats;
+int armour_roadmap_build(armour_planner* p, const armour_roadmap_config* cfg, const double* nodes, const double* goals,
+                         armour_roadmap_stats* stats);
+int armour_roadmap_get(armour_planner* p, int w, double* node_clearance, int* is_free, unsigned* adjacency, double* togo,
+                       int* next);
+int armour_roadmap_waypoint(armour_planner* p, const double* q, double lookahead, double* q_des, int* entry,
+                            double* path_left);
+int armour_episode_roadmap(armour_planner* p, const armour_roadmap_config* cfg, const double* nodes);
+int armour_episode_get_roadmap(armour_planner* p, int* entry, double* path_left);
+
 /* Outputs of world w of the last batch (the armour_*.out payloads, armour_main.cu:340-398) */
 int armour_get_constraints(armour_planner* p, int w, double* g);              /* m values at k_opt (m_w of world w) */
 int armour_get_link_centers(armour_planner* p, int w, double* centers);       /* [T][NJ][3] sliced at the
